@@ -10,7 +10,7 @@ state Quantizer._forward (ant_quantization/antquant/quant_modules.py:535-551) th
 One STEP = one pass over all `nbuf` tensors = ONE launch of the batched entry point
 (antq_fakequant_batch); the set (nbuf x 33.5 MB in, same out) is far larger than the 256 MB
 Infinity Cache, so everything streams from / to HBM.  The same pass issued as one launch per
-tensor (antq_fakequant, the reference's granularity) is timed too and reported in
+tensor (antq_fakequant, the reference's granularity) is timed too with --full and reported in
 config.per_tensor_launches.
 Inputs are resident in HBM before the timed region.  Weak scaling: every rank owns its own
 `nbuf` tensors, there is no data-path collective; ranks only meet at the barriers that
@@ -24,11 +24,20 @@ bracket the timed region and at the MAX-reduction of the elapsed time.
 Rank 0 prints ONE JSON line.  `roofline.achieved` = algorithmic bytes of one launch (4 B/elem:
 read bf16 + write bf16, x nbuf x 16.7 M elements) / average duration of that launch, measured
 here with HIP events recorded on the launch stream around the timed region (which consists of
-exactly `steps` launches of that kernel).  `roofline.copy_ceiling` is the empirical ceiling SURVEY 8d
-asks for: a plain 16-byte-per-lane nontemporal copy kernel and hipMemcpyDtoD over the same buffers,
-timed right after the timed region.  `cpu_baseline` times the CPU oracle (oracle/antq_oracle.c, a
-literal restatement of the reference's op sequence: "port") with OpenMP on all host cores (and on
-one); `cpu_baseline_torch` is the same op sequence as PyTorch CPU ops.
+exactly `steps` launches of that kernel).
+
+A plain run does only that: set up, bring the GPU to steady clocks (>= 0.3 s of the timed step),
+the `warmup` + `steps` launches, the line.  `--full` adds everything else, each measured in runs of
+its own: the per-tensor launches, the idempotence spot check, `roofline.copy_ceiling` (the empirical
+ceiling SURVEY 8d asks for: a plain 16-byte-per-lane nontemporal copy kernel and hipMemcpyDtoD over
+the same buffers, timed right after the timed region), `roofline.traffic` (two rocprofv3 --pmc child
+passes), `config.configs[]` and the CPU baselines: `cpu_baseline` times the CPU oracle
+(oracle/antq_oracle.c, a literal restatement of the reference's op sequence: "port") with OpenMP on
+all host cores (and on one); `cpu_baseline_torch` is the same op sequence as PyTorch CPU ops.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last step computed as DIR/outputs.npy
+(float32; rank 0's tensors; when they do not all fit in 32 MB, a fixed, seeded sample of the rows of
+every output tensor), so that two builds can be compared output for output on identical inputs.
 
 ANTQ_BENCH_SELFTEST=1 (tests/test_sharding_gloo.py): the rank / barrier / MAX-over-ranks / report
 logic below runs unchanged on CPU over gloo with a stub in place of the GPU workload, so that the
@@ -48,6 +57,7 @@ HBM_PEAK_GBPS = 8000.0           # MI355X HBM3E spec peak (/opt/skills/guides/MI
 ROWS = COLS = 4096
 BYTES_PER_ELEM = 4               # algorithmic: read one bf16 + write one bf16
 METRIC = "Gelements/s quant-dequant + achieved HBM GB/s %peak, 4-bit ANT, 1/8 MI355X"
+DUMP_ELEMS = 8 << 20             # --dump-outputs: at most 32 MB of float32
 
 
 # ------------------------------------------------------------------------------------------------
@@ -133,6 +143,24 @@ class Harness:
         if self.dist is not None:
             self.dist.barrier()
             self.dist.destroy_process_group()
+
+
+def dump_outputs(torch, outs, path):
+    """DIR/outputs.npy: the output tensors of the timed step as float32 (bf16 -> f32 is exact), stacked when they share one
+    shape.  When they do not fit in DUMP_ELEMS, the same number of rows of every tensor, picked once by a fixed seed."""
+    import numpy as np
+    k = max(1, DUMP_ELEMS // sum(o.shape[-1] for o in outs))
+    rng = np.random.default_rng(0)
+    parts = []
+    for o in outs:
+        o = o.reshape(-1, o.shape[-1])
+        if o.shape[0] > k:
+            rows = torch.from_numpy(np.sort(rng.choice(o.shape[0], k, replace=False))).to(o.device)
+            o = o.index_select(0, rows)
+        parts.append(o.float().cpu().numpy())
+    same = len({p.shape for p in parts}) == 1
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "outputs.npy"), np.stack(parts) if same else np.concatenate([p.reshape(-1) for p in parts]))
 
 
 def per_rank_stats(values, digits=2):
@@ -402,7 +430,8 @@ def build_headline(args, h, _lib, grids):
                 workload="headline: %d x [4096,4096] bf16 weight tensors per GPU, ANT 4-bit signed flint grid, calibrated per-row "
                          "alpha, steady-state _forward; one step = ONE batched launch (antq_fakequant_batch) over all %d "
                          "tensors" % (args.nbuf, args.nbuf),
-                sharding="independent tensors per rank, no data-path collective", keep=(x_slab, out_slab, xs, alphas, outs, batch))
+                sharding="independent tensors per rank, no data-path collective", outputs=outs,
+                keep=(x_slab, out_slab, xs, alphas, outs, batch))
 
 
 def build_model(args, h, _lib, grids):
@@ -447,7 +476,7 @@ def build_model(args, h, _lib, grids):
                 workload="%s%s; OliVe 4-bit flint + outliers with outlier-victim pairs, alpha = 3 sigma per row, bf16%s; one step = "
                          "ONE batched launch per rank over its %d units" % (what, " (%d layers)" % args.layers if args.layers else "",
                                                                            ", quantised in place (from the second step on the input is the previous step's output -- a fixed point of the quantiser: same bytes moved, already-quantised values)" if inplace else "", len(ws)),
-                sharding="%d units on rank 0 of %d ranks, no data-path collective" % (len(ws), h.world),
+                sharding="%d units on rank 0 of %d ranks, no data-path collective" % (len(ws), h.world), outputs=outs,
                 keep=(ws, outs, alphas, batch, dst))
 
 
@@ -693,11 +722,15 @@ def main():
                          "Linear weights sharded over the ranks, strong scaling")
     ap.add_argument("--layers", type=int, default=0, help="model workloads: decoder layers (0 = the model's own depth)")
     ap.add_argument("--inplace", action="store_true", help="model workloads: out = x (llama70b always: 137 GB of weights)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc child passes (roofline.traffic falls back "
-                                                               "to the committed profiles/hbm_traffic.json value)")
-    ap.add_argument("--configs", default="all", help="headline workload at N = 1: which config.configs[] entries to time after "
-                                                     "the headline region: all | none | comma list of headline_olive,C1,C2,C3,C4")
+    ap.add_argument("--full", action="store_true", help="besides the headline: per-tensor launches, idempotence check, copy ceiling, "
+                                                        "HBM traffic, config.configs[], CPU baselines (each in runs of its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed (rank 0) "
+                                                          "to DIR/outputs.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baselines")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: skip the two rocprofv3 --pmc child passes (roofline.traffic "
+                                                               "falls back to the committed profiles/hbm_traffic.json value)")
+    ap.add_argument("--configs", default="all", help="--full, headline workload at N = 1: which config.configs[] entries to time "
+                                                     "after the headline region: all | none | comma list of headline_olive,C1,C2,C3,C4")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -738,13 +771,12 @@ def main():
             last = ev0.elapsed_time(ev1) * 1e-3 / per_call
         return last
 
-    # ---- setup pass: the same work as one launch per tensor (the reference's granularity).
-    # Reported beside the headline; it also keeps the GPU busy for >= 0.3 s before anything is timed,
-    # which is what it takes for an idle MI355X to reach steady clocks (the first ~50 ms of load run
-    # up to 20 % slower: tools/probe_clock_ramp.py).
-    if W["per_tensor"]:
-        pt_launch_s = event_time(W["per_tensor"][0], 0.3, 5) / args.nbuf
-        ptu_launch_s = event_time(W["per_tensor"][1], 0.15, 5) / args.nbuf
+    # ---- setup pass: keeps the GPU busy for >= 0.3 s before anything is timed, which is what it takes for an idle
+    # MI355X to reach steady clocks (the first ~50 ms of load run up to 20 % slower: tools/probe_clock_ramp.py).
+    # With --full it is the same work as one launch per tensor (the reference's granularity), reported beside the headline.
+    pt = None
+    if args.full and W["per_tensor"]:
+        pt = (event_time(W["per_tensor"][0], 0.3, 5) / args.nbuf, event_time(W["per_tensor"][1], 0.15, 5) / args.nbuf)
     else:
         event_time(step, 0.3, 1)
 
@@ -759,13 +791,41 @@ def main():
     fracs = [b / t / 1e9 / HBM_PEAK_GBPS for b, t in zip(bytes_all, launch_all)]
     worst = min(range(h.world), key=lambda r: fracs[r])
     achieved = bytes_all[worst] / launch_all[worst] / 1e9           # the SLOWEST rank's kernel (N = 1: the only one)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, W["outputs"], args.dump_outputs)
 
     # ---- parity spot check of what was just measured (cheap, outside the timed region) --------
-    ok = W["check"]()
+    ok = W["check"]() if args.full else None
 
     h.finish()                          # every rank is done; what follows is rank 0 describing its own GPU
     if rank != 0:
         return
+
+    config = {"workload": W["workload"], "io_dtype": "bf16", "elements_per_step_per_gpu": W["elems"],
+              "elements_per_step_per_rank": [int(b // BYTES_PER_ELEM) for b in bytes_all],
+              "sharding": W["sharding"]}
+    res = report(h, args, sum(bytes_all) / BYTES_PER_ELEM, elapsed, {
+        "config": config,
+        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                     "frac": round(achieved / HBM_PEAK_GBPS, 4),
+                     "kernel": W["kernel"], "launch_us": round(launch_all[worst] * 1e6, 2),
+                     "algorithmic_bytes_per_launch": int(bytes_all[worst]),
+                     "per_rank": {"what": "every rank's own launch duration (HIP events around its timed region) and its "
+                                          "algorithmic bytes / that duration / 8 TB/s; `achieved`, `frac`, `launch_us` above "
+                                          "are the slowest rank's (rank %d)" % worst,
+                                  "ranks": h.world, "launch_us": per_rank_stats([t * 1e6 for t in launch_all]),
+                                  "frac": per_rank_stats(fracs, 4)}},
+    }, scaling=W["scaling"])
+    if args.full:
+        config["idempotence_check"] = ok
+        full_sections(args, h, W, _lib, grids, event_time, res, pt, achieved, algo_bytes)
+    print(json.dumps(res), flush=True)
+
+
+def full_sections(args, h, W, _lib, grids, event_time, res, pt, achieved, algo_bytes):
+    """--full, rank 0, after the headline's timed region: the copy ceiling, the measured HBM traffic, the per-tensor
+    launches, config.configs[] and the CPU baselines, added to the line `res`."""
+    config, roofline = res["config"], res["roofline"]
 
     # ---- empirical ceiling on the same bytes (SURVEY 8d): plain copies in -> out, one launch each
     copy_bytes = W.get("copy_bytes", algo_bytes)
@@ -803,10 +863,8 @@ def main():
         except Exception:
             traffic = None
 
-    config = {"workload": W["workload"], "io_dtype": "bf16", "elements_per_step_per_gpu": W["elems"],
-              "elements_per_step_per_rank": [int(b // BYTES_PER_ELEM) for b in bytes_all],
-              "sharding": W["sharding"], "idempotence_check": ok}
-    if W["per_tensor"]:
+    if pt:
+        pt_launch_s, ptu_launch_s = pt
         config["per_tensor_launches"] = {
             "what": "the same pass as ONE LAUNCH PER TENSOR (antq_fakequant, the reference's granularity), %d independent weight "
                     "tensors back to back on one stream, each launch marked ANTQ_FLAG_UNORDERED (inputs at rest: its dispatch "
@@ -827,30 +885,18 @@ def main():
                 e["traffic"], e["traffic_source"] = traffic_olive
                 if e["traffic"]:
                     e["traffic_over_algorithmic"] = round(e["traffic"] / e["algorithmic_bytes"], 4)
-    res = report(h, args, sum(bytes_all) / BYTES_PER_ELEM, elapsed, {
-        "config": config,
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_note,
-                     "kernel": W["kernel"], "launch_us": round(launch_all[worst] * 1e6, 2),
-                     "algorithmic_bytes_per_launch": int(bytes_all[worst]),
-                     "per_rank": {"what": "every rank's own launch duration (HIP events around its timed region) and its "
-                                          "algorithmic bytes / that duration / 8 TB/s; `achieved`, `frac`, `launch_us` above "
-                                          "are the slowest rank's (rank %d)" % worst,
-                                  "ranks": h.world, "launch_us": per_rank_stats([t * 1e6 for t in launch_all]),
-                                  "frac": per_rank_stats(fracs, 4)},
-                     "copy_ceiling": {"antq_copy_GBps": round(copy_bytes / copy_s / 1e9, 1),
-                                      "hipMemcpyDtoD_GBps": round(copy_bytes / d2d_s / 1e9, 1),
-                                      "frac_of_copy_ceiling": round(achieved / ceiling, 4),
-                                      "what": "plain copy of %d bytes in -> out (one launch) on rank 0's GPU, timed after the "
-                                              "timed region" % (copy_bytes // 2)}},
-    }, scaling=W["scaling"])
+    roofline["traffic"], roofline["traffic_source"] = traffic, traffic_note
+    roofline["copy_ceiling"] = {"antq_copy_GBps": round(copy_bytes / copy_s / 1e9, 1),
+                                "hipMemcpyDtoD_GBps": round(copy_bytes / d2d_s / 1e9, 1),
+                                "frac_of_copy_ceiling": round(achieved / ceiling, 4),
+                                "what": "plain copy of %d bytes in -> out (one launch) on rank 0's GPU, timed after the "
+                                        "timed region" % (copy_bytes // 2)}
     if h.world == 1 and not args.no_cpu_baseline and args.workload == "headline":      # reported baselines, N=1 only
         res["cpu_baseline"] = cpu_baseline()
         phys = _physical_cores()
         if phys and phys < (os.cpu_count() or 1):      # SMT box: the same port with one thread per physical core beside it
             res["cpu_baseline_physical_cores"] = cpu_baseline(seconds_budget=2.0, threads=phys)
         res["cpu_baseline_torch"] = cpu_baseline_torch()
-    print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":

@@ -714,7 +714,7 @@ def test_histogram_clip_search_equals_direct_kernels_and_the_oracle(antq_lib, or
 
 
 def test_bench_sharded_workload_line_on_the_gpu(antq_lib, dev):
-    """`python bench.py --workload opt6.7b --layers 1` (BASELINE configs[3], shortened to one decoder layer): ONE JSON line,
+    """`python bench.py --full --workload opt6.7b --layers 1` (BASELINE configs[3], shortened to one decoder layer): ONE JSON line,
     strong scaling, the per-rank roofline block, algorithmic bytes = 4 B x the rank's elements, the kernel of the OliVe pairs."""
     import json
     import os
@@ -722,7 +722,7 @@ def test_bench_sharded_workload_line_on_the_gpu(antq_lib, dev):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "opt6.7b", "--layers", "1", "--steps", "10",
-                          "--warmup", "3", "--no-traffic"], capture_output=True, text=True, timeout=600)
+                          "--warmup", "3", "--full", "--no-traffic"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-800:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

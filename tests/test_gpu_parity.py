@@ -3061,13 +3061,14 @@ def test_calibrate_one_call_equals_the_stepwise_calibration_and_the_oracle(antq_
 
 
 def test_bench_line_contract_on_the_gpu(antq_lib, dev):
-    """`python bench.py` prints ONE JSON line with the driver's keys, the roofline object of the dominant kernel (live launch
-    time, algorithmic bytes, copy ceiling of the same process) and -- unless switched off -- the CPU baseline; K steps are timed."""
+    """`python bench.py --full` prints ONE JSON line with the driver's keys, the roofline object of the dominant kernel (live
+    launch time, algorithmic bytes, copy ceiling of the same process) and -- unless switched off -- the CPU baseline; K steps
+    are timed."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "12", "--warmup", "3", "--nbuf", "8"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "12", "--warmup", "3", "--nbuf", "8", "--full"],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-800:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -3088,6 +3089,43 @@ def test_bench_line_contract_on_the_gpu(antq_lib, dev):
     assert abs(r["launch_us"] - d["ms_per_step"] * 1e3) < 0.25 * r["launch_us"]
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["unit"] == "Gelem/s" and c["cores"] >= 1 and c["value"] > 0 and c["sample"]
+
+
+def test_bench_plain_line_and_dumped_outputs_on_the_gpu(antq_lib, dev, tmp_path):
+    """A plain `python bench.py` (no --full) times exactly K steps and prints the headline line without the --full sections;
+    `--dump-outputs DIR` writes what the last step computed (float32, <= 64 MB), the same from run to run whatever K, and it
+    is a fixed point of the quantiser at the same scales (fake-quant of a fake-quantised row returns the row)."""
+    import json
+    import subprocess
+    import sys
+    import torch
+    from ant_quantization_amd import grids
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for steps in (7, 3):
+        d_out = str(tmp_path / ("k%d" % steps))
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2",
+                              "--nbuf", "4", "--dump-outputs", d_out], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-800:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+            assert k in d, k
+        assert d["steps"] == steps and d["warmup"] == 2 and d["unit"] == "Gelem/s" and d["higher_is_better"] is True
+        assert abs(d["value"] - 4 * 4096 * 4096 / (d["ms_per_step"] * 1e-3) / 1e9) < 0.01 * d["value"]
+        assert "cpu_baseline" not in d and "configs" not in d["config"] and "per_tensor_launches" not in d["config"]
+        assert "copy_ceiling" not in d["roofline"] and "traffic" not in d["roofline"]
+        f = os.path.join(d_out, "outputs.npy")
+        assert os.path.getsize(f) <= 64 << 20
+        dumps.append(np.load(f))
+    a = dumps[0]
+    assert a.dtype == np.float32 and a.shape == (4, 512, 4096) and np.isfinite(a).all() and np.abs(a).max() > 0
+    assert np.array_equal(a, dumps[1])
+    x = torch.from_numpy(a.reshape(-1, 4096)).to(dev).to(torch.bfloat16)
+    alpha = x.float().abs().amax(1).contiguous()            # flint's largest value (10) times alpha / 10: the row's abs-max
+    y = antq_lib.fakequant(x, alpha, antq_lib.plan_for(grids.ant_flint(4, True)), 10.0, x.shape[0], 4096, True)
+    assert torch.equal(y, x)
 
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("ANTQ_FUZZ_SEEDS", 2))))

@@ -8,7 +8,7 @@ OUT=$REPO/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 for i in 1 2 3; do
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_driver_cmd_$i.json"
+  python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_driver_cmd_$i.json"
   python3 - "$OUT/${TAG}_bench_driver_cmd_$i.json" <<'PY'
 import json, sys
 j = json.load(open(sys.argv[1]))
@@ -23,9 +23,9 @@ for e in j["config"].get("configs", []):
           "  traffic x%.4f" % e["traffic_over_algorithmic"] if e.get("traffic_over_algorithmic") else ""))
 PY
 done
-python3 bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_driver_cmd.json"
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_driver_cmd.json"
 ( cd /tmp && rm -rf /tmp/prof_drv && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_drv -- \
-    python3 "$REPO/bench.py" --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/${TAG}_bench_driver_cmd_profiled.json" 2> /tmp/prof_drv.err )
+    python3 "$REPO/bench.py" --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > "$OUT/${TAG}_bench_driver_cmd_profiled.json" 2> /tmp/prof_drv.err )
 KT=$(find /tmp/prof_drv -name '*kernel_trace.csv' | head -1)
 KS=$(find /tmp/prof_drv -name '*kernel_stats.csv' | head -1)
 [ -n "$KS" ] && cp "$KS" "$OUT/${TAG}_bench_driver_cmd_kernel_stats.csv"
