@@ -8,7 +8,8 @@
 // (antq_k_hrow.h): out(x) = O_J, J = #{k : x >= X_k}, with the x-domain thresholds X_k = min{x : RN(x / s) >= T_k}
 // (x_threshold: exact) and O_j = fl32((v_j + 0) * s), so
 //     sum_x (O_J(x) - x)^2 = sum x^2 + n O_0^2 - 2 O_0 S + sum_k [ (O_{k+1}^2 - O_k^2) N_k - 2 (O_{k+1} - O_k) S_k ]
-// where N_k, S_k = count and sum of the elements at or above threshold k.  And as the candidate scale grows every threshold
+// where N_k, S_k = count and sum of the elements at or above threshold k (sweep_finish evaluates it around the cell that holds
+// zero: thresholds below zero with the count and sum of the elements BELOW them).  And as the candidate scale grows every threshold
 // moves monotonically (away from zero), so "x >= X_k(c)" flips AT MOST ONCE along the candidate list: an element contributes
 //   * one entry to a static histogram (its interval at the first candidate), and
 //   * one signed event (k, c*) per threshold that sweeps across it -- on average less than one --
@@ -71,7 +72,9 @@ __device__ __forceinline__ double sweep_term(float q, float d, float s, float xv
 {
     const float tt = (q - d) + d;
     const float df = fabsf(tt * s - xv);
-    return (double)(df * df);
+    // widened BEFORE squaring: a literal element's term is as exact as the closed form's terms around it (squared in float, a
+    // far-clipped element -- the largest term of its row -- carried a 2^-24 rounding into the row's sum, and 1e30 gave Inf)
+    return (double)df * (double)df;
 }
 
 // x in fixed point, units of 2^(ex - 38), as a 64-bit integer: |x| < 2^(ex + 8) -> |x * F| < 2^46, so adding 1.5 * 2^52 leaves
@@ -132,12 +135,20 @@ __device__ __forceinline__ void sweep_finish(uint32_t lane, uint32_t nthr, uint3
         const uint32_t cc = lane + 64u * h;
         if (cc < ncand) {
             const float s = sS[cc];
+            // Written around the cell that holds zero, as the sorted-row search writes it (antq_k_sortsearch.h): a threshold
+            // below zero counts the elements BELOW it (n - N_k, S_tot - S_k: exact integers).  Anchored at the most negative
+            // value O_0, n O_0^2 cancelled against the rest -- with OliVe's outlier values (16 x the largest normal one) that
+            // cost 5 digits of the double (measured 6e-11 against the exact sums on rows of 256 elements).
+            uint32_t b = 0;
+            while (b < nthr && sV[b] < 0.0f) b++;
+            const double Ob = (double)(sV[b] * s);
             double Op = (double)(sV[0] * s);
-            double sum = Q + (double)n_tot * Op * Op - 2.0 * Op * ((double)s_tot * unit);
+            double sum = Q + (double)n_tot * Ob * Ob - 2.0 * Ob * ((double)s_tot * unit);
             for (uint32_t k = 0; k < nthr; k++) {
                 const double On = (double)(sV[k + 1u] * s);
-                const double N = (double)sEn[k * cp + cc], S = (double)sEs[k * cp + cc] * unit;
-                sum += (On * On - Op * Op) * N - 2.0 * (On - Op) * S;
+                const long long en = (long long)sEn[k * cp + cc], es = sEs[k * cp + cc];
+                const double N = k >= b ? (double)en : -(double)(n_tot - en), S = (double)(k >= b ? es : -(s_tot - es)) * unit;
+                sum += (On - Op) * ((On + Op) * N - 2.0 * S);
                 Op = On;
             }
             sum += h ? exc1 : exc0;

@@ -117,3 +117,123 @@ def check_type_pick(key, got_mode, ref_mode, types, type_sums):
     gap = abs(sums[got_mode] - sums[ref_mode]) / sums[ref_mode]
     assert gap <= NEAR_TIE_RTOL, (key, "type %s vs reference %s, reference sums differ by %.3g" % (got_mode, ref_mode, gap))
     LEDGER.append(("type:" + str(key), 1, 0, float(gap)))
+
+
+# Bars of the GPU tests against the yardstick (tests/test_gpu_search_exact.py).  Each is derived from the worst relative
+# deviation measured on the MI355X over every (codebook, candidate, row) cell of every case, against the yardstick and never
+# against another kernel (profiles/search_exactness.md: 8.7e5 cells):
+#   closed forms (sorted-row search, sweep) vs `exact`: worst 2.0e-13 (rows of 256 elements under OliVe's codebooks, where a few
+#     exactly-represented outliers make sum x^2 a thousand times the sum of squared errors: 2^-53 times that condition
+#     number).  8 x worst = 1.6e-12 exceeds the ceiling of 1e-12 -- the point where a single misplaced element of a
+#     16 384-wide row (1 %-quantile 1.6e-10) stops being resolved with two orders of margin -- so the ceiling is the bar.
+#   histogram search vs `terms32`: worst 1.4e-15, bar 8 x, rounded up.
+#   direct kernels vs `terms32`: worst 1.3e-7 (ANT) / 1.5e-7 (OliVe): they add a lane's float32 terms in float32.  Bar 2 x.
+EXACT_RTOL = 1e-12                  # sorted-row search and sweep vs `exact`
+EXACT_RTOL_FAR_STATISTIC = 7e-14    # ... the named row whose statistic lies 2^15 and more above its elements (worst 8.2e-15)
+HIST_RTOL = 2e-14                   # histogram search vs `terms32`
+DIRECT_RTOL = 3e-7                  # direct kernels vs `terms32`, ANT codebooks
+DIRECT_RTOL_OLIVE = 3e-7            # direct kernels vs `terms32`, OliVe codebooks
+
+
+def exact_sse(oracle, x2d_f32, xmax, ratios, grid, gmax, ovp, per_row):
+    """The yardstick of every clip-search kernel: the float64 sums of squared errors of the oracle's per-element outputs.
+
+    For every candidate c:  alpha = fl32(xmax * ratios[c])  (the reference's scale, `ratios_of`),  out = oracle.forward(x, alpha),
+    d = fl32(out - x).  Returns two float64 arrays [ncand, rows] (per_row) or [ncand, 1] (one scale for the tensor):
+      exact   = sum of float64(d)^2             -- what the closed forms of the sorted-row search and the sweep stand for
+      terms32 = sum of float64(fl32(d * d))     -- what the direct kernels and the histogram search stand for, and what the
+                                                   reference's *_traces64.npz record (its float32 element terms, mean in float64)
+    Both sums are numpy's float64 pairwise sums over a row (error <= log2(n) * 2^-53 relative on non-negative terms).  A
+    16-bit tensor enters as its float32 image.  NaN / Inf / zero-statistic rows give what the float64 arithmetic gives."""
+    x = np.ascontiguousarray(x2d_f32, dtype=np.float32)
+    assert x.ndim == 2
+    rows = x.shape[0]
+    na = rows if per_row else 1
+    xmax = np.asarray(xmax, dtype=np.float32).reshape(-1)
+    assert xmax.size == na, (xmax.size, na)
+    ratios = np.asarray(ratios, dtype=np.float32).reshape(-1)
+    exact = np.empty((ratios.size, na), dtype=np.float64)
+    terms32 = np.empty((ratios.size, na), dtype=np.float64)
+    with np.errstate(all="ignore"):
+        for c in range(ratios.size):
+            alpha = (xmax * ratios[c]).astype(np.float32)
+            if per_row and rows == 1:        # (oracle.forward reads a single alpha as one scale for the tensor: the same thing)
+                alpha = alpha[:1]
+            out = oracle.forward(x, alpha, grid, gmax, ovp, want_idx=False)[0]
+            d = (out - x).astype(np.float32)
+            d64 = d.astype(np.float64)
+            t32 = (d * d).astype(np.float32).astype(np.float64)
+            if per_row:
+                exact[c], terms32[c] = (d64 * d64).sum(axis=1), t32.sum(axis=1)
+            else:
+                exact[c, 0], terms32[c, 0] = (d64 * d64).sum(), t32.sum()
+    return exact, terms32
+
+
+def _three_sigma_reference(x, per_row):
+    """OliVe's clip statistic in the reference's own op sequence (OQ:193-195 / :213-215: torch float32 mean, std, 3 * std, sum,
+    difference).  The recorded scores depend on this float32 value to the bit, and a float64 restatement of it lands one ulp
+    away on about half of the rows -- so the statistic (an INPUT of the search, not the thing under test) is restated with
+    the library the recorder ran: torch on the CPU."""
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    if per_row:
+        mean, std = t.view(t.shape[0], -1).mean(dim=-1), t.view(t.shape[0], -1).std(dim=-1)
+    else:
+        mean, std = t.mean(), t.std()
+    return torch.maximum((mean + 3 * std).abs(), (mean - 3 * std).abs()).reshape(-1).numpy().astype(np.float32)
+
+
+def _absmax(x, per_row):
+    return (np.abs(x).max(1) if per_row else np.abs(x).max(keepdims=True).reshape(1)).astype(np.float32)
+
+
+def restated_traces64(oracle, path):
+    """Every calibration recorded in one tests/golden/*_traces64.npz, restated as the arguments of its FINAL clip search
+    (the one on the installed grid): a list of dicts with key, x [rows, K] float32, xmax, lo / up / step, ratios, grid, gmax,
+    ovp, per_row and trace64 [ncand, rows or 1] (the reference's float32 element terms, averaged in float64).
+    OliVe: grid = the normal values followed by the outliers, gmax = normal.max(), 3-sigma statistic under the pair rule and
+    abs-max without outliers (OQ:193-218), as tests/test_oracle_golden.py restates them."""
+    name = os.path.basename(path)
+    tree = name.split("_")[0]
+    t64 = np.load(path)
+    base = np.load(path.replace("_traces64", ""))
+    step = 1 if tree == "ant" else 2
+    cases = []
+    for k64 in t64.files:
+        trace64 = t64[k64]
+        if k64.endswith("__trace64"):                            # a complete TensorQuantizer calibration
+            k = k64[:-len("__trace64")]
+            parts = k.split("__")
+            tname = parts[0]
+            xkey = next(c for c in (tname + "__x", tname[5:] + "_x" if tname.startswith("full_") else "") if c in base.files)
+            per_row = tname.startswith(("w", "full_w"))
+            bit = int(parts[2][1:]) if len(parts) > 2 else 4
+            lo, up = map(int, parts[3].split("_")) if len(parts) > 3 else (75, 150 if tree == "ant" else 250)
+            if tree == "ant" and bit > 6:
+                lo = 95                                          # AQ:296-297
+            normal = base[k + "__grid"]
+            ovp = tree == "olive" and not k.endswith("__noout")
+            grid = np.concatenate([normal, base[k + "__outliers"]]) if ovp else normal
+        else:                                                    # a single search_mse of the round-1 fixtures
+            k = k64[:-len("_trace64")]
+            parts = k.split("_")
+            tname, t = parts[0], parts[1]
+            xkey = ("a_x" if tname.startswith("a") else "w_x")
+            per_row = tname == "w"
+            lo, up = 75, 150 if tree == "ant" else 250
+            if tree == "ant":
+                normal, ovp = oracle.ant_grid(t, 4, tname != "au"), False
+                grid = normal
+            else:
+                normal, ovp = oracle.olive_grid(t, 4, True), parts[2] == "ovp"
+                grid = np.concatenate([normal, oracle.olive_outlier_value(4, True)]) if ovp else normal
+        x = np.asarray(base[xkey], dtype=np.float32)
+        x = x.reshape(x.shape[0], -1)
+        if tname == "au":
+            x = np.abs(x)
+        xmax = _three_sigma_reference(x, per_row) if ovp else _absmax(x, per_row)
+        cases.append(dict(key=k, x=x, xmax=xmax, lo=lo, up=up, step=step, ratios=ratios_of(lo, up, step),
+                          grid=np.asarray(grid, dtype=np.float32), gmax=float(np.max(normal)), ovp=ovp, per_row=per_row,
+                          trace64=trace64))
+    return cases

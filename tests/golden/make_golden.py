@@ -742,6 +742,68 @@ def gen_long(outdir, tree):
     np.savez_compressed(os.path.join(outdir, "%s_select_long_traces64.npz" % tree), **t64)
 
 
+# Rows of more than one 4096-key chunk (and one below it): the shapes behind every timed calibration, whose sorted-row search
+# had never met scores the reference recorded.  Same recorder as gen_long; three weight tensors of two rows each.  `__out` is
+# stored for the installed grid at the picked alpha only, as everywhere; each file stays below the largest committed fixture.
+XLONG_MAX_BYTES = 447682
+
+
+def gen_xlong(outdir, tree):
+    import torch
+
+    _install_shim()
+    if tree == "ant":
+        import torch.distributed as dist
+        os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29536")
+        dist.init_process_group("gloo", rank=0, world_size=1)
+        sys.path.insert(0, os.path.join(REF, "ant_quantization", "antquant"))
+    else:
+        sys.path.insert(0, os.path.join(REF, "olive_quantization", "antquant"))
+    import quant_modules as qm
+
+    scores, tr, sel, keys = _record_mse_loss(qm), {}, {}, []
+    torch.manual_seed(47 if tree == "ant" else 53)
+    if tree == "ant":
+        combos = [("ant-int-pot-flint", 4, {}), ("ant-int-flint", 4, {})]
+        lo, up, step = 75, 150, 1
+    else:
+        combos = [("ant-int-flint", 4, dict(no_outlier=False)), ("ant-int-flint", 4, dict(no_outlier=True))]
+        lo, up, step = 75, 250, 2
+    for K in (2048, 4096 + 64, 3 * 4096):
+        name = "w%d" % K
+        w = torch.distributions.Laplace(0.0, 0.03).sample((2, K))
+        w[1] *= 0.4
+        if tree == "olive":
+            m = torch.rand(2, K) < 0.01
+            w[m] *= torch.empty(int(m.sum())).uniform_(6, 40)
+        sel[name + "__x"] = w.numpy()
+        for mode, bit, kw in combos:
+            q = qm.TensorQuantizer(mode=mode, bit=bit, is_signed=True, is_enable=True, is_input=False,
+                                   args=_args(w_low=lo, a_low=lo, w_up=up, a_up=up, **kw))
+            q.name = "golden"
+            q.alpha.data = torch.ones(w.shape[0], 1)
+            _reset(scores)
+            out = q(w)
+            k = "%s__%s__b%d__%d_%d" % (name, mode, bit, lo, up)
+            if tree == "olive":
+                k += "__noout" if kw["no_outlier"] else "__ovp"
+                sel[k + "__outliers"] = q.outliers.data.numpy()
+            keys.append(k)
+            sel[k + "__mode"] = np.array(q.mode)
+            sel[k + "__signed"] = np.array(bool(q.is_signed))
+            sel[k + "__alpha"] = q.alpha.data.numpy().reshape(-1)
+            sel[k + "__grid"] = q.quant_grid.data.numpy()
+            sel[k + "__out"] = out.detach().numpy()
+            sel[k + "__mse"] = np.float32(q.mse.item())
+            _put_trace(tr, k, scores, len(range(lo, up, step)))
+    sel["keys"] = np.array(keys)
+    t64 = tr.pop("__64", {})
+    for fname, arrays in (("%s_select_xlong.npz" % tree, sel), ("%s_select_xlong_traces.npz" % tree, tr), ("%s_select_xlong_traces64.npz" % tree, t64)):
+        path = os.path.join(outdir, fname)
+        np.savez_compressed(path, **arrays)
+        assert os.path.getsize(path) <= XLONG_MAX_BYTES, (fname, os.path.getsize(path))
+
+
 # ----------------------------------------------------------------------------
 # Round 3: CHECKPOINTS WRITTEN BY THE REFERENCE'S OWN CODE and one MultiheadAttentionQuantizer forward (N4).
 # The reference's quant_model.py / quant_utils.py are imported unmodified (torchvision is absent from the image and is
@@ -902,7 +964,7 @@ def gen_mha_options(outdir):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--tree", choices=["ant", "ant_wide", "olive", "olive_wide", "ant_long", "olive_long", "ant_ckpt", "olive_ckpt", "ant_mha", "all"], default="all")
+    ap.add_argument("--tree", choices=["ant", "ant_wide", "olive", "olive_wide", "ant_long", "olive_long", "ant_xlong", "olive_xlong", "ant_ckpt", "olive_ckpt", "ant_mha", "all"], default="all")
     ap.add_argument("--out", default=HERE)
     ap.add_argument("--traces-only", action="store_true",
                     help="write only the *_traces.npz files (per-candidate MSE of the complete calibrations)")
@@ -912,7 +974,7 @@ def main():
     if not os.path.isdir(REF):
         sys.exit("make_golden.py needs the reference checkout at %s (build container only)" % REF)
     if a.tree == "all":
-        for t in ("ant", "ant_wide", "olive", "olive_wide", "ant_long", "olive_long") + (() if a.traces_only else ("ant_ckpt", "olive_ckpt", "ant_mha")):
+        for t in ("ant", "ant_wide", "olive", "olive_wide", "ant_long", "olive_long", "ant_xlong", "olive_xlong") + (() if a.traces_only else ("ant_ckpt", "olive_ckpt", "ant_mha")):
             subprocess.check_call([sys.executable, os.path.abspath(__file__), "--tree", t, "--out", a.out] +
                                   (["--traces-only"] if a.traces_only else []))
         return
@@ -920,6 +982,8 @@ def main():
     torch.set_num_threads(1)   # deterministic reductions for the recorded MSE traces
     if a.tree in ("ant_long", "olive_long"):
         gen_long(a.out, a.tree[:-5])
+    elif a.tree in ("ant_xlong", "olive_xlong"):
+        gen_xlong(a.out, a.tree[:-6])
     elif a.tree in ("ant_ckpt", "olive_ckpt"):
         gen_ckpt(a.out, a.tree[:-5])
     elif a.tree == "ant_mha":

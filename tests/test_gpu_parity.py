@@ -1727,16 +1727,19 @@ def test_olive_quantizer_end_to_end_wide_fixture_set(antq_lib, dev, capsys):
     _pick_report("end to end, olive wide fixture set", n_same, n_rows, led0)
 
 
+@pytest.mark.parametrize("which", ["long", "xlong"])
 @pytest.mark.parametrize("tree", ["ant", "olive"])
-def test_quantizer_end_to_end_long_rows_single_read_type_selection(antq_lib, dev, tree, capsys):
+def test_quantizer_end_to_end_long_rows_single_read_type_selection(antq_lib, dev, tree, which, capsys):
     """*_select_long.npz: complete `ant-...` calibrations recorded from the reference on rows of 1024 elements -- the
     shapes on which the quantiser selects the type on ONE read of the tensor (antq_search_sse_multi: 2, 3 and 4 candidate
     codebooks, the installed grid's search reused).  Picks against the reference's own scores, outputs for every row on
-    the reference's alpha; and exactly one search launch per calibration."""
+    the reference's alpha; and exactly one search launch per calibration.
+    "xlong" (*_select_xlong.npz): weights of 2 x 2048, 2 x (4096 + 64) and 2 x 3 * 4096 elements -- rows of one chunk of the
+    sorted-row search, of a ragged second chunk and of three chunks, against scores the reference recorded."""
     import importlib
     import torch
     qm = importlib.import_module("ant_quantization_amd.%s.quant_modules" % tree)
-    sel, tr = golden("%s_select_long.npz" % tree), golden("%s_select_long_traces.npz" % tree)
+    sel, tr = golden("%s_select_%s.npz" % (tree, which)), golden("%s_select_%s_traces.npz" % (tree, which))
     calls = {"multi": 0, "single": 0}
     real_m, real_s = antq_lib.search_sse_multi, antq_lib.search_sse
 
@@ -1757,7 +1760,7 @@ def test_quantizer_end_to_end_long_rows_single_read_type_selection(antq_lib, dev
             om = parts[4] if tree == "olive" else "noout"
             bit, (lo, up) = int(b[1:]), map(int, win.split("_"))
             x_np = sel[name + "__x"]
-            is_input = name != "w"
+            is_input = not name.startswith("w")                   # ("w", and the xlong files' "w2048" / "w4160" / "w12288")
             kw = dict(w_low=lo, a_low=lo, w_up=up, a_up=up)
             if tree == "olive":
                 kw["no_outlier"] = om == "noout"
@@ -3128,12 +3131,14 @@ def test_bench_plain_line_and_dumped_outputs_on_the_gpu(antq_lib, dev, tmp_path)
     assert torch.equal(y, x)
 
 
-@pytest.mark.parametrize("seed", range(int(os.environ.get("ANTQ_FUZZ_SEEDS", 2))))
+@pytest.mark.parametrize("seed", range(int(os.environ.get("ANTQ_FUZZ_SEEDS", 12))))
 def test_calibration_fuzz_random_shapes_vs_oracle(antq_lib, oracle, dev, seed):
     """The calibration kernels on random shapes -- rows of one partial task, of many tasks with a partial last one (4- and
     8-vector tasks), ragged and unaligned rows (element kernel), per row and per tensor, fp32 / bf16, ANT types and OliVe's
     pair rule: every candidate's mean squared error against the oracle's trace (summation-order tolerance), the picks
-    against the oracle's (near-ties excepted), through antq_search_sse, antq_search_sse_multi and antq_calibrate."""
+    against the oracle's (near-ties excepted), through antq_search_sse, antq_search_sse_multi and antq_calibrate.  Every sum is
+    also held to the float64 yardstick (calib_check.exact_sse): `exact` where a closed form answered (the sorted-row search
+    under the default rule: its bits differ from the direct kernels'), `terms32` where the direct kernels did."""
     import torch
     from ant_quantization_amd import core
     G, O = golden("ant_grids.npz"), golden("olive_grids.npz")
@@ -3151,7 +3156,7 @@ def test_calibration_fuzz_random_shapes_vs_oracle(antq_lib, oracle, dev, seed):
         epv = 8 if bf16 else 4
         kind = rng.integers(0, 4)
         if kind == 0:
-            K = epv * int(rng.integers(128, 2200))              # long rows: 4- / 8-vector tasks, partial last task
+            K = epv * int(rng.integers(128, 4300))              # long rows: 4- / 8-vector tasks, partial last task, up to 5 / 9 chunks of 4096 keys
         elif kind == 1:
             K = epv * int(rng.integers(1, 128))                 # short rows
         elif kind == 2:
@@ -3177,6 +3182,18 @@ def test_calibration_fuzz_random_shapes_vs_oracle(antq_lib, oracle, dev, seed):
             rb, ra, trace = oracle.search_mse(xf.reshape(r_, k_), xm_np, lb, ub, step, g, gm, ovp, per_row)
             sse = antq_lib.search_sse(xt, r_, k_, xm, per_row, ratios, plans[t], gm, ovp=ovp)
             np.testing.assert_allclose((sse / k_).float().cpu().numpy(), trace, rtol=3e-5, atol=1e-12, err_msg=str(tag + (t,)))
+            knob = antq_lib.lib().antq_debug_set
+            knob(19, 0); knob(20, 0); knob(14, 0)
+            try:
+                direct = antq_lib.search_sse(xt, r_, k_, xm, per_row, ratios, plans[t], gm, ovp=ovp).cpu().numpy()
+            finally:
+                knob(19, 1); knob(20, 1); knob(14, 1)
+            exact, terms32 = calib_check.exact_sse(oracle, xf.reshape(r_, k_), xm_np, ratios_of(lb, ub, step), g, gm, ovp, per_row)
+            got = sse.cpu().numpy()
+            closed = not np.array_equal(got.view(np.uint64), direct.view(np.uint64))
+            np.testing.assert_allclose(got, exact if closed else terms32, atol=0, err_msg=str(tag + (t, "yardstick", "closed form" if closed else "direct kernels")),
+                                       rtol=calib_check.EXACT_RTOL if closed else (calib_check.DIRECT_RTOL_OLIVE if olive else calib_check.DIRECT_RTOL))
+            np.testing.assert_allclose(direct, terms32, rtol=calib_check.DIRECT_RTOL_OLIVE if olive else calib_check.DIRECT_RTOL, atol=0, err_msg=str(tag + (t, "direct")))
             check_alpha_picks("fuzz_%d_%d_%d" % (seed, case, t), alpha[t].cpu().numpy(), ra, trace, ratios_of(lb, ub, step), xmax_rtol=0.0)
             osum.append(float(rb.astype(np.float64).sum()))
         multi = antq_lib.search_sse_multi(xt, r_, k_, xm, per_row, ratios, plans, gmaxs, ovp=ovp)

@@ -1,10 +1,12 @@
 """Where the sorted-row search and the direct kernels differ most on the OliVe test tensor: both against the exact (float64)
 sum of the reference's per-element outputs (oracle.forward), with and without the reference's fp32 rounding of each term."""
 import os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import numpy as np, torch
 from ant_quantization_amd import _lib as L, grids
 from oracle import antq_oracle as orc
+from calib_check import exact_sse        # the suite's yardstick (tests/calib_check.py)
 orc.build(); orc.lib()
 dev = torch.device("cuda:0")
 torch.manual_seed(73)
@@ -35,12 +37,8 @@ for dt in (torch.float32, torch.bfloat16):
         rel = torch.where(torch.isfinite(rel), rel, torch.zeros_like(rel))
         t, c, r = np.unravel_index(int(rel.argmax()), rel.shape)
         xn = x[r:r + 1].float().cpu().numpy()
-        alpha = (xm[r:r + 1] * rt[c]).cpu().numpy().astype(np.float32).reshape(1, 1)
-        out = orc.forward(xn, alpha, cb[t][0], cb[t][1], ovp=ovp, want_idx=False)
-        out = out[0] if isinstance(out, tuple) else out
-        d32 = (out.astype(np.float32) - xn.astype(np.float32)).astype(np.float32)
-        exact = float((d32.astype(np.float64) ** 2).sum())
-        rounded = float(((d32 * d32).astype(np.float32)).astype(np.float64).sum())
+        ex, t32 = exact_sse(orc, xn, xm[r:r + 1].cpu().numpy(), rt[c:c + 1].cpu().numpy(), cb[t][0], cb[t][1], ovp, True)
+        exact, rounded = float(ex[0, 0]), float(t32[0, 0])
         print("%s %dx%d ovp %d: worst rel %.2e at type %d cand %d row %d: direct %.12e sorted %.12e | exact-sum %.12e (direct %+.2e sorted %+.2e)  fp32-terms %.12e (direct %+.2e sorted %+.2e)" % (
             str(dt)[6:], rows, K, ovp, float(rel.max()), t, c, r, float(a[t, c, r]), float(b[t, c, r]), exact, float(a[t, c, r]) / exact - 1, float(b[t, c, r]) / exact - 1,
             rounded, float(a[t, c, r]) / rounded - 1, float(b[t, c, r]) / rounded - 1), flush=True)
