@@ -549,6 +549,20 @@ def absmax(x, rows, row_len, per_row=True):
     return amax
 
 
+def absmax_t(x):
+    """[1] float32: the abs-max of the whole tensor in ONE launch (antq_absmax_t: the result is written, not accumulated,
+    through the stream's ticket block)."""
+    _require_gpu(x, "x")
+    dt = _DTYPES.get(x.dtype)
+    if dt is None or dt == F64:
+        raise AntqError("unsupported dtype %s" % x.dtype)
+    amax = torch.empty(1, dtype=torch.float32, device=x.device)
+    with _on_device(x.device):
+        _check(lib().antq_absmax_t(x.data_ptr(), amax.data_ptr(), x.numel(), dt, _reduce_ws(x.device).data_ptr(),
+                                   _stream_int(x.device)), "antq_absmax_t")
+    return amax
+
+
 def moments(x, rows, row_len, per_row=True):
     """[rows or 1, 2] float64: (sum x, sum x^2) per row or for the whole tensor, on ONE read, in a fixed order."""
     _require_gpu(x, "x")

@@ -426,6 +426,16 @@ extern "C" int antq_absmax_into(const void *x, float *amax, size_t n, int dtype,
 // Whole-tensor reductions in one launch (antq_k_reduce.h, ABI 7)
 // ======================================================================================
 namespace antq {
+// What the ticket block's layout holds (antq_k_reduce.h): 1024 workgroup partials, kTkMaxGroups group counters and group
+// partials, one lane per member of a group.  The defaults fit (256 / 16, 512 / 32); the A/B knobs (keys 17 / 18) are clamped
+// to it here: workgroups <= 1024, workgroups per group <= 64 and large enough for at most kTkMaxGroups groups.
+static void clamp_to_ticket_layout(size_t &blocks, uint32_t &group)
+{
+    if (blocks > 1024u) blocks = 1024u;
+    if (group > 64u) group = 64u;
+    const uint32_t least = (uint32_t)((blocks + kTkMaxGroups - 1u) / kTkMaxGroups);
+    if (group < least) group = least;
+}
 template <typename T>
 static int launch_absmax_t(const void *x, float *amax, size_t n, void *ws, hipStream_t st)
 {
@@ -435,7 +445,8 @@ static int launch_absmax_t(const void *x, float *amax, size_t n, void *ws, hipSt
     const size_t cap = g_knob_tk_blocks > 0 ? (size_t)g_knob_tk_blocks : 256;
     if (blocks > cap) blocks = cap;              // one workgroup per CU: few, long streams (see launch_absmax)
     if (blocks < 1) blocks = 1;
-    const uint32_t group = g_knob_tk_group > 0 ? (uint32_t)g_knob_tk_group : 16u;
+    uint32_t group = g_knob_tk_group > 0 ? (uint32_t)g_knob_tk_group : 16u;
+    clamp_to_ticket_layout(blocks, group);
     hipLaunchKernelGGL((k_absmax_t<T>), dim3((unsigned)blocks), dim3(256), 0, st, x, amax, n, vec_ok, ws, group);
     return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
 }
@@ -450,7 +461,8 @@ static int launch_alpha_grad_t(const void *x, const void *out, const void *gout,
     const size_t cap = g_knob_tk_blocks > 0 ? (size_t)g_knob_tk_blocks : (sizeof(T) == 4 ? 256 : 512);
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
-    const uint32_t group = g_knob_tk_group > 0 ? (uint32_t)g_knob_tk_group : 32u;
+    uint32_t group = g_knob_tk_group > 0 ? (uint32_t)g_knob_tk_group : 32u;
+    clamp_to_ticket_layout(blocks, group);
     hipLaunchKernelGGL((k_alpha_grad_t<T>), dim3((unsigned)blocks), dim3(256), 0, st, x, out, gout, gsum, n, vec_ok, ws, group);
     return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
 }

@@ -581,26 +581,43 @@ int main()
             antq_oracle_absmax_f32(xf.data(), w2.data(), 1, n - (size_t)rep, 0, 1.0f);
             same_bits("antq_absmax_t (one launch, ticket block)", dslot.down(st), w2);
         }
-        std::vector<float> gout(n);
-        for (size_t i = 0; i < n; i++) gout[i] = nd(rng) * 50.0f;
-        DevBuf<float> dg(n);
-        dg.up(gout, st);
-        ANTQ_OK_(antq_fakequant(dxf.p, dout.p, nullptr, rows, K, dalpha.p, 1, 10.0f, plan.data(), dplan.p, 0, ANTQ_F32, st));
-        const std::vector<float> o = dout.down(st);
-        DevBuf<double> dgs(1);
-        ANTQ_OK_(antq_alpha_grad_t(dxf.p, dout.p, dg.p, n, dgs.p, ANTQ_F32, dred.p, st));
-        const std::vector<double> g1 = dgs.down(st);
-        ANTQ_OK_(antq_alpha_grad_t(dxf.p, dout.p, dg.p, n, dgs.p, ANTQ_F32, dred.p, st));
-        const std::vector<double> g2 = dgs.down(st);
-        double wantg = 0.0, mag = 0.0;
-        for (size_t i = 0; i < n; i++) {
-            const float diff = o[i] - xf[i];
-            const float term = gout[i] * diff;
-            wantg += (double)term;
-            mag += std::fabs((double)term);
+        // bf16: the maximum of the 16-bit magnitudes (they order like their bits), n, n - 1, n - 2 elements
+        {
+            std::vector<uint16_t> xb(n);
+            antq_oracle_f32_to_bf16(xf.data(), xb.data(), n);
+            DevBuf<uint16_t> dxb(n);
+            dxb.up(xb, st);
+            for (int rep = 0; rep < 3; rep++) {
+                DevBuf<float> dslot(1);
+                HIP_OK(hipMemsetAsync(dslot.p, 0x7f, 4, st));
+                ANTQ_OK_(antq_absmax_t(dxb.p, dslot.p, n - (size_t)rep, ANTQ_BF16, dred.p, st));
+                uint32_t m = 0;
+                for (size_t i = 0; i < n - (size_t)rep; i++) m = std::max(m, (uint32_t)(xb[i] & 0x7fffu));
+                m <<= 16;
+                std::vector<float> w2(1);
+                std::memcpy(&w2[0], &m, 4);
+                same_bits("antq_absmax_t bf16 (one launch, ticket block)", dslot.down(st), w2);
+            }
         }
-        const bool okg = std::fabs(g1[0] - wantg) <= 1e-6 * mag + 1e-30 && std::memcmp(&g1[0], &g2[0], 8) == 0;
-        printf("%-58s %s\n", "antq_alpha_grad_t (one launch, bit-reproducible)", okg ? "ok" : "FAIL");
+        // integer-valued inputs in [-128, 128]: every product, every fp32 partial over a lane's vector and every double sum
+        // is exact in any order, so the result must EQUAL the integer sum (n and n - 3 elements: vector and element tails)
+        std::uniform_int_distribution<int> ui(-128, 128);
+        std::vector<float> xi(n), oi(n), gi(n);
+        for (size_t i = 0; i < n; i++) { xi[i] = (float)ui(rng); oi[i] = (float)ui(rng); gi[i] = (float)ui(rng); }
+        DevBuf<float> dxi(n), doi(n), dg(n);
+        dxi.up(xi, st); doi.up(oi, st); dg.up(gi, st);
+        DevBuf<double> dgs(1);
+        bool okg = true;
+        for (size_t cut : {(size_t)0, (size_t)3}) {
+            ANTQ_OK_(antq_alpha_grad_t(dxi.p, doi.p, dg.p, n - cut, dgs.p, ANTQ_F32, dred.p, st));
+            const std::vector<double> g1 = dgs.down(st);
+            ANTQ_OK_(antq_alpha_grad_t(dxi.p, doi.p, dg.p, n - cut, dgs.p, ANTQ_F32, dred.p, st));
+            const std::vector<double> g2 = dgs.down(st);
+            long long wantg = 0;
+            for (size_t i = 0; i < n - cut; i++) wantg += (long long)gi[i] * ((long long)oi[i] - (long long)xi[i]);
+            okg = okg && g1[0] == (double)wantg && std::memcmp(&g1[0], &g2[0], 8) == 0;
+        }
+        printf("%-58s %s\n", "antq_alpha_grad_t (one launch, == the integer sum)", okg ? "ok" : "FAIL");
         if (!okg) failures++;
         const std::vector<uint8_t> red = dred.down(st);
         size_t nz = 0;

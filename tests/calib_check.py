@@ -170,6 +170,46 @@ def exact_sse(oracle, x2d_f32, xmax, ratios, grid, gmax, ovp, per_row):
     return exact, terms32
 
 
+def _round_bf16(v):
+    """float32 -> the nearest bfloat16 (ties to even) as float32; NaN stays NaN."""
+    v = np.asarray(v, dtype=np.float32)
+    u = v.view(np.uint32).astype(np.uint64)
+    r = (((u + 0x7fff + ((u >> 16) & 1)) >> 16) << 16).astype(np.uint32).view(np.float32)
+    return np.where(np.isnan(v), np.float32(np.nan), r).astype(np.float32)
+
+
+ROUND_TO = {"float32": lambda v: np.asarray(v, dtype=np.float32),
+            "bfloat16": _round_bf16,
+            "float16": lambda v: np.asarray(v, dtype=np.float32).astype(np.float16).astype(np.float32)}
+
+
+def exact_three_sigma(x, per_row, dtype="float32"):
+    """The yardstick of antq_moments + antq_xmax_3sigma: OliVe's clip statistic max(|mean + 3 std|, |mean - 3 std|)
+    (OQ:193-197, :213-218) from the EXACT mean and the exact centred second moment -- no one-pass sums, no cancellation.
+
+    x: 2-D array holding the tensor's values (a 16-bit tensor as its float32 image); per row, or over everything.  The
+    mean is math.fsum(row) / n (the sum correctly rounded), the variance math.fsum((v - mean)^2) / (n - 1) (unbiased,
+    torch.std's default; each term carries two float64 roundings, 2^-52 relative), then the roundings include/antq.h
+    documents for `dtype`: float32 -- mean and std rounded to float, 3 * std, the sum and the difference in float;
+    bfloat16 / float16 -- each of the five rounded to the tensor's dtype.  One element: NaN (0 / 0), like torch.std.
+    Returns float32 [rows or 1]."""
+    import math
+    rnd = ROUND_TO[dtype]
+    x = np.asarray(x, dtype=np.float64)
+    x = x.reshape(x.shape[0], -1) if per_row else x.reshape(1, -1)
+    n = x.shape[1]
+    mean, std = np.empty(x.shape[0]), np.empty(x.shape[0])
+    for r in range(x.shape[0]):
+        mean[r] = math.fsum(x[r].tolist()) / n
+        d = x[r] - mean[r]
+        std[r] = math.sqrt(math.fsum((d * d).tolist()) / (n - 1)) if n > 1 else np.nan
+    with np.errstate(all="ignore"):
+        m, sd = rnd(mean.astype(np.float32)), rnd(std.astype(np.float32))
+        t3 = rnd(np.float32(3.0) * sd)
+        a, b = np.abs(rnd(m + t3)), np.abs(rnd(m - t3))
+        return np.where(np.isnan(a) | np.isnan(b), np.float32(np.nan), np.maximum(a, b)).astype(np.float32)
+
+
 def _three_sigma_reference(x, per_row):
     """OliVe's clip statistic in the reference's own op sequence (OQ:193-195 / :213-215: torch float32 mean, std, 3 * std, sum,
     difference).  The recorded scores depend on this float32 value to the bit, and a float64 restatement of it lands one ulp
