@@ -1,7 +1,10 @@
 // antq_batch.hip -- the batched launch of libantq: antq_batch_capacity / antq_batch_build / antq_fakequant_batch
 // (many tensors' Quantizer._forward, AQ/quant_modules.py:535-551 / OQ:294-330, in one launch).  gfx950 only.
 #include "antq_host.h"
+#include "antq_dispatch.h"
 #include "antq_k_batch.h"
+
+#include <type_traits>
 
 using namespace antq;
 
@@ -281,43 +284,64 @@ extern "C" int antq_batch_build(const antq_job *jobs, int n, int dtype, unsigned
     return (int)h.bytes;
 }
 
-// family 5 (16-bit dtypes only)
-template <typename T>
-static void launch_hbatch(uint32_t map_entries, const BatchDesc *descs, const uint32_t *map, bool ovp, hipStream_t st)
+// The launches of one dtype and pair rule.  Families (antq_batch_build): 0 row tables (or, in a mixed static batch, the
+// all-in-one kernel), 1 / 2 lane jobs with / without the approximate quotient, 3 / 4 dynamic rows in 4 / 16 wavefronts,
+// 5 static and 6 / 7 / 8 dynamic rows in the 16-bit domain (1 / 4 / 16 wavefronts per row; 16-bit dtypes only).
+template <typename T, bool OVP>
+static int launch_batch(const BatchHeader *h, const BatchDesc *descs, const uint32_t *const *fmap, hipStream_t st)
 {
-    const dim3 g(map_entries * 4u), b(64u);
-    // (the occupancy cap pays once the launch is several rounds of workgroups; a small batch wants every slot -- as a single
-    //  tensor does, antq_fq.hip)
-    const unsigned pad = g_knob_hlds >= 0 ? (unsigned)g_knob_hlds : (map_entries >= 8192u ? kHRowLdsPad : 0u);
-    if (ovp) hipLaunchKernelGGL((k_fq_hbatch<T, true>), g, b, pad, st, descs, map, (uint32_t)g_knob_rot);
-    else hipLaunchKernelGGL((k_fq_hbatch<T, false>), g, b, pad, st, descs, map, (uint32_t)g_knob_rot);
+    const dim3 block(256);
+    const bool dyn = (h->flags & ANTQ_FLAG_DYNAMIC) != 0;
+    constexpr bool H16 = !std::is_same<T, float>::value;         // (build never files an fp32 job under families 5 .. 8)
+    auto hbatch = [&]() {
+        if constexpr (H16) {
+            if (!h->fam_blocks[5]) return;
+            // (the occupancy cap pays once the launch is several rounds of workgroups; a small batch wants every slot -- as a
+            //  single tensor does, antq_fq.hip)
+            const unsigned pad = g_knob_hlds >= 0 ? (unsigned)g_knob_hlds : (h->fam_blocks[5] >= 8192u ? kHRowLdsPad : 0u);
+            hipLaunchKernelGGL((k_fq_hbatch<T, OVP>), dim3(h->fam_blocks[5] * 4u), dim3(64u), pad, st, descs, fmap[5], (uint32_t)g_knob_rot);
+        }
+    };
+    if (h->pad & 1u) {      // mixed static batch: the all-in-one kernel
+        hipLaunchKernelGGL((k_fq_batch_all<T, OVP>), dim3(h->fam_blocks[0]), block, h->lds_bytes, st, descs, fmap[0]);
+        hbatch();           // (a big 16-bit-domain share keeps its own launch)
+        return launch_status();
+    }
+    if (h->fam_blocks[0]) {
+        // wavefronts per workgroup: knob 6, or what build chose (1, anything else means 4)
+        const int hw = (int)((h->pad >> 8) & 7u);
+        const int w = (g_knob_waves == 4 || g_knob_waves == 2 || g_knob_waves == 1) ? g_knob_waves : (hw == 1 ? 1 : 4);
+        with_value<1, 2, 4>(w, [&](auto ww) {
+            constexpr int W = decltype(ww)::value;
+            hipLaunchKernelGGL((k_fq_batch<T, OVP, W>), dim3(h->fam_blocks[0] * (4u / W)), dim3(64u * W), 0, st, descs, fmap[0], (uint32_t)g_knob_rot);
+            return (int)ANTQ_OK;
+        });
+    }
+    hbatch();
+    if constexpr (H16) {
+        // the occupancy cap of family 6 follows the widest job of the batch (pad2[0])
+        if (h->fam_blocks[6])
+            hipLaunchKernelGGL((k_fq_hbatch_dyn<T, OVP, 1>), dim3(h->fam_blocks[6] * 4u), dim3(64u), g_knob_hlds >= 0 ? (unsigned)g_knob_hlds : h->pad2[0],
+                               st, descs, fmap[6]);
+        if (h->fam_blocks[7]) hipLaunchKernelGGL((k_fq_hbatch_dyn<T, OVP, 4>), dim3(h->fam_blocks[7]), dim3(256u), 0, st, descs, fmap[7]);
+        if (h->fam_blocks[8]) hipLaunchKernelGGL((k_fq_hbatch_dyn<T, OVP, 16>), dim3(h->fam_blocks[8]), dim3(1024u), 0, st, descs, fmap[8]);
+    }
+    for (int f = 1; f <= 2; f++) {
+        if (!h->fam_blocks[f]) continue;
+        // (fp32 static lane jobs, launches of many rounds: 6 workgroups = 24 wavefronts per CU, +1.5..2 points; r04_fp32_occupancy.log)
+        const unsigned cap = (sizeof(T) == 4 && !dyn && h->fam_blocks[f] >= 32768u && h->lds_bytes < 24576u) ? 24576u - h->lds_bytes : 0u;
+        const unsigned lds = h->lds_bytes + (g_knob_dlds >= 0 ? (unsigned)g_knob_dlds : cap);
+        with_bool(f == 1, [&](auto ad) {
+            return with_bool(dyn, [&](auto d) {
+                hipLaunchKernelGGL((k_fq_batch_d<T, OVP, decltype(ad)::value, decltype(d)::value>), dim3(h->fam_blocks[f]), block, lds, st, descs, fmap[f]);
+                return (int)ANTQ_OK;
+            });
+        });
+    }
+    if (h->fam_blocks[3]) hipLaunchKernelGGL((k_fq_batch_dyn<T, OVP>), dim3(h->fam_blocks[3]), block, 0, st, descs, fmap[3]);
+    if (h->fam_blocks[4]) hipLaunchKernelGGL((k_fq_batch_dyn16<T, OVP>), dim3(h->fam_blocks[4]), dim3(1024), 0, st, descs, fmap[4]);
+    return launch_status();
 }
-template <>
-void launch_hbatch<float>(uint32_t, const BatchDesc *, const uint32_t *, bool, hipStream_t) {}
-
-// families 6 / 7 / 8 (16-bit dtypes only).  The occupancy cap of family 6 follows the widest job of the batch.
-template <typename T>
-static void launch_hbatch_dyn(const BatchHeader *h, const BatchDesc *descs, const uint32_t *const *fmap, bool ovp, hipStream_t st)
-{
-    if (h->fam_blocks[6]) {
-        const dim3 g(h->fam_blocks[6] * 4u), b(64u);
-        const unsigned pad = g_knob_hlds >= 0 ? (unsigned)g_knob_hlds : h->pad2[0];
-        if (ovp) hipLaunchKernelGGL((k_fq_hbatch_dyn<T, true, 1>), g, b, pad, st, descs, fmap[6]);
-        else hipLaunchKernelGGL((k_fq_hbatch_dyn<T, false, 1>), g, b, pad, st, descs, fmap[6]);
-    }
-    if (h->fam_blocks[7]) {
-        const dim3 g(h->fam_blocks[7]), b(256u);
-        if (ovp) hipLaunchKernelGGL((k_fq_hbatch_dyn<T, true, 4>), g, b, 0, st, descs, fmap[7]);
-        else hipLaunchKernelGGL((k_fq_hbatch_dyn<T, false, 4>), g, b, 0, st, descs, fmap[7]);
-    }
-    if (h->fam_blocks[8]) {
-        const dim3 g(h->fam_blocks[8]), b(1024u);
-        if (ovp) hipLaunchKernelGGL((k_fq_hbatch_dyn<T, true, 16>), g, b, 0, st, descs, fmap[8]);
-        else hipLaunchKernelGGL((k_fq_hbatch_dyn<T, false, 16>), g, b, 0, st, descs, fmap[8]);
-    }
-}
-template <>
-void launch_hbatch_dyn<float>(const BatchHeader *, const BatchDesc *, const uint32_t *const *, bool, hipStream_t) {}
 
 extern "C" int antq_fakequant_batch(const void *batch_host, const void *batch_dev, void *stream)
 {
@@ -327,67 +351,15 @@ extern "C" int antq_fakequant_batch(const void *batch_host, const void *batch_de
     if (h->total_blocks == 0) return ANTQ_OK;
     const char *pd = static_cast<const char *>(batch_dev);
     const BatchDesc *descs = reinterpret_cast<const BatchDesc *>(pd + sizeof(BatchHeader));
-    const uint32_t *map = reinterpret_cast<const uint32_t *>(pd + h->map_offset);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 block(256);
-    const bool ovp = (h->flags & ANTQ_FLAG_OVP) != 0;
-    const bool dyn = (h->flags & ANTQ_FLAG_DYNAMIC) != 0;
     const uint32_t *fmap[kBatchFamilies];
     {
-        const uint32_t *m = map;
+        const uint32_t *m = reinterpret_cast<const uint32_t *>(pd + h->map_offset);
         for (int f = 0; f < kBatchFamilies; f++) { fmap[f] = m; m += h->fam_blocks[f]; }
     }
-#define ANTQ_LAUNCH_D(TT, OO, AA)                                                                                   \
-    do {                                                                                                            \
-        const int f_ = (AA) ? 1 : 2;                                                                                \
-        /* (fp32 static lane jobs, launches of many rounds: 6 workgroups = 24 wavefronts per CU, +1.5..2 points; r04_fp32_occupancy.log) */ \
-        const unsigned cap_ = (sizeof(TT) == 4 && !dyn && h->fam_blocks[f_] >= 32768u && h->lds_bytes < 24576u) ? 24576u - h->lds_bytes : 0u;  \
-        const unsigned lds_ = h->lds_bytes + (g_knob_dlds >= 0 ? (unsigned)g_knob_dlds : cap_);                    \
-        if (dyn) hipLaunchKernelGGL((k_fq_batch_d<TT, OO, AA, true>), dim3(h->fam_blocks[f_]), block, lds_, st, descs, fmap[f_]);  \
-        else hipLaunchKernelGGL((k_fq_batch_d<TT, OO, AA, false>), dim3(h->fam_blocks[f_]), block, lds_, st, descs, fmap[f_]);     \
-    } while (0)
-#define ANTQ_LAUNCH_B(TT)                                                                                         \
-    do {                                                                                                          \
-        if (h->pad & 1u) {      /* mixed static batch: the all-in-one kernel */                                       \
-            if (ovp) hipLaunchKernelGGL((k_fq_batch_all<TT, true>), dim3(h->fam_blocks[0]), block, h->lds_bytes, st, descs, fmap[0]);  \
-            else hipLaunchKernelGGL((k_fq_batch_all<TT, false>), dim3(h->fam_blocks[0]), block, h->lds_bytes, st, descs, fmap[0]);     \
-            if (h->fam_blocks[5]) launch_hbatch<TT>(h->fam_blocks[5], descs, fmap[5], ovp, st);   /* (a big 16-bit-domain share keeps its own launch) */ \
-            break;                                                                                                \
-        }                                                                                                         \
-        if (h->fam_blocks[0]) {                                                                                   \
-            const int hw_ = (int)((h->pad >> 8) & 7u);                                                           \
-            const int w_ = (g_knob_waves == 4 || g_knob_waves == 2 || g_knob_waves == 1) ? g_knob_waves : (hw_ == 1 ? 1 : 4);   \
-            const dim3 g_(h->fam_blocks[0] * (4u / w_)), b_(64u * w_);                                           \
-            const uint32_t rot_ = (uint32_t)g_knob_rot;                                                          \
-            if (w_ == 1) { if (ovp) hipLaunchKernelGGL((k_fq_batch<TT, true, 1>), g_, b_, 0, st, descs, fmap[0], rot_);        \
-                           else hipLaunchKernelGGL((k_fq_batch<TT, false, 1>), g_, b_, 0, st, descs, fmap[0], rot_); }         \
-            else if (w_ == 2) { if (ovp) hipLaunchKernelGGL((k_fq_batch<TT, true, 2>), g_, b_, 0, st, descs, fmap[0], rot_);   \
-                           else hipLaunchKernelGGL((k_fq_batch<TT, false, 2>), g_, b_, 0, st, descs, fmap[0], rot_); }         \
-            else { if (ovp) hipLaunchKernelGGL((k_fq_batch<TT, true, 4>), g_, b_, 0, st, descs, fmap[0], rot_);                \
-                   else hipLaunchKernelGGL((k_fq_batch<TT, false, 4>), g_, b_, 0, st, descs, fmap[0], rot_); }                 \
-        }                                                                                                         \
-        if (h->fam_blocks[5]) launch_hbatch<TT>(h->fam_blocks[5], descs, fmap[5], ovp, st);                       \
-        if (h->fam_blocks[6] || h->fam_blocks[7] || h->fam_blocks[8]) launch_hbatch_dyn<TT>(h, descs, fmap, ovp, st);      \
-        if (h->fam_blocks[1]) { if (ovp) ANTQ_LAUNCH_D(TT, true, true); else ANTQ_LAUNCH_D(TT, false, true); }    \
-        if (h->fam_blocks[2]) { if (ovp) ANTQ_LAUNCH_D(TT, true, false); else ANTQ_LAUNCH_D(TT, false, false); }  \
-        if (h->fam_blocks[3]) {                                                                                   \
-            if (ovp) hipLaunchKernelGGL((k_fq_batch_dyn<TT, true>), dim3(h->fam_blocks[3]), block, 0, st, descs, fmap[3]);   \
-            else hipLaunchKernelGGL((k_fq_batch_dyn<TT, false>), dim3(h->fam_blocks[3]), block, 0, st, descs, fmap[3]);      \
-        }                                                                                                         \
-        if (h->fam_blocks[4]) {                                                                                   \
-            if (ovp) hipLaunchKernelGGL((k_fq_batch_dyn16<TT, true>), dim3(h->fam_blocks[4]), dim3(1024), 0, st, descs, fmap[4]);   \
-            else hipLaunchKernelGGL((k_fq_batch_dyn16<TT, false>), dim3(h->fam_blocks[4]), dim3(1024), 0, st, descs, fmap[4]);      \
-        }                                                                                                         \
-    } while (0)
-    switch (h->dtype) {
-    case ANTQ_F32: ANTQ_LAUNCH_B(float); break;
-    case ANTQ_BF16: ANTQ_LAUNCH_B(bf16_tag); break;
-    case ANTQ_F16: ANTQ_LAUNCH_B(f16_tag); break;
-    default: return ANTQ_ERR_UNSUPPORTED;
-    }
-#undef ANTQ_LAUNCH_B
-#undef ANTQ_LAUNCH_D
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return with_dtype((int)h->dtype, [&](auto tag) {
+        return with_bool((h->flags & ANTQ_FLAG_OVP) != 0, [&](auto ovp) { return launch_batch<decltype(tag), decltype(ovp)::value>(h, descs, fmap, st); });
+    });
 }
 
 namespace antq {

@@ -1,4 +1,4 @@
-// antq_kernels.hip -- hand-written gfx950 (CDNA4, wave64) kernels of the ANT / OliVe
+// antq_fq.hip -- hand-written gfx950 (CDNA4, wave64) kernels of the ANT / OliVe
 // fake-quant hot path + their C-ABI launchers (include/antq.h).
 //
 // Reference semantics being reproduced (bit-exact):
@@ -20,27 +20,17 @@
 // float op below must round exactly as written).
 // This translation unit: antq_fakequant / antq_fakequant_dynamic (one tensor per launch).
 #include "antq_host.h"
+#include "antq_dispatch.h"
 #include "antq_k_fakequant.h"
 #include "antq_k_hrow.h"
 #include "antq_k_aux.h"
 
-#include <hip/hip_ext.h>
-#include <type_traits>
 
 namespace antq {
 
-// ANTQ_FLAG_UNORDERED of the call being dispatched (set by the entry point, read by the launch helpers of this file)
+// ANTQ_FLAG_UNORDERED of the call being dispatched (set by the entry point for the length of the call, handed to launch_k
+// by the launches that may go out of order)
 static thread_local bool t_unordered = false;
-
-// One launch.  `unordered`: the dispatch packet goes out without the barrier bit (hipExtAnyOrderLaunch), so the kernel may
-// start while the launches queued before it on the same stream are still draining -- the caller has promised that it
-// does not depend on them (weights at rest).  Later ordinary launches still wait for it.
-template <typename... KArgs, typename... Args>
-static inline void launch_k(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args)
-{
-    if (t_unordered) hipExtLaunchKernelGGL(kernel, grid, block, (unsigned)lds, st, nullptr, nullptr, hipExtAnyOrderLaunch, static_cast<KArgs>(args)...);
-    else hipLaunchKernelGGL(kernel, grid, block, (unsigned)lds, st, static_cast<KArgs>(args)...);
-}
 
 template <typename T, bool OVP, bool IDX, bool DYN>
 static int launch_uniform(const void *x, void *out, int16_t *idx, size_t rows, size_t vpr, const float *alpha,
@@ -73,57 +63,39 @@ static int launch_uniform(const void *x, void *out, int16_t *idx, size_t rows, s
         const uint4 *entries = tab + (pa.m_pad >> 2);
         const float *grid = reinterpret_cast<const float *>(tab);
         const dim3 grid_dim((unsigned)((total + 3) / 4)), block(256);
-#define ANTQ_LAUNCH_X(UU)                                                                                           \
-    launch_k(k_fq_xrow<T, OVP, IDX, UU, DYN>, grid_dim, block, 0, st, xv, ov, idx, (uint32_t)total,                 \
-             (uint32_t)vpr, (uint32_t)tpr, alpha, per_row, gmax, ratio, alpha_out, xa, entries, grid)
+        // every form of the kernel takes the same arguments
+        auto xrow = [&](auto kernel, dim3 g, dim3 b, bool unordered) {
+            launch_k(unordered, kernel, g, b, 0, st, xv, ov, idx, (uint32_t)total, (uint32_t)vpr, (uint32_t)tpr, alpha, per_row,
+                     gmax, ratio, alpha_out, xa, entries, grid);
+            return launch_status();
+        };
         // static rows, no index output: ONE wavefront per workgroup when the launch is unordered (or knob 6 = 1) -- the
         // tables are wave-private, there is no workgroup barrier, and wavefronts that start and retire one by one keep
         // the memory system busy across the launch boundary (tools/exp_lane.hip: 73.7 -> 74.7 % unordered, U = 4)
         if constexpr (!DYN && !IDX) {
             const int wpb = g_knob_waves ? g_knob_waves : (t_unordered ? 1 : 4);
             if (wpb == 1 && U >= 2 && U <= 4) {
-                const dim3 g1((unsigned)total), b1(64);
                 if (total > 0x7fffffffull) return ANTQ_ERR_UNSUPPORTED;
-#define ANTQ_LAUNCH_X1(UU)                                                                                          \
-    launch_k(k_fq_xrow<T, OVP, false, UU, false, 1, 1>, g1, b1, 0, st, xv, ov, idx, (uint32_t)total,                \
-             (uint32_t)vpr, (uint32_t)tpr, alpha, per_row, gmax, ratio, alpha_out, xa, entries, grid)
-                if (U == 4) ANTQ_LAUNCH_X1(4); else if (U == 3) ANTQ_LAUNCH_X1(3); else ANTQ_LAUNCH_X1(2);
-#undef ANTQ_LAUNCH_X1
-                return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+                return with_value<4, 3, 2>(U, [&](auto u) {
+                    return xrow(k_fq_xrow<T, OVP, false, decltype(u)::value, false, 1, 1>, dim3((unsigned)total), dim3(64), t_unordered);
+                });
             }
         }
-        if (wpr16) {
-            const dim3 g16((unsigned)rows), b16(1024);
-            if (U == 8)
-                hipLaunchKernelGGL((k_fq_xrow<T, OVP, IDX, 8, DYN, DYN ? 16 : 1>), g16, b16, 0, st, xv, ov, idx,
-                                   (uint32_t)total, (uint32_t)vpr, (uint32_t)tpr, alpha, per_row, gmax, ratio, alpha_out,
-                                   xa, entries, grid);
-            else
-                hipLaunchKernelGGL((k_fq_xrow<T, OVP, IDX, 4, DYN, DYN ? 16 : 1>), g16, b16, 0, st, xv, ov, idx,
-                                   (uint32_t)total, (uint32_t)vpr, (uint32_t)tpr, alpha, per_row, gmax, ratio, alpha_out,
-                                   xa, entries, grid);
-            return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+        if constexpr (DYN) {
+            // one row per workgroup of 4 / 16 wavefronts (always ordered); 8 vectors per lane, or 4 for every other U
+            if (wpr4 || wpr16)
+                return with_value<16, 4>(wpr16 ? 16 : 4, [&](auto w) {
+                    constexpr int WPR = decltype(w)::value;
+                    const dim3 g = WPR == 16 ? dim3((unsigned)rows) : grid_dim;
+                    return with_value<8, 4>(one_of<8>(U, 4), [&](auto u) {
+                        return xrow(k_fq_xrow<T, OVP, IDX, decltype(u)::value, true, WPR>, g, dim3(WPR == 16 ? 1024 : 256), false);
+                    });
+                });
         }
-        if (wpr4) {
-            if (U == 8)
-                hipLaunchKernelGGL((k_fq_xrow<T, OVP, IDX, 8, DYN, DYN ? 4 : 1>), grid_dim, block, 0, st, xv, ov, idx,
-                                   (uint32_t)total, (uint32_t)vpr, (uint32_t)tpr, alpha, per_row, gmax, ratio, alpha_out,
-                                   xa, entries, grid);
-            else
-                hipLaunchKernelGGL((k_fq_xrow<T, OVP, IDX, 4, DYN, DYN ? 4 : 1>), grid_dim, block, 0, st, xv, ov, idx,
-                                   (uint32_t)total, (uint32_t)vpr, (uint32_t)tpr, alpha, per_row, gmax, ratio, alpha_out,
-                                   xa, entries, grid);
-            return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
-        }
-        switch (U) {
-        case 8: ANTQ_LAUNCH_X(8); break;
-        case 4: ANTQ_LAUNCH_X(4); break;
-        case 3: ANTQ_LAUNCH_X(3); break;
-        case 2: ANTQ_LAUNCH_X(2); break;
-        default: ANTQ_LAUNCH_X(1); break;
-        }
-#undef ANTQ_LAUNCH_X
-        return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+        // (a forced U that is none of 8 / 4 / 3 / 2 launches the 1-vector kernel)
+        return with_value<8, 4, 3, 2, 1>(one_of<8, 4, 3, 2>(U, 1), [&](auto u) {
+            return xrow(k_fq_xrow<T, OVP, IDX, decltype(u)::value, DYN>, grid_dim, block, t_unordered);
+        });
     }
     // U: 1 .. 4 KiB of one row per task, keeping lane utilisation high at the row tail
     int U = 4;
@@ -152,20 +124,15 @@ static int launch_uniform(const void *x, void *out, int16_t *idx, size_t rows, s
         hipLaunchKernelGGL((k_fq_uniform<T, OVP, IDX, 4, false, true>), grid_l, block_l, lds, st, xv, ov, idx,
                            (uint32_t)((rows * ((vpr + 255) / 256))), (uint32_t)vpr, (uint32_t)((vpr + 255) / 256), alpha,
                            per_row, gmax, ratio, alpha_out, pa, tab);
-        return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+        return launch_status();
     }
     const dim3 grid((unsigned)blocks), block(256);
-#define ANTQ_LAUNCH_U(UU)                                                                                          \
-    hipLaunchKernelGGL((k_fq_uniform<T, OVP, IDX, UU, DYN>), grid, block, lds, st, xv, ov, idx, (uint32_t)total,  \
-                       (uint32_t)vpr, (uint32_t)tpr, alpha, per_row, gmax, ratio, alpha_out, pa, tab)
-    switch (U) {
-    case 8: ANTQ_LAUNCH_U(8); break;
-    case 4: ANTQ_LAUNCH_U(4); break;
-    case 2: ANTQ_LAUNCH_U(2); break;
-    default: ANTQ_LAUNCH_U(1); break;
-    }
-#undef ANTQ_LAUNCH_U
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    // (a forced U that is none of 8 / 4 / 2 launches the 1-vector kernel)
+    return with_value<8, 4, 2, 1>(one_of<8, 4, 2>(U, 1), [&](auto u) {
+        hipLaunchKernelGGL((k_fq_uniform<T, OVP, IDX, decltype(u)::value, DYN>), grid, block, lds, st, xv, ov, idx, (uint32_t)total,
+                           (uint32_t)vpr, (uint32_t)tpr, alpha, per_row, gmax, ratio, alpha_out, pa, tab);
+        return launch_status();
+    });
 }
 
 // 16-bit rows of >= 128 vectors in their own 16-bit domain (antq_k_hrow.h): one wavefront per workgroup, up to 4 KiB of
@@ -202,13 +169,20 @@ static int launch_hrow(const void *x, void *out, size_t rows, size_t vpr, const 
         const dim3 g((unsigned)((total + W - 1) / W)), b(64 * W);
         const uint4 *tl = plan_tlist_dev(plan_host, plan_dev);
         const float *grid = reinterpret_cast<const float *>(plan_tab_ptr(plan_dev));
-#define ANTQ_LAUNCH_H(UU, WW)                                                                                      \
-    launch_k(k_fq_hrow<T, OVP, UU, WW>, g, b, (WW) == 1 ? pad : 0u, st, static_cast<const uint4 *>(x), static_cast<uint4 *>(out), (uint32_t)total,  \
-             (uint32_t)vpr, (uint32_t)tpr, alpha, per_row, gmax, ha, tl, grid)
-        if (W == 4) { if (U == 4) ANTQ_LAUNCH_H(4, 4); else if (U == 3) ANTQ_LAUNCH_H(3, 4); else ANTQ_LAUNCH_H(2, 4); }
-        else { if (U == 8) ANTQ_LAUNCH_H(8, 1); else if (U == 4) ANTQ_LAUNCH_H(4, 1); else if (U == 3) ANTQ_LAUNCH_H(3, 1); else ANTQ_LAUNCH_H(2, 1); }
-#undef ANTQ_LAUNCH_H
-        return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+        // one wavefront per workgroup: 8 / 4 / 3 vectors per lane, 2 for every other U; four (knob 6): 4 / 3, 2 for every other
+        return with_value<4, 1>(W, [&](auto w) {
+            constexpr int WW = decltype(w)::value;
+            return with_value<8, 4, 3, 2>(one_of<8, 4, 3>(U, 2), [&](auto u) {
+                constexpr int UU = decltype(u)::value;
+                if constexpr (WW == 4 && UU == 8) {
+                    return (int)ANTQ_ERR_UNSUPPORTED;           // (no such kernel; unreachable: W == 4 lowered U from 8 to 4 above)
+                } else {
+                    launch_k(t_unordered, k_fq_hrow<T, OVP, UU, WW>, g, b, WW == 1 ? pad : 0u, st, static_cast<const uint4 *>(x),
+                             static_cast<uint4 *>(out), (uint32_t)total, (uint32_t)vpr, (uint32_t)tpr, alpha, per_row, gmax, ha, tl, grid);
+                    return launch_status();
+                }
+            });
+        });
     }
 }
 
@@ -267,14 +241,23 @@ static int launch_fq(const void *x, void *out, int16_t *idx, size_t rows, size_t
             if (blocks > 0x7fffffffull) return ANTQ_ERR_UNSUPPORTED;
             const uint4 *xv = static_cast<const uint4 *>(x);
             uint4 *ov = static_cast<uint4 *>(out);
-#define ANTQ_LANE(UU, WW, AA)                                                                                          \
-    launch_k(k_fq_lane<T, OVP, IDX, UU, false, AA, WW>, dim3((unsigned)blocks), dim3(64 * WW), lds, st, xv, ov, idx, n_vec,  \
-             (uint32_t)vpr, vshift, alpha, per_row, gmax, 1.0f, (float *)nullptr, pa, tab)
-            if (!pa.adom) ANTQ_LANE(2, 4, false);
-            else if constexpr (IDX) ANTQ_LANE(2, 4, true);
-            else if (W == 1) { if (U == 1) ANTQ_LANE(1, 1, true); else if (U == 2) ANTQ_LANE(2, 1, true); else ANTQ_LANE(4, 1, true); }
-            else             { if (U == 1) ANTQ_LANE(1, 4, true); else if (U == 2) ANTQ_LANE(2, 4, true); else ANTQ_LANE(4, 4, true); }
-#undef ANTQ_LANE
+            // plans without the approximate-quotient form and launches with an index output have the one shape above
+            // (4 wavefronts, 2 vectors per lane)
+            auto lane = [&](auto kernel, int w) {
+                launch_k(t_unordered, kernel, dim3((unsigned)blocks), dim3(64 * w), lds, st, xv, ov, idx, n_vec, (uint32_t)vpr, vshift,
+                         alpha, per_row, gmax, 1.0f, (float *)nullptr, pa, tab);
+                return launch_status();
+            };
+            if (!pa.adom) return lane(k_fq_lane<T, OVP, IDX, 2, false, false, 4>, 4);
+            if constexpr (IDX) {
+                return lane(k_fq_lane<T, OVP, true, 2, false, true, 4>, 4);
+            } else {
+                return with_value<1, 4>(W, [&](auto w) {
+                    return with_value<1, 2, 4>(U, [&](auto u) {
+                        return lane(k_fq_lane<T, OVP, false, decltype(u)::value, false, true, decltype(w)::value>, decltype(w)::value);
+                    });
+                });
+            }
         }
     } else if (aligned && !per_row && n >= (size_t)64 * EPL) {
         // per-tensor scale with a ragged tail: vector body + element tail
@@ -285,28 +268,15 @@ static int launch_fq(const void *x, void *out, int16_t *idx, size_t rows, size_t
         const size_t pairs = (n_tail + 1) / 2;
         hipLaunchKernelGGL((k_fq_scalar<T, OVP, IDX>), dim3((unsigned)((pairs + 255) / 256)), dim3(256), lds, st, x, out,
                            idx, n_body, n_tail, n, n, alpha, 0, gmax, pa, tab);
+        return launch_status();
     } else {
         const size_t pairs = (n + 1) / 2;
         const size_t blocks = (pairs + 255) / 256;
         if (blocks > 0x7fffffffull) return ANTQ_ERR_UNSUPPORTED;
         hipLaunchKernelGGL((k_fq_scalar<T, OVP, IDX>), dim3((unsigned)blocks), dim3(256), lds, st, x, out, idx,
                            (size_t)0, n, n, row_len, alpha, per_row, gmax, pa, tab);
+        return launch_status();
     }
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
-}
-
-template <typename T>
-static int launch_fq_flags(const void *x, void *out, int16_t *idx, size_t rows, size_t row_len,
-                           const float *alpha, int per_row, float gmax, const PlanArgs &pa,
-                           const void *plan_host, const void *plan_dev, unsigned flags, hipStream_t st)
-{
-    const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
-    if (ovp) {
-        if (idx) return launch_fq<T, true, true>(x, out, idx, rows, row_len, alpha, per_row, gmax, pa, plan_host, plan_dev, st);
-        return launch_fq<T, true, false>(x, out, idx, rows, row_len, alpha, per_row, gmax, pa, plan_host, plan_dev, st);
-    }
-    if (idx) return launch_fq<T, false, true>(x, out, idx, rows, row_len, alpha, per_row, gmax, pa, plan_host, plan_dev, st);
-    return launch_fq<T, false, false>(x, out, idx, rows, row_len, alpha, per_row, gmax, pa, plan_host, plan_dev, st);
 }
 
 template <typename T, bool OVP, bool IDX>
@@ -330,15 +300,12 @@ static int launch_dynamic(const void *x, void *out, int16_t *idx, float *alpha_o
             constexpr int U = 2;
             const size_t blocks = (n_vec + 256 * U - 1) / (256 * U);
             if (blocks > 0x7fffffffull) return ANTQ_ERR_UNSUPPORTED;
-            if (pa.adom)
-                hipLaunchKernelGGL((k_fq_lane<T, OVP, IDX, U, true, true>), dim3((unsigned)blocks), dim3(256), lds, st,
+            return with_bool(pa.adom != 0u, [&](auto ad) {
+                hipLaunchKernelGGL((k_fq_lane<T, OVP, IDX, U, true, decltype(ad)::value>), dim3((unsigned)blocks), dim3(256), lds, st,
                                    static_cast<const uint4 *>(x), static_cast<uint4 *>(out), idx, n_vec, (uint32_t)vpr,
                                    vshift, (const float *)nullptr, 1, gmax, ratio, alpha_out, pa, tab);
-            else
-                hipLaunchKernelGGL((k_fq_lane<T, OVP, IDX, U, true, false>), dim3((unsigned)blocks), dim3(256), lds, st,
-                                   static_cast<const uint4 *>(x), static_cast<uint4 *>(out), idx, n_vec, (uint32_t)vpr,
-                                   vshift, (const float *)nullptr, 1, gmax, ratio, alpha_out, pa, tab);
-            return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+                return launch_status();
+            });
         }
         if constexpr (!IDX && !std::is_same<T, float>::value) {
             // 16-bit rows of 128 .. 8192 vectors in their own domain (antq_k_hrow.h): the row in 1 / 4 / 16 wavefronts
@@ -350,11 +317,14 @@ static int launch_dynamic(const void *x, void *out, int16_t *idx, float *alpha_o
                 const uint4 *tl = plan_tlist_dev(plan_host, plan_dev);
                 const float *grid = reinterpret_cast<const float *>(tab);
                 const dim3 g((unsigned)rows), b(64u * sh.wpr);
-#define ANTQ_HD(WW) hipLaunchKernelGGL((k_fq_hrow_dyn<T, OVP, WW>), g, b, (WW) == 1 ? pad : 0u, st, static_cast<const uint4 *>(x), \
-                                       static_cast<uint4 *>(out), (uint32_t)rows, (uint32_t)vpr, (uint32_t)sh.vpt, ratio, alpha_out, gmax, ha, tl, grid)
-                if (sh.wpr == 1) ANTQ_HD(1); else if (sh.wpr == 4) ANTQ_HD(4); else ANTQ_HD(16);
-#undef ANTQ_HD
-                return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+                // (hrow_dyn_shape: 1, 4 or 16 wavefronts per row)
+                return with_value<1, 4, 16>(one_of<1, 4>(sh.wpr, 16), [&](auto w) {
+                    constexpr int WW = decltype(w)::value;
+                    hipLaunchKernelGGL((k_fq_hrow_dyn<T, OVP, WW>), g, b, WW == 1 ? pad : 0u, st, static_cast<const uint4 *>(x),
+                                       static_cast<uint4 *>(out), (uint32_t)rows, (uint32_t)vpr, (uint32_t)sh.vpt, ratio, alpha_out,
+                                       gmax, ha, tl, grid);
+                    return launch_status();
+                });
             }
         }
         if (vpr <= 8192) {
@@ -372,20 +342,6 @@ static int launch_dynamic(const void *x, void *out, int16_t *idx, float *alpha_o
     if (rc != ANTQ_OK) return rc;
     hipLaunchKernelGGL(k_scale_inplace, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, alpha_out, rows, ratio);
     return launch_fq<T, OVP, IDX>(x, out, idx, rows, row_len, alpha_out, 1, gmax, pa, plan_host, plan_dev, st);
-}
-
-template <typename T>
-static int launch_dynamic_flags(const void *x, void *out, int16_t *idx, float *alpha_out, size_t rows, size_t row_len,
-                                float ratio, float gmax, const PlanArgs &pa, const void *plan_host, const void *plan_dev, unsigned flags,
-                                hipStream_t st)
-{
-    const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
-    if (ovp) {
-        if (idx) return launch_dynamic<T, true, true>(x, out, idx, alpha_out, rows, row_len, ratio, gmax, pa, plan_host, plan_dev, st);
-        return launch_dynamic<T, true, false>(x, out, idx, alpha_out, rows, row_len, ratio, gmax, pa, plan_host, plan_dev, st);
-    }
-    if (idx) return launch_dynamic<T, false, true>(x, out, idx, alpha_out, rows, row_len, ratio, gmax, pa, plan_host, plan_dev, st);
-    return launch_dynamic<T, false, false>(x, out, idx, alpha_out, rows, row_len, ratio, gmax, pa, plan_host, plan_dev, st);
 }
 
 }  // namespace antq
@@ -407,19 +363,17 @@ extern "C" int antq_fakequant(const void *x, void *out, int16_t *idx, size_t row
         explicit Unordered(bool on) { t_unordered = on; }
         ~Unordered() { t_unordered = false; }
     } scope((flags & ANTQ_FLAG_UNORDERED) != 0);
-    switch (dtype) {
-    case ANTQ_F32:
-        if (reinterpret_cast<uintptr_t>(x) % 4 || reinterpret_cast<uintptr_t>(out) % 4) return ANTQ_ERR_ALIGN;
-        return launch_fq_flags<float>(x, out, idx, rows, row_len, alpha, per_row, gmax, pa, plan_host, plan_dev, flags, st);
-    case ANTQ_BF16:
-        if (reinterpret_cast<uintptr_t>(x) % 2 || reinterpret_cast<uintptr_t>(out) % 2) return ANTQ_ERR_ALIGN;
-        return launch_fq_flags<bf16_tag>(x, out, idx, rows, row_len, alpha, per_row, gmax, pa, plan_host, plan_dev, flags, st);
-    case ANTQ_F16:
-        if (reinterpret_cast<uintptr_t>(x) % 2 || reinterpret_cast<uintptr_t>(out) % 2) return ANTQ_ERR_ALIGN;
-        return launch_fq_flags<f16_tag>(x, out, idx, rows, row_len, alpha, per_row, gmax, pa, plan_host, plan_dev, flags, st);
-    default:
-        return ANTQ_ERR_UNSUPPORTED;
-    }
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        const uintptr_t esz = sizeof(T) == 4 ? 4 : 2;       // (the 16-bit tags are empty types)
+        if (reinterpret_cast<uintptr_t>(x) % esz || reinterpret_cast<uintptr_t>(out) % esz) return (int)ANTQ_ERR_ALIGN;
+        return with_bool((flags & ANTQ_FLAG_OVP) != 0, [&](auto ovp) {
+            return with_bool(idx != nullptr, [&](auto want_idx) {
+                return launch_fq<T, decltype(ovp)::value, decltype(want_idx)::value>(x, out, idx, rows, row_len, alpha, per_row, gmax,
+                                                                                     pa, plan_host, plan_dev, st);
+            });
+        });
+    });
 }
 
 extern "C" int antq_fakequant_dynamic(const void *x, void *out, int16_t *idx, float *alpha_out, size_t rows,
@@ -431,12 +385,14 @@ extern "C" int antq_fakequant_dynamic(const void *x, void *out, int16_t *idx, fl
     PlanArgs pa;
     if (!plan_args_from_host(plan_host, pa)) return ANTQ_ERR_PLAN;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-    case ANTQ_F32: return launch_dynamic_flags<float>(x, out, idx, alpha_out, rows, row_len, ratio, gmax, pa, plan_host, plan_dev, flags, st);
-    case ANTQ_BF16: return launch_dynamic_flags<bf16_tag>(x, out, idx, alpha_out, rows, row_len, ratio, gmax, pa, plan_host, plan_dev, flags, st);
-    case ANTQ_F16: return launch_dynamic_flags<f16_tag>(x, out, idx, alpha_out, rows, row_len, ratio, gmax, pa, plan_host, plan_dev, flags, st);
-    default: return ANTQ_ERR_UNSUPPORTED;
-    }
+    return with_dtype(dtype, [&](auto tag) {
+        return with_bool((flags & ANTQ_FLAG_OVP) != 0, [&](auto ovp) {
+            return with_bool(idx != nullptr, [&](auto want_idx) {
+                return launch_dynamic<decltype(tag), decltype(ovp)::value, decltype(want_idx)::value>(
+                    x, out, idx, alpha_out, rows, row_len, ratio, gmax, pa, plan_host, plan_dev, st);
+            });
+        });
+    });
 }
 
 namespace antq {

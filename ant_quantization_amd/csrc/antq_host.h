@@ -17,30 +17,37 @@
 
 namespace antq {
 
-// tuning knobs (dev / bench only; see antq_debug_set).  THREAD-LOCAL: they change the dispatch of the calling thread's
-// later calls only, so a probe that forgets to reset them cannot change which kernel another thread's calls run, and the
-// library keeps no process-global mutable state.  Defined in antq_kernels.hip.
-extern thread_local int g_knob_u;             // force U of the uniform kernel (0 = heuristic)
-extern thread_local int g_knob_encwg;         // persistent workgroups of the 4-bit encoder (256 CUs x 8)
-extern thread_local int g_knob_x;             // 0 disables the x-domain row kernel (A/B measurements)
-extern thread_local int g_knob_nearest_fast;  // 0: antq_nearest always runs the literal scan
-extern thread_local int g_knob_lane_rows;     // 0: rows of a power of two of vectors through the per-row table kernels (A/B)
-extern thread_local int g_knob_a;             // 0 disables the approximate-quotient element path (quant_vec_a): exact division
-extern thread_local int g_knob_waves;         // wavefronts per workgroup of the streaming kernels: 0 = the measured default, 1 / 2 / 4 (A/B)
-extern thread_local int g_knob_rot;            // 1: rotate the workgroup -> task map of the batched row kernel per group of 8 (XCD balance)
-extern thread_local int g_knob_lane_u;        // vectors per lane of the one-launch-per-tensor lane kernel: 0 = default (A/B)
-extern thread_local int g_knob_h;             // 0 disables the 16-bit-domain row kernels (antq_k_hrow.h; A/B measurements)
-extern thread_local int g_knob_hist;          // clip search of 16-bit per-tensor quantisers on the tensor's histogram: 0 off, 1 when it pays, 2 always (tests)
-extern thread_local int g_knob_sweep;         // 0: per-row clip searches through the direct kernels instead of the threshold sweep (A/B, tests)
-extern thread_local int g_knob_sort_short;    // 0: rows of <= 1024 elements through the 4096-key sorted search instead of the one-row-per-wavefront kernel (A/B)
-extern thread_local int g_knob_sort;          // clip searches from the sorted row (antq_k_sortsearch.h): 0 off, 1 the default rule, 2 every eligible launch (tests)
-extern thread_local int g_knob_tk_group, g_knob_tk_blocks;   // A/B of the one-launch reductions (antq_k_reduce.h)
-extern thread_local int g_knob_rows_stream;   // 0: row abs-max of 128..1024-vector rows through the round-5 kernel (A/B)
-extern thread_local int g_knob_hist_xmax;     // antq_calibrate: the abs-max statistic of a histogram-searched tensor from the counting pass (1) or from its own pass (0)
-extern thread_local int g_knob_exp;           // experiment switch of the kernel under development (A/B; 0 = off)
-extern thread_local int g_knob_schunks;       // clip search: candidate-list chunks (blockIdx.y) forced to this many (A/B; 0 = cost model)
-extern thread_local int g_knob_dlds;          // extra dynamic LDS bytes of the d-domain batched kernels' workgroups (occupancy A/B)
-extern thread_local int g_knob_hlds;          // dynamic LDS of those kernels' workgroups (occupancy, A/B): -1 = kHRowLdsPad
+// tuning knobs (dev / bench only; see antq_debug_set and the description of every key in include/antq.h).  THREAD-LOCAL:
+// they change the dispatch of the calling thread's later calls only, so a probe that forgets to reset them cannot change
+// which kernel another thread's calls run, and the library keeps no process-global mutable state.
+// ONE list -- X(key of antq_debug_set, name, default) -- makes the declarations below, the definitions and the setter
+// (antq_kernels.hip).  A launcher reads knob `name` as g_knob_name.
+#define ANTQ_KNOBS(X)                                                                                                      \
+    X(0, u, 0)             /* force U of the uniform kernel (0 = heuristic) */                                             \
+    X(1, encwg, 2048)      /* persistent workgroups of the 4-bit encoder (256 CUs x 8); a value <= 0 means 2048 */         \
+    X(2, x, 1)             /* 0 disables the x-domain row kernel (A/B measurements) */                                     \
+    X(3, nearest_fast, 1)  /* 0: antq_nearest always runs the literal scan */                                              \
+    X(4, a, 1)             /* 0 disables the approximate-quotient element path (quant_vec_a): exact division */            \
+    X(5, lane_rows, 1)     /* 0: rows of a power of two of vectors through the per-row table kernels (A/B) */              \
+    X(6, waves, 0)         /* wavefronts per workgroup of the streaming kernels: 0 = the measured default, 1 / 2 / 4 */    \
+    X(7, lane_u, 0)        /* vectors per lane of the one-launch-per-tensor lane kernel: 0 = default (A/B) */              \
+    X(8, rot, 0)           /* 1: rotate the workgroup -> task map of the batched row kernel per group of 8 (XCD balance) */ \
+    X(9, h, 1)             /* 0 disables the 16-bit-domain row kernels (antq_k_hrow.h; A/B measurements) */                \
+    X(10, hlds, -1)        /* dynamic LDS of those kernels' workgroups (occupancy, A/B): -1 = kHRowLdsPad */               \
+    X(11, dlds, -1)        /* extra dynamic LDS bytes of the d-domain batched kernels' workgroups (occupancy A/B) */       \
+    X(12, schunks, 0)      /* clip search: candidate-list chunks (blockIdx.y) forced to this many (A/B; 0 = cost model) */ \
+    X(13, exp, 0)          /* experiment switch of the kernel under development (A/B; 0 = off) */                          \
+    X(14, hist, 1)         /* clip search of 16-bit per-tensor quantisers on the histogram: 0 off, 1 when it pays, 2 always */ \
+    X(15, hist_xmax, 1)    /* antq_calibrate: abs-max of a histogram-searched tensor from the counting pass (1) or its own pass (0) */ \
+    X(16, rows_stream, 1)  /* 0: row abs-max of 128..1024-vector rows through the round-5 kernel (A/B) */                   \
+    X(17, tk_group, 0)     /* workgroups per ticket group of the one-launch reductions (antq_k_reduce.h; 0 = default, clamped) */ \
+    X(18, tk_blocks, 0)    /* workgroups of the one-launch reductions (0 = default, clamped) */                            \
+    X(19, sweep, 1)        /* per-row clip searches through the threshold sweep (antq_k_sweep.h): 0 = the direct kernels, 2 = every eligible launch */ \
+    X(20, sort, 1)         /* clip searches from the sorted row (antq_k_sortsearch.h): 0 off, 1 the default rule, 2 every eligible launch */ \
+    X(21, sort_short, 1)   /* 0: rows of <= 1024 elements through the 4096-key sorted search (A/B) */
+#define ANTQ_KNOB_DECLARE(key, name, dflt) extern thread_local int g_knob_##name;
+ANTQ_KNOBS(ANTQ_KNOB_DECLARE)
+#undef ANTQ_KNOB_DECLARE
 
 static inline bool plan_args_from_host(const void *plan_host, PlanArgs &pa)
 {

@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "antq_host.h"
+#include "antq_dispatch.h"
 #include "antq_k_fakequant.h"
 #include "antq_k_nearest.h"
 #include "antq_k_aux.h"
@@ -31,28 +32,9 @@
 
 namespace antq {
 
-thread_local int g_knob_u = 0;
-thread_local int g_knob_encwg = 2048;
-thread_local int g_knob_x = 1;
-thread_local int g_knob_nearest_fast = 1;
-thread_local int g_knob_lane_rows = 1;
-thread_local int g_knob_a = 1;
-thread_local int g_knob_waves = 0;
-thread_local int g_knob_lane_u = 0;
-thread_local int g_knob_rot = 0;
-thread_local int g_knob_h = 1;
-thread_local int g_knob_hlds = -1;
-thread_local int g_knob_dlds = -1;
-thread_local int g_knob_schunks = 0;
-thread_local int g_knob_exp = 0;
-thread_local int g_knob_hist = 1;
-thread_local int g_knob_hist_xmax = 1;
-thread_local int g_knob_rows_stream = 1;
-thread_local int g_knob_tk_group = 0;     // A/B: workgroups per ticket group of the one-launch reductions (0 = default)
-thread_local int g_knob_tk_blocks = 0;
-thread_local int g_knob_sort_short = 1;
-thread_local int g_knob_sort = 1;         // clip searches from the sorted row (antq_k_sortsearch.h): 0 off, 1 default rule, 2 every eligible launch
-thread_local int g_knob_sweep = 1;        // per-row clip searches through the threshold-sweep kernel (antq_k_sweep.h): 0 = the direct kernels (A/B, tests)    // A/B: workgroups of the one-launch reductions (0 = default)
+#define ANTQ_KNOB_DEFINE(key, name, dflt) thread_local int g_knob_##name = dflt;
+ANTQ_KNOBS(ANTQ_KNOB_DEFINE)
+#undef ANTQ_KNOB_DEFINE
 
 }  // namespace antq
 
@@ -76,6 +58,21 @@ extern "C" const char *antq_strerror(int code)
     }
 }
 
+// fp32 / fp64: the binary search for grids of at most 256 values (knob 3), the literal scan otherwise
+template <typename F>
+static int launch_nearest(const void *x, void *z, int16_t *idx, size_t n, const void *grid, int m, hipStream_t st)
+{
+    const size_t blocks = (n + 1023) / 1024;
+    if (blocks > 0x7fffffffull) return ANTQ_ERR_UNSUPPORTED;
+    if (m <= 256 && g_knob_nearest_fast)
+        hipLaunchKernelGGL((k_nearest_fast<F>), dim3((unsigned)((n + 2047) / 2048)), dim3(256), 0, st, static_cast<const F *>(x),
+                           static_cast<F *>(z), idx, n, static_cast<const F *>(grid), m);
+    else
+        hipLaunchKernelGGL((k_nearest<F>), dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const F *>(x), static_cast<F *>(z),
+                           idx, n, static_cast<const F *>(grid), m);
+    return launch_status();
+}
+
 extern "C" int antq_nearest(const void *x, void *z, int16_t *idx, size_t n, const void *grid, int m, int dtype,
                             void *stream)
 {
@@ -83,41 +80,21 @@ extern "C" int antq_nearest(const void *x, void *z, int16_t *idx, size_t n, cons
     if (!x || !z || !grid || m < 1) return ANTQ_ERR_ARG;
     if (m > ANTQ_MAX_GRID) return ANTQ_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == ANTQ_F32 || dtype == ANTQ_F64) {
-        const size_t blocks = (n + 1023) / 1024;
-        if (blocks > 0x7fffffffull) return ANTQ_ERR_UNSUPPORTED;
-        if (dtype == ANTQ_F32) {
-            if (m <= 256 && g_knob_nearest_fast)
-                hipLaunchKernelGGL((k_nearest_fast<float>), dim3((unsigned)((n + 2047) / 2048)), dim3(256), 0, st,
-                                   static_cast<const float *>(x), static_cast<float *>(z), idx, n,
-                                   static_cast<const float *>(grid), m);
-            else
-                hipLaunchKernelGGL((k_nearest<float>), dim3((unsigned)blocks), dim3(256), 0, st,
-                                   static_cast<const float *>(x), static_cast<float *>(z), idx, n,
-                                   static_cast<const float *>(grid), m);
+    if (dtype == ANTQ_F64) return launch_nearest<double>(x, z, idx, n, grid, m, st);    // (the one entry point that takes float64)
+    bool known = false;
+    const int rc = with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        known = true;
+        if constexpr (std::is_same<T, float>::value) {
+            return launch_nearest<float>(x, z, idx, n, grid, m, st);
         } else {
-            if (m <= 256 && g_knob_nearest_fast)
-                hipLaunchKernelGGL((k_nearest_fast<double>), dim3((unsigned)((n + 2047) / 2048)), dim3(256), 0, st,
-                                   static_cast<const double *>(x), static_cast<double *>(z), idx, n,
-                                   static_cast<const double *>(grid), m);
-            else
-                hipLaunchKernelGGL((k_nearest<double>), dim3((unsigned)blocks), dim3(256), 0, st,
-                                   static_cast<const double *>(x), static_cast<double *>(z), idx, n,
-                                   static_cast<const double *>(grid), m);
+            const size_t blocks = (n + 255) / 256;
+            if (blocks > 0x7fffffffull) return (int)ANTQ_ERR_UNSUPPORTED;
+            hipLaunchKernelGGL((k_nearest16<T>), dim3((unsigned)blocks), dim3(256), 0, st, x, z, idx, n, static_cast<const float *>(grid), m);
+            return launch_status();
         }
-    } else if (dtype == ANTQ_BF16 || dtype == ANTQ_F16) {
-        const size_t blocks = (n + 255) / 256;
-        if (blocks > 0x7fffffffull) return ANTQ_ERR_UNSUPPORTED;
-        if (dtype == ANTQ_BF16)
-            hipLaunchKernelGGL((k_nearest16<bf16_tag>), dim3((unsigned)blocks), dim3(256), 0, st, x, z, idx, n,
-                               static_cast<const float *>(grid), m);
-        else
-            hipLaunchKernelGGL((k_nearest16<f16_tag>), dim3((unsigned)blocks), dim3(256), 0, st, x, z, idx, n,
-                               static_cast<const float *>(grid), m);
-    } else {
-        return ANTQ_ERR_ARG;
-    }
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    });
+    return known ? rc : ANTQ_ERR_ARG;            // (an unknown dtype is an argument error here, not ANTQ_ERR_UNSUPPORTED)
 }
 
 // quant_cuda.quant for a grid the caller has a plan for (quantisers' static codebooks): table lookup instead of the scan.
@@ -145,23 +122,24 @@ static int launch_nearest_plan(const void *x, void *z, int16_t *idx, size_t n, c
     const uint4 *xv = static_cast<const uint4 *>(x);
     uint4 *zv = static_cast<uint4 *>(z);
     const uint4 *tab = plan_tab_ptr(plan_dev);
-#define ANTQ_LAUNCH_N2(TT, II, HH, UU)                                                                             \
-    hipLaunchKernelGGL((k_nearest_plan<TT, II, HH, UU>), dim3((unsigned)blocks), dim3(256), lds, st, xv, zv, idx, n_vec, pa, \
-                       tab, gcheck, stale)
-#define ANTQ_LAUNCH_N(TT)                                                                                          \
-    do {                                                                                                           \
-        if (gcheck) { if (idx) ANTQ_LAUNCH_N2(TT, true, true, 4); else ANTQ_LAUNCH_N2(TT, false, true, 4); }       \
-        else if (u2) { if (idx) ANTQ_LAUNCH_N2(TT, true, false, 2); else ANTQ_LAUNCH_N2(TT, false, false, 2); }    \
-        else { if (idx) ANTQ_LAUNCH_N2(TT, true, false, 4); else ANTQ_LAUNCH_N2(TT, false, false, 4); }            \
-    } while (0)
-    switch (dtype) {
-    case ANTQ_F32: ANTQ_LAUNCH_N(float); break;
-    case ANTQ_BF16: ANTQ_LAUNCH_N(bf16_tag); break;
-    default: ANTQ_LAUNCH_N(f16_tag); break;
-    }
-#undef ANTQ_LAUNCH_N
-#undef ANTQ_LAUNCH_N2
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    // hinted: 4 vectors per lane; plain: 2 when the table is small, 4 otherwise
+    return with_dtype(dtype, [&](auto tag) {
+        return with_bool(idx != nullptr, [&](auto want_idx) {
+            return with_bool(gcheck != nullptr, [&](auto hinted) {
+                return with_value<2, 4>(u2 ? 2 : 4, [&](auto u) {
+                    constexpr bool HH = decltype(hinted)::value;
+                    constexpr int UU = decltype(u)::value;
+                    if constexpr (HH && UU == 2) {
+                        return (int)ANTQ_ERR_UNSUPPORTED;       // (no such kernel; unreachable: u2 requires !gcheck)
+                    } else {
+                        hipLaunchKernelGGL((k_nearest_plan<decltype(tag), decltype(want_idx)::value, HH, UU>), dim3((unsigned)blocks),
+                                           dim3(256), lds, st, xv, zv, idx, n_vec, pa, tab, gcheck, stale);
+                        return launch_status();
+                    }
+                });
+            });
+        });
+    });
 }
 
 extern "C" int antq_nearest_plan(const void *x, void *z, int16_t *idx, size_t n, const void *plan_host, const void *plan_dev,
@@ -193,13 +171,13 @@ extern "C" int antq_affine(const float *x, float *out, int32_t *q, size_t rows, 
         hipLaunchKernelGGL(k_affine_vec, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const uint4 *>(x),
                            reinterpret_cast<uint4 *>(out), reinterpret_cast<int4 *>(q), n_vec, vpr, k, xmin, xmax,
                            per_row ? 1 : 0);
-        return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+        return launch_status();
     }
     const size_t blocks = (n + 255) / 256;
     if (blocks > 0x7fffffffull) return ANTQ_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_affine, dim3((unsigned)blocks), dim3(256), 0, st, x, out, q, n,
                        row_len, k, xmin, xmax, per_row ? 1 : 0);
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return launch_status();
 }
 
 extern "C" int antq_copy(const void *src, void *dst, size_t bytes, void *stream)
@@ -212,7 +190,7 @@ extern "C" int antq_copy(const void *src, void *dst, size_t bytes, void *stream)
     if (blocks > 0x7fffffffull) return ANTQ_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_copy, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint4 *>(src), static_cast<uint4 *>(dst), n_vec);
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return launch_status();
 }
 
 // HIP loads a translation unit's code object when one of its kernels is first launched (or asked about): ~50 ms for the
@@ -236,29 +214,13 @@ extern "C" int antq_prefetch_kernels(void)
 
 extern "C" int antq_debug_set(int key, int value)
 {
-    if (key == 0) g_knob_u = value;
-    else if (key == 1) g_knob_encwg = value > 0 ? value : 2048;
-    else if (key == 2) g_knob_x = value;
-    else if (key == 3) g_knob_nearest_fast = value;
-    else if (key == 4) g_knob_a = value;
-    else if (key == 5) g_knob_lane_rows = value;
-    else if (key == 6) g_knob_waves = value;
-    else if (key == 7) g_knob_lane_u = value;
-    else if (key == 8) g_knob_rot = value;
-    else if (key == 9) g_knob_h = value;
-    else if (key == 10) g_knob_hlds = value;
-    else if (key == 11) g_knob_dlds = value;
-    else if (key == 12) g_knob_schunks = value;
-    else if (key == 13) g_knob_exp = value;
-    else if (key == 14) g_knob_hist = value;
-    else if (key == 15) g_knob_hist_xmax = value;
-    else if (key == 16) g_knob_rows_stream = value;
-    else if (key == 17) g_knob_tk_group = value;
-    else if (key == 18) g_knob_tk_blocks = value;
-    else if (key == 19) g_knob_sweep = value;
-    else if (key == 20) g_knob_sort = value;
-    else if (key == 21) g_knob_sort_short = value;
-    else return ANTQ_ERR_ARG;
+    if (key == 1) { g_knob_encwg = value > 0 ? value : 2048; return ANTQ_OK; }      // (the one knob with a rule of its own)
+    switch (key) {
+#define ANTQ_KNOB_SET(k, name, dflt) case k: g_knob_##name = value; break;
+    ANTQ_KNOBS(ANTQ_KNOB_SET)
+#undef ANTQ_KNOB_SET
+    default: return ANTQ_ERR_ARG;
+    }
     return ANTQ_OK;
 }
 
@@ -279,7 +241,7 @@ static int launch_absmax(const void *x, float *amax, size_t rows, size_t row_len
             if (gblocks > 0x7fffffffull) return ANTQ_ERR_UNSUPPORTED;
             hipLaunchKernelGGL((k_absmax_groups<T>), dim3((unsigned)gblocks), dim3(256), 0, st, static_cast<const uint4 *>(x), amax,
                                n_vec, (uint32_t)vpr, vshift);
-            return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+            return launch_status();
         }
     }
     if (per_row && vec_ok && g_knob_rows_stream && rows <= 0x7fffffffull) {
@@ -287,13 +249,11 @@ static int launch_absmax(const void *x, float *amax, size_t rows, size_t row_len
         const size_t vpr = row_len / EPL;
         const dim3 g((unsigned)(rows < 262144u ? rows : 262144u)), b(64);
         const uint4 *xv = static_cast<const uint4 *>(x);
-        bool done = true;
-        if (vpr == 128) hipLaunchKernelGGL((k_absmax_rows<T, 2>), g, b, 0, st, xv, amax, (uint32_t)rows);
-        else if (vpr == 256) hipLaunchKernelGGL((k_absmax_rows<T, 4>), g, b, 0, st, xv, amax, (uint32_t)rows);
-        else if (vpr == 512) hipLaunchKernelGGL((k_absmax_rows<T, 8>), g, b, 0, st, xv, amax, (uint32_t)rows);
-        else if (vpr == 1024) hipLaunchKernelGGL((k_absmax_rows<T, 16>), g, b, 0, st, xv, amax, (uint32_t)rows);
-        else done = false;
-        if (done) return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+        if (vpr == 128 || vpr == 256 || vpr == 512 || vpr == 1024)
+            return with_value<2, 4, 8, 16>((int)(vpr / 64), [&](auto u) {      // (vectors per lane)
+                hipLaunchKernelGGL((k_absmax_rows<T, decltype(u)::value>), g, b, 0, st, xv, amax, (uint32_t)rows);
+                return launch_status();
+            });
     }
     size_t waves = per_row ? rows : (rows * row_len + 64 * EPL * 4 - 1) / (64 * EPL * 4);
     size_t blocks = (waves + 3) / 4;
@@ -308,7 +268,7 @@ static int launch_absmax(const void *x, float *amax, size_t rows, size_t row_len
     // the whole-tensor maximum is an atomicMax of workgroup maxima into a zero (stream-ordered, capturable)
     if (!per_row && zero) hipLaunchKernelGGL(k_zero_f32, dim3(1), dim3(64), 0, st, amax);
     hipLaunchKernelGGL((k_absmax<T>), dim3((unsigned)blocks), dim3(256), 0, st, x, amax, rows, row_len, per_row, vec_ok);
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return launch_status();
 }
 }  // namespace antq
 
@@ -329,7 +289,7 @@ static int launch_alpha_grad(const void *x, const void *out, const void *gout, d
     hipLaunchKernelGGL((k_alpha_grad<T>), dim3((unsigned)blocks), dim3(256), 0, st, x, out, gout, gsum, ws, rows, row_len,
                        per_row, vec_ok);
     if (!per_row) hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, st, ws, (uint32_t)blocks, 1, gsum);
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return launch_status();
 }
 }  // namespace antq
 
@@ -340,12 +300,7 @@ extern "C" int antq_alpha_grad(const void *x, const void *out, const void *gout,
     if (!x || !out || !gout || !gsum || (!per_row && !workspace)) return ANTQ_ERR_ARG;
     double *ws = static_cast<double *>(workspace);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-    case ANTQ_F32: return launch_alpha_grad<float>(x, out, gout, gsum, ws, rows, row_len, per_row ? 1 : 0, st);
-    case ANTQ_BF16: return launch_alpha_grad<bf16_tag>(x, out, gout, gsum, ws, rows, row_len, per_row ? 1 : 0, st);
-    case ANTQ_F16: return launch_alpha_grad<f16_tag>(x, out, gout, gsum, ws, rows, row_len, per_row ? 1 : 0, st);
-    default: return ANTQ_ERR_UNSUPPORTED;
-    }
+    return with_dtype(dtype, [&](auto tag) { return launch_alpha_grad<decltype(tag)>(x, out, gout, gsum, ws, rows, row_len, per_row ? 1 : 0, st); });
 }
 
 namespace antq {
@@ -362,7 +317,7 @@ static int launch_moments(const void *x, double *sums, double *ws, size_t rows, 
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL((k_moments<T>), dim3((unsigned)blocks), dim3(256), 0, st, x, sums, ws, rows, row_len, per_row, vec_ok);
     if (!per_row) hipLaunchKernelGGL(k_sum_partials, dim3(2), dim3(256), 0, st, ws, (uint32_t)blocks, 2, sums);
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return launch_status();
 }
 }  // namespace antq
 
@@ -373,12 +328,7 @@ extern "C" int antq_moments(const void *x, size_t rows, size_t row_len, int per_
     if (!x || !sums || (!per_row && !workspace)) return ANTQ_ERR_ARG;
     double *ws = static_cast<double *>(workspace);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-    case ANTQ_F32: return launch_moments<float>(x, sums, ws, rows, row_len, per_row ? 1 : 0, st);
-    case ANTQ_BF16: return launch_moments<bf16_tag>(x, sums, ws, rows, row_len, per_row ? 1 : 0, st);
-    case ANTQ_F16: return launch_moments<f16_tag>(x, sums, ws, rows, row_len, per_row ? 1 : 0, st);
-    default: return ANTQ_ERR_UNSUPPORTED;
-    }
+    return with_dtype(dtype, [&](auto tag) { return launch_moments<decltype(tag)>(x, sums, ws, rows, row_len, per_row ? 1 : 0, st); });
 }
 
 extern "C" int antq_xmax_3sigma(const double *sums, size_t na, size_t n_per, int dtype, float *xmax, void *stream)
@@ -387,13 +337,10 @@ extern "C" int antq_xmax_3sigma(const double *sums, size_t na, size_t n_per, int
     if (!sums || !xmax || n_per == 0) return ANTQ_ERR_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 g((unsigned)((na + 255) / 256)), b(256);
-    switch (dtype) {
-    case ANTQ_F32: hipLaunchKernelGGL((k_xmax_3sigma<float>), g, b, 0, st, sums, na, (double)n_per, xmax); break;
-    case ANTQ_BF16: hipLaunchKernelGGL((k_xmax_3sigma<bf16_tag>), g, b, 0, st, sums, na, (double)n_per, xmax); break;
-    case ANTQ_F16: hipLaunchKernelGGL((k_xmax_3sigma<f16_tag>), g, b, 0, st, sums, na, (double)n_per, xmax); break;
-    default: return ANTQ_ERR_UNSUPPORTED;
-    }
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return with_dtype(dtype, [&](auto tag) {
+        hipLaunchKernelGGL((k_xmax_3sigma<decltype(tag)>), g, b, 0, st, sums, na, (double)n_per, xmax);
+        return launch_status();
+    });
 }
 
 extern "C" int antq_absmax(const void *x, float *amax, size_t rows, size_t row_len, int per_row, int dtype, void *stream)
@@ -401,12 +348,7 @@ extern "C" int antq_absmax(const void *x, float *amax, size_t rows, size_t row_l
     if (rows == 0 || row_len == 0) return ANTQ_OK;
     if (!x || !amax) return ANTQ_ERR_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-    case ANTQ_F32: return launch_absmax<float>(x, amax, rows, row_len, per_row ? 1 : 0, st);
-    case ANTQ_BF16: return launch_absmax<bf16_tag>(x, amax, rows, row_len, per_row ? 1 : 0, st);
-    case ANTQ_F16: return launch_absmax<f16_tag>(x, amax, rows, row_len, per_row ? 1 : 0, st);
-    default: return ANTQ_ERR_UNSUPPORTED;
-    }
+    return with_dtype(dtype, [&](auto tag) { return launch_absmax<decltype(tag)>(x, amax, rows, row_len, per_row ? 1 : 0, st); });
 }
 
 extern "C" int antq_absmax_into(const void *x, float *amax, size_t n, int dtype, void *stream)
@@ -414,12 +356,7 @@ extern "C" int antq_absmax_into(const void *x, float *amax, size_t n, int dtype,
     if (n == 0) return ANTQ_OK;
     if (!x || !amax) return ANTQ_ERR_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-    case ANTQ_F32: return launch_absmax<float>(x, amax, 1, n, 0, st, false);
-    case ANTQ_BF16: return launch_absmax<bf16_tag>(x, amax, 1, n, 0, st, false);
-    case ANTQ_F16: return launch_absmax<f16_tag>(x, amax, 1, n, 0, st, false);
-    default: return ANTQ_ERR_UNSUPPORTED;
-    }
+    return with_dtype(dtype, [&](auto tag) { return launch_absmax<decltype(tag)>(x, amax, 1, n, 0, st, false); });
 }
 
 // ======================================================================================
@@ -448,7 +385,7 @@ static int launch_absmax_t(const void *x, float *amax, size_t n, void *ws, hipSt
     uint32_t group = g_knob_tk_group > 0 ? (uint32_t)g_knob_tk_group : 16u;
     clamp_to_ticket_layout(blocks, group);
     hipLaunchKernelGGL((k_absmax_t<T>), dim3((unsigned)blocks), dim3(256), 0, st, x, amax, n, vec_ok, ws, group);
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return launch_status();
 }
 template <typename T>
 static int launch_alpha_grad_t(const void *x, const void *out, const void *gout, double *gsum, size_t n, void *ws, hipStream_t st)
@@ -464,7 +401,7 @@ static int launch_alpha_grad_t(const void *x, const void *out, const void *gout,
     uint32_t group = g_knob_tk_group > 0 ? (uint32_t)g_knob_tk_group : 32u;
     clamp_to_ticket_layout(blocks, group);
     hipLaunchKernelGGL((k_alpha_grad_t<T>), dim3((unsigned)blocks), dim3(256), 0, st, x, out, gout, gsum, n, vec_ok, ws, group);
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return launch_status();
 }
 }  // namespace antq
 
@@ -473,12 +410,7 @@ extern "C" int antq_absmax_t(const void *x, float *amax, size_t n, int dtype, vo
     if (!x || !amax || !reduce_ws || n == 0) return ANTQ_ERR_ARG;
     if (reinterpret_cast<uintptr_t>(reduce_ws) % 16) return ANTQ_ERR_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-    case ANTQ_F32: return launch_absmax_t<float>(x, amax, n, reduce_ws, st);
-    case ANTQ_BF16: return launch_absmax_t<bf16_tag>(x, amax, n, reduce_ws, st);
-    case ANTQ_F16: return launch_absmax_t<f16_tag>(x, amax, n, reduce_ws, st);
-    default: return ANTQ_ERR_UNSUPPORTED;
-    }
+    return with_dtype(dtype, [&](auto tag) { return launch_absmax_t<decltype(tag)>(x, amax, n, reduce_ws, st); });
 }
 
 extern "C" int antq_alpha_grad_t(const void *x, const void *out, const void *gout, size_t n, double *gsum, int dtype,
@@ -487,12 +419,7 @@ extern "C" int antq_alpha_grad_t(const void *x, const void *out, const void *gou
     if (!x || !out || !gout || !gsum || !reduce_ws || n == 0) return ANTQ_ERR_ARG;
     if (reinterpret_cast<uintptr_t>(reduce_ws) % 16) return ANTQ_ERR_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-    case ANTQ_F32: return launch_alpha_grad_t<float>(x, out, gout, gsum, n, reduce_ws, st);
-    case ANTQ_BF16: return launch_alpha_grad_t<bf16_tag>(x, out, gout, gsum, n, reduce_ws, st);
-    case ANTQ_F16: return launch_alpha_grad_t<f16_tag>(x, out, gout, gsum, n, reduce_ws, st);
-    default: return ANTQ_ERR_UNSUPPORTED;
-    }
+    return with_dtype(dtype, [&](auto tag) { return launch_alpha_grad_t<decltype(tag)>(x, out, gout, gsum, n, reduce_ws, st); });
 }
 
 // ======================================================================================
@@ -515,13 +442,11 @@ extern "C" int antq_fakequant_f64(const double *x, double *out, size_t rows, siz
     if (blocks > 256 * 32) blocks = 256 * 32;
     const size_t lds = lds_table(pa, false);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (flags & ANTQ_FLAG_OVP)
-        hipLaunchKernelGGL((antq::k_fq_f64<true>), dim3((unsigned)blocks), dim3(256), lds, st, x, out, n, row_len, alpha,
+    return with_bool((flags & ANTQ_FLAG_OVP) != 0, [&](auto ovp) {
+        hipLaunchKernelGGL((antq::k_fq_f64<decltype(ovp)::value>), dim3((unsigned)blocks), dim3(256), lds, st, x, out, n, row_len, alpha,
                            alpha_per_row ? 1 : 0, gmax, pa, plan_tab_ptr(plan_dev));
-    else
-        hipLaunchKernelGGL((antq::k_fq_f64<false>), dim3((unsigned)blocks), dim3(256), lds, st, x, out, n, row_len, alpha,
-                           alpha_per_row ? 1 : 0, gmax, pa, plan_tab_ptr(plan_dev));
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+        return launch_status();
+    });
 }
 
 // ======================================================================================
@@ -540,12 +465,9 @@ extern "C" int antq_encode4(const void *x, uint8_t *codes, size_t rows, size_t r
     if (!plan_args_from_host(plan_host, pa)) return ANTQ_ERR_PLAN;
     const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-    case ANTQ_F32: return launch_codec<float>(true, x, codes, nullptr, rows, row_len, alpha, per_row ? 1 : 0, gmax, pa, plan_host, plan_dev, n_normal, ovp, st);
-    case ANTQ_BF16: return launch_codec<bf16_tag>(true, x, codes, nullptr, rows, row_len, alpha, per_row ? 1 : 0, gmax, pa, plan_host, plan_dev, n_normal, ovp, st);
-    case ANTQ_F16: return launch_codec<f16_tag>(true, x, codes, nullptr, rows, row_len, alpha, per_row ? 1 : 0, gmax, pa, plan_host, plan_dev, n_normal, ovp, st);
-    default: return ANTQ_ERR_UNSUPPORTED;
-    }
+    return with_dtype(dtype, [&](auto tag) {
+        return launch_codec<decltype(tag)>(true, x, codes, nullptr, rows, row_len, alpha, per_row ? 1 : 0, gmax, pa, plan_host, plan_dev, n_normal, ovp, st);
+    });
 }
 
 extern "C" int antq_decode4(const uint8_t *codes, void *out, size_t rows, size_t row_len, const float *alpha, int per_row,
@@ -559,12 +481,9 @@ extern "C" int antq_decode4(const uint8_t *codes, void *out, size_t rows, size_t
     if (!plan_args_from_host(plan_host, pa)) return ANTQ_ERR_PLAN;
     const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-    case ANTQ_F32: return launch_codec<float>(false, nullptr, out, codes, rows, row_len, alpha, per_row ? 1 : 0, gmax, pa, plan_host, plan_dev, n_normal, ovp, st);
-    case ANTQ_BF16: return launch_codec<bf16_tag>(false, nullptr, out, codes, rows, row_len, alpha, per_row ? 1 : 0, gmax, pa, plan_host, plan_dev, n_normal, ovp, st);
-    case ANTQ_F16: return launch_codec<f16_tag>(false, nullptr, out, codes, rows, row_len, alpha, per_row ? 1 : 0, gmax, pa, plan_host, plan_dev, n_normal, ovp, st);
-    default: return ANTQ_ERR_UNSUPPORTED;
-    }
+    return with_dtype(dtype, [&](auto tag) {
+        return launch_codec<decltype(tag)>(false, nullptr, out, codes, rows, row_len, alpha, per_row ? 1 : 0, gmax, pa, plan_host, plan_dev, n_normal, ovp, st);
+    });
 }
 
 

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "antq_host.h"
+#include "antq_dispatch.h"
 #include "antq_k_fakequant.h"
 #include "antq_k_search.h"
 #include "antq_k_hist.h"
@@ -99,14 +100,14 @@ static int launch_hist_search(const void *x, size_t n, const float *xmax, const 
         } else {
             float *const xo = (hx && !hx->taken) ? hx->out : nullptr;
             if (hx && xo) hx->taken = true;
-            if (xo)
-                hipLaunchKernelGGL((k_hist16<T, false, true>), dim3(2 * G), dim3(1024), 0, st, static_cast<const uint4 *>(x), nv, G, slabs, hp, xo);
-            else
-                hipLaunchKernelGGL((k_hist16<T, false>), dim3(2 * G), dim3(1024), 0, st, static_cast<const uint4 *>(x), nv, G, slabs, hp, nullptr);
+            with_bool(xo != nullptr, [&](auto xm) {
+                hipLaunchKernelGGL((k_hist16<T, false, decltype(xm)::value>), dim3(2 * G), dim3(1024), 0, st, static_cast<const uint4 *>(x), nv, G, slabs, hp, xo);
+                return (int)ANTQ_OK;
+            });
             hipLaunchKernelGGL((k_hist_reduce<false>), dim3(256), dim3(256), 0, st, slabs, G, count, hp, 0u);
             hipLaunchKernelGGL((k_hist_score<T, false>), dim3(nflat), dim3(1024), lds, st, count, xmax, ratios, ncand, ht, sse, hp);
         }
-        return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+        return launch_status();
     }
 }
 
@@ -241,7 +242,7 @@ static int launch_sweep(const void *x, size_t rows, size_t row_len, const float 
                                static_cast<const uint4 *>(x), (uint32_t)(row_len / EPL), rows, xmax, ratios + c0,
                                sse + ((size_t)t * (size_t)ncand + (size_t)c0) * rows, ty[t], (uint32_t)nc, (uint32_t)nc + 1u);
         }
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return launch_status();
 }
 
 template <typename T>
@@ -306,7 +307,7 @@ static int launch_sweep_pt(const void *x, size_t n, const float *xmax, const flo
         hipLaunchKernelGGL(k_sweep_pt_total, dim3((ncells + 255) / 256, 1), dim3(256), 0, st, part, ngroups, ngroups, ncells, nint, tot);
         hipLaunchKernelGGL(k_sweep_pt_finish, dim3(1), dim3(64), lds, st, tot, xmax, ratios, sse + (size_t)t * ncand, ty[t], (uint32_t)ncand, cp, fbits);
     }
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return launch_status();
 }
 
 
@@ -397,7 +398,7 @@ static int launch_sorted(const void *x, size_t rows, size_t row_len, const float
                 hipLaunchKernelGGL((k_search_sorted_short<T, OVP>), dim3(blocks), dim3(256), lds_of(nc), st, static_cast<const uint4 *>(x),
                                    (uint32_t)(row_len / EPL), rows, xmax, ratios + c0, sse + (size_t)c0 * rows, stt, (uint32_t)nc, (uint32_t)ncand);
             }
-            return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+            return launch_status();
         }
     }
     const int piece = sort_piece(stt, ncand, OVP);
@@ -409,7 +410,7 @@ static int launch_sorted(const void *x, size_t rows, size_t row_len, const float
         hipLaunchKernelGGL((k_search_sorted<T, OVP, false>), dim3(blocks), dim3(kSortNT), L.total, st, static_cast<const uint4 *>(x),
                            row_len / EPL, rows, xmax, ratios + c0, sse + (size_t)c0 * rows, stt, (uint32_t)nc, (uint32_t)ncand, nullptr);
     }
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return launch_status();
 }
 
 template <typename T>
@@ -451,7 +452,68 @@ static int launch_sorted_pt(const void *x, size_t n, const float *xmax, const fl
         hipLaunchKernelGGL(k_sort_pt_total, dim3((ncell + 255) / 256, 1), dim3(256), 0, st, part, ngroups, ngroups, ncell, tot);
         hipLaunchKernelGGL(k_sort_pt_finish, dim3((ntc + 255) / 256), dim3(256), 0, st, tot, ntc, nkg, OVP ? 1 : 0, (uint32_t)nc, (uint32_t)ncand, sse + c0);
     }
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return launch_status();
+}
+
+// ---- the front of a clip search: what runs instead of the direct kernels where it applies -----------------------------
+// Rows with their own scales (rows > 1): the sorted-row search, then the threshold sweep.  ONE scale (rows == 1 -- the
+// caller has folded a tensor without per-row scales into one row): the histogram search (16-bit data), then the sorted
+// search and the sweep over many workgroups.  One codebook (antq_search_sse) or several on one read of the tensor
+// (antq_search_sse_multi: company).
+// company: a codebook's sums must not depend on which other codebooks are searched with it.  When the launch as a whole
+//   is not taken by a path that one search per type would send SOME of these types through, the answer is
+//   ANTQ_ERR_UNSUPPORTED, on which the caller issues one search per type.
+// bound_cap: where the lower bound of the pair rule (hist_outlier_bound) starts before the minimum over the codebooks.
+// Returns the call's result when the search is settled, kSearchGoOn when the direct kernels have to run -- gated by the
+// device flag run_if if the histogram search went in front with the pair rule.
+constexpr int kSearchGoOn = 1;                  // (no ANTQ_* code: those are <= 0)
+template <typename T, bool OVP>
+static int search_front(const void *x, size_t rows, size_t row_len, const float *xmax, const float *ratios, int ncand, int ntypes,
+                         const float *gmax, const void *const *plan_host, const void *const *plan_dev, double *sse, void *ws,
+                         hipStream_t st, HistXmax *hx, bool company, float bound_cap, const int *&run_if)
+{
+    int rc = ANTQ_ERR_UNSUPPORTED;
+    auto some_type = [&](bool (*ok)(const void *, float)) {
+        for (int t = 0; t < ntypes; t++)
+            if (ok(plan_host[t], gmax[t])) return true;
+        return false;
+    };
+    if (rows > 1) {
+        rc = launch_sorted<T, OVP>(x, rows, row_len, xmax, ratios, ncand, ntypes, gmax, plan_host, plan_dev, sse, st);
+        if (rc != ANTQ_ERR_UNSUPPORTED) return rc;
+        if (company && sort_shape_ok<T, OVP>(x, rows, row_len, ncand, 1) && some_type(sort_type_ok)) return ANTQ_ERR_UNSUPPORTED;
+        rc = launch_sweep<T, OVP>(x, rows, row_len, xmax, ratios, ncand, ntypes, gmax, plan_host, plan_dev, sse, st);
+        if (rc != ANTQ_ERR_UNSUPPORTED) return rc;
+        if (company && sweep_shape_ok<T, OVP>(x, rows, row_len, ncand, 1) && some_type(sweep_type_ok)) return ANTQ_ERR_UNSUPPORTED;
+    }
+    if (rows == 1 && hist_eligible<T>(row_len, OVP, x, ntypes * ncand)) {
+        HistTypes ht;
+        memset(&ht, 0, sizeof(ht));
+        ht.ntypes = ntypes;
+        float bound = bound_cap;
+        bool ok = true;
+        for (int t = 0; t < ntypes; t++) {
+            if (!plan_args_from_host(plan_host[t], ht.pa[t])) return ANTQ_ERR_PLAN;
+            ht.plan_tab[t] = plan_tab_ptr(plan_dev[t]);
+            ht.gmax[t] = gmax[t];
+            float b = 0.0f;
+            if (OVP) { ok = ok && hist_outlier_bound(plan_host[t], gmax[t], b); bound = std::min(bound, b); }
+        }
+        if (ok) {
+            rc = launch_hist_search<T>(x, row_len, xmax, ratios, ncand, ht, sse, ws, OVP, bound, &run_if, st, hx);
+            if (rc != ANTQ_OK || !OVP) return rc;
+        }
+    }
+    if (hx && hx->out && !hx->taken) return ANTQ_ERR_LAUNCH;       // (the caller counted on the histogram pass for its statistic)
+    if (rows == 1 && !run_if) {                 // no histogram search in front
+        rc = launch_sorted_pt<T, OVP>(x, row_len, xmax, ratios, ncand, ntypes, gmax, plan_host, plan_dev, sse, ws, st);
+        if (rc != ANTQ_ERR_UNSUPPORTED) return rc;
+        if (company && sort_pt_shape_ok<T>(x, row_len, ncand) && !(OVP && (row_len & 1)) && some_type(sort_type_ok)) return ANTQ_ERR_UNSUPPORTED;
+        rc = launch_sweep_pt<T, OVP>(x, row_len, xmax, ratios, ncand, ntypes, gmax, plan_host, plan_dev, sse, ws, st);
+        if (rc != ANTQ_ERR_UNSUPPORTED) return rc;
+        if (company && sweep_pt_shape_ok<T>(x, row_len, ncand) && !(OVP && g_knob_sweep != 2) && some_type(sweep_type_ok)) return ANTQ_ERR_UNSUPPORTED;
+    }
+    return kSearchGoOn;
 }
 
 template <typename T, bool OVP>
@@ -474,35 +536,15 @@ static int launch_search(const void *x, size_t rows, size_t row_len, const float
                            row_len, xmax, per_row, ratios, ncand, gmax, sse, ws, pa, plan_tab_ptr(plan_dev));
         if (!per_row)
             hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)ncand), dim3(256), 0, st, ws, (uint32_t)blocks, kPtCand, sse);
-        return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
-    }
-    if (per_row && rows > 1) {                   // per-row scales: the sorted-row search, then the threshold sweep, where they apply
-        const void *ph1[1] = {plan_host}, *pd1[1] = {plan_dev};
-        int rc = launch_sorted<T, OVP>(x, rows, row_len, xmax, ratios, ncand, 1, &gmax, ph1, pd1, sse, st);
-        if (rc != ANTQ_ERR_UNSUPPORTED) return rc;
-        rc = launch_sweep<T, OVP>(x, rows, row_len, xmax, ratios, ncand, 1, &gmax, ph1, pd1, sse, st);
-        if (rc != ANTQ_ERR_UNSUPPORTED) return rc;
+        return launch_status();
     }
     if (!per_row) { row_len = rows * row_len; rows = 1; }
     const int *run_if = nullptr;                 // device flag: run the direct kernels only if it is set (pair-list overflow)
-    float bound = 0.0f;
-    if (rows == 1 && hist_eligible<T>(row_len, OVP, x, ncand) && (!OVP || hist_outlier_bound(plan_host, gmax, bound))) {
-        HistTypes ht;
-        memset(&ht, 0, sizeof(ht));
-        ht.ntypes = 1;
-        ht.pa[0] = pa;
-        ht.plan_tab[0] = plan_tab_ptr(plan_dev);
-        ht.gmax[0] = gmax;
-        const int rc = launch_hist_search<T>(x, row_len, xmax, ratios, ncand, ht, sse, ws, OVP, bound, &run_if, st, hx);
-        if (rc != ANTQ_OK || !OVP) return rc;
-    }
-    if (hx && hx->out && !hx->taken) return ANTQ_ERR_LAUNCH;     // (the caller counted on the histogram pass for its statistic)
-    if (rows == 1 && !run_if) {                  // one scale, no histogram search in front: the sorted search / the sweep over many workgroups
+    {
+        // (one codebook has no company; no cap on the pair rule's bound, which nothing reads without the pair rule)
         const void *ph1[1] = {plan_host}, *pd1[1] = {plan_dev};
-        int rc = launch_sorted_pt<T, OVP>(x, row_len, xmax, ratios, ncand, 1, &gmax, ph1, pd1, sse, ws, st);
-        if (rc != ANTQ_ERR_UNSUPPORTED) return rc;
-        rc = launch_sweep_pt<T, OVP>(x, row_len, xmax, ratios, ncand, 1, &gmax, ph1, pd1, sse, ws, st);
-        if (rc != ANTQ_ERR_UNSUPPORTED) return rc;
+        const int rc = search_front<T, OVP>(x, rows, row_len, xmax, ratios, ncand, 1, &gmax, ph1, pd1, sse, ws, st, hx, false, OVP ? INFINITY : 0.0f, run_if);
+        if (rc != kSearchGoOn) return rc;
     }
     const size_t vpr = row_len / EPL;
     if (vpr > 0xffffffffull) return ANTQ_ERR_UNSUPPORTED;
@@ -526,24 +568,30 @@ static int launch_search(const void *x, size_t rows, size_t row_len, const float
     const XArgs xa = xargs_from_plan(plan_host, pa);
     const uint4 *xv = static_cast<const uint4 *>(x);
     SearchGrid sg{0, 0, 0};
-#define ANTQ_LAUNCH_S(PT_, XD_, U_)                                                                                \
-    do {                                                                                                           \
-        const int resident_ = resident_workgroups(k_search_sse<T, OVP, U_, PT_, XD_>, (XD_) ? 0 : lds);            \
-        sg = search_grid(PT_ ? total : rows, PT_ ? 1 : tpr, PT_, ncand, resident_);                                \
-        if (sg.chunks == 0) return ANTQ_ERR_UNSUPPORTED;                                                           \
-        hipLaunchKernelGGL((k_search_sse<T, OVP, U_, PT_, XD_>), dim3((unsigned)sg.blocks, (unsigned)sg.chunks), dim3(256), \
-                           (XD_) ? 0 : lds, st, xv, (uint32_t)total, (uint32_t)vpr, (uint32_t)tpr, rows, xmax, per_row,  \
-                           ratios, ncand, gmax, sse, ws, pa, plan_tab_ptr(plan_dev), sg.chunk, xa, run_if);         \
-    } while (0)
-#define ANTQ_LAUNCH_SU(PT_, XD_) do { if (U == 8) ANTQ_LAUNCH_S(PT_, XD_, 8); else ANTQ_LAUNCH_S(PT_, XD_, 4); } while (0)
-    if (pt) { if (xd) ANTQ_LAUNCH_SU(true, true); else ANTQ_LAUNCH_SU(true, false); }
-    else if (U == 2) { if (xd) ANTQ_LAUNCH_S(false, true, 2); else ANTQ_LAUNCH_S(false, false, 2); }
-    else if (U == 1) ANTQ_LAUNCH_S(false, false, 1);
-    else    { if (xd) ANTQ_LAUNCH_SU(false, true); else ANTQ_LAUNCH_SU(false, false); }
-#undef ANTQ_LAUNCH_SU
-#undef ANTQ_LAUNCH_S
+    // the kernels: one scale -- 8 or 4 vectors per lane; rows -- 8 / 4, 2 and, without the x-domain table, 1
+    // (U is one of 8 / 4 / 2 / 1 by the lines above: there is no other value to fall through from)
+    const int rc = with_bool(pt, [&](auto pt_) {
+        return with_bool(xd, [&](auto xd_) {
+            return with_value<8, 4, 2, 1>(U, [&](auto u_) {
+                constexpr bool PT = decltype(pt_)::value, XD = decltype(xd_)::value;
+                constexpr int UU = decltype(u_)::value;
+                if constexpr ((PT && UU < 4) || (XD && UU == 1)) {
+                    return (int)ANTQ_ERR_UNSUPPORTED;           // (no such kernels; unreachable: pt leaves U at 8 / 4, xd requires pt or U != 1)
+                } else {
+                    const size_t dlds = XD ? 0 : lds;
+                    sg = search_grid(PT ? total : rows, PT ? 1 : tpr, PT, ncand, resident_workgroups(k_search_sse<T, OVP, UU, PT, XD>, dlds));
+                    if (sg.chunks == 0) return (int)ANTQ_ERR_UNSUPPORTED;
+                    hipLaunchKernelGGL((k_search_sse<T, OVP, UU, PT, XD>), dim3((unsigned)sg.blocks, (unsigned)sg.chunks), dim3(256), dlds, st,
+                                       xv, (uint32_t)total, (uint32_t)vpr, (uint32_t)tpr, rows, xmax, per_row, ratios, ncand, gmax, sse, ws, pa,
+                                       plan_tab_ptr(plan_dev), sg.chunk, xa, run_if);
+                    return (int)ANTQ_OK;
+                }
+            });
+        });
+    });
+    if (rc != ANTQ_OK) return rc;
     if (pt) hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)ncand), dim3(256), 0, st, ws, (uint32_t)sg.blocks, sg.chunk, sse, run_if);
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return launch_status();
 }
 
 // all candidate types of a type selection on one read of the tensor; every plan must have the x-domain path
@@ -554,56 +602,12 @@ static int launch_search_multi(const void *x, size_t rows, size_t row_len, const
 {
     constexpr int EPL = IO<T>::EPL;
     if (reinterpret_cast<uintptr_t>(x) % 16 != 0 || (per_row ? row_len : rows * row_len) % EPL != 0) return ANTQ_ERR_UNSUPPORTED;
-    if (per_row && rows > 1) {                   // per-row scales: the sorted-row search, then the threshold sweep, where they apply
-        int rc = launch_sorted<T, OVP>(x, rows, row_len, xmax, ratios, ncand, ntypes, gmax, plan_host, plan_dev, sse, st);
-        if (rc != ANTQ_ERR_UNSUPPORTED) return rc;
-        // (a codebook's sums must not depend on its company: one search per type if some of them would take the sorted search)
-        if (sort_shape_ok<T, OVP>(x, rows, row_len, ncand, 1))
-            for (int t = 0; t < ntypes; t++)
-                if (sort_type_ok(plan_host[t], gmax[t])) return ANTQ_ERR_UNSUPPORTED;
-        rc = launch_sweep<T, OVP>(x, rows, row_len, xmax, ratios, ncand, ntypes, gmax, plan_host, plan_dev, sse, st);
-        if (rc != ANTQ_ERR_UNSUPPORTED) return rc;
-        // a codebook's sums must not depend on which other codebooks are searched with it: if one search per type would send
-        // SOME of these types through the sweep, the caller has to issue one search per type (it does on this return code)
-        if (sweep_shape_ok<T, OVP>(x, rows, row_len, ncand, 1))
-            for (int t = 0; t < ntypes; t++)
-                if (sweep_type_ok(plan_host[t], gmax[t])) return ANTQ_ERR_UNSUPPORTED;
-    }
     if (!per_row) { row_len = rows * row_len; rows = 1; }
     const int *run_if = nullptr;
-    if (rows == 1 && hist_eligible<T>(row_len, OVP, x, ntypes * ncand)) {
-        HistTypes ht;
-        memset(&ht, 0, sizeof(ht));
-        ht.ntypes = ntypes;
-        float bound = 3.0e38f;
-        bool ok = true;
-        for (int t = 0; t < ntypes; t++) {
-            PlanArgs pa;
-            if (!plan_args_from_host(plan_host[t], pa)) return ANTQ_ERR_PLAN;
-            ht.pa[t] = pa;
-            ht.plan_tab[t] = plan_tab_ptr(plan_dev[t]);
-            ht.gmax[t] = gmax[t];
-            float b = 0.0f;
-            if (OVP) { ok = ok && hist_outlier_bound(plan_host[t], gmax[t], b); bound = std::min(bound, b); }
-        }
-        if (ok) {
-            const int rc = launch_hist_search<T>(x, row_len, xmax, ratios, ncand, ht, sse, ws, OVP, bound, &run_if, st, hx);
-            if (rc != ANTQ_OK || !OVP) return rc;
-        }
-    }
-    if (hx && hx->out && !hx->taken) return ANTQ_ERR_LAUNCH;     // (see launch_search)
-    if (rows == 1 && !run_if) {
-        int rc = launch_sorted_pt<T, OVP>(x, row_len, xmax, ratios, ncand, ntypes, gmax, plan_host, plan_dev, sse, ws, st);
-        if (rc != ANTQ_ERR_UNSUPPORTED) return rc;
-        if (sort_pt_shape_ok<T>(x, row_len, ncand) && !(OVP && (row_len & 1)))
-            for (int t = 0; t < ntypes; t++)
-                if (sort_type_ok(plan_host[t], gmax[t])) return ANTQ_ERR_UNSUPPORTED;
-        rc = launch_sweep_pt<T, OVP>(x, row_len, xmax, ratios, ncand, ntypes, gmax, plan_host, plan_dev, sse, ws, st);
-        if (rc != ANTQ_ERR_UNSUPPORTED) return rc;
-        // (as for rows: a codebook's sums must not depend on its company -- one search per type if some types would sweep)
-        if (sweep_pt_shape_ok<T>(x, row_len, ncand) && !(OVP && g_knob_sweep != 2))
-            for (int t = 0; t < ntypes; t++)
-                if (sweep_type_ok(plan_host[t], gmax[t])) return ANTQ_ERR_UNSUPPORTED;
+    {
+        // (a codebook's sums must not depend on its company; the bound of the pair rule is capped as it always was here)
+        const int rc = search_front<T, OVP>(x, rows, row_len, xmax, ratios, ncand, ntypes, gmax, plan_host, plan_dev, sse, ws, st, hx, true, 3.0e38f, run_if);
+        if (rc != kSearchGoOn) return rc;
     }
     const size_t vpr = row_len / EPL;
     if (vpr < kSearchMinVpr || vpr > 0xffffffffull) return ANTQ_ERR_UNSUPPORTED;
@@ -631,22 +635,25 @@ static int launch_search_multi(const void *x, size_t rows, size_t row_len, const
     const int nflat = ntypes * ncand;
     const uint4 *xv = static_cast<const uint4 *>(x);
     SearchGrid sg{0, 0, 0};
-#define ANTQ_LAUNCH_M(PT_, U_)                                                                                            \
-    do {                                                                                                                  \
-        const int resident_ = resident_workgroups(k_search_sse_multi<T, OVP, U_, PT_>, 0);                                \
-        sg = search_grid(PT_ ? total : rows, PT_ ? 1 : tpr, PT_, nflat, resident_);                                       \
-        if (sg.chunks == 0) return ANTQ_ERR_UNSUPPORTED;                                                                  \
-        hipLaunchKernelGGL((k_search_sse_multi<T, OVP, U_, PT_>), dim3((unsigned)sg.blocks, (unsigned)sg.chunks), dim3(256), 0, st, \
-                           xv, (uint32_t)total, (uint32_t)vpr, (uint32_t)tpr, rows, xmax, per_row, ratios, ncand, sse, ws, ma, sg.chunk, run_if); \
-    } while (0)
-    if (pt) {
-        if (U == 8) ANTQ_LAUNCH_M(true, 8); else ANTQ_LAUNCH_M(true, 4);
-        hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)nflat), dim3(256), 0, st, ws, (uint32_t)sg.blocks, sg.chunk, sse, run_if);
-    } else {
-        if (U == 8) ANTQ_LAUNCH_M(false, 8); else if (U == 2) ANTQ_LAUNCH_M(false, 2); else ANTQ_LAUNCH_M(false, 4);
-    }
-#undef ANTQ_LAUNCH_M
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    // the kernels: one scale -- 8 or 4 vectors per lane; rows -- 8, 2, or 4
+    const int rc = with_bool(pt, [&](auto pt_) {
+        return with_value<8, 2, 4>(one_of<8, 2>(U, 4), [&](auto u_) {
+            constexpr bool PT = decltype(pt_)::value;
+            constexpr int UU = decltype(u_)::value;
+            if constexpr (PT && UU == 2) {
+                return (int)ANTQ_ERR_UNSUPPORTED;               // (no such kernel; unreachable: only !pt sets U = 2 above)
+            } else {
+                sg = search_grid(PT ? total : rows, PT ? 1 : tpr, PT, nflat, resident_workgroups(k_search_sse_multi<T, OVP, UU, PT>, 0));
+                if (sg.chunks == 0) return (int)ANTQ_ERR_UNSUPPORTED;
+                hipLaunchKernelGGL((k_search_sse_multi<T, OVP, UU, PT>), dim3((unsigned)sg.blocks, (unsigned)sg.chunks), dim3(256), 0, st, xv,
+                                   (uint32_t)total, (uint32_t)vpr, (uint32_t)tpr, rows, xmax, per_row, ratios, ncand, sse, ws, ma, sg.chunk, run_if);
+                return (int)ANTQ_OK;
+            }
+        });
+    });
+    if (rc != ANTQ_OK) return rc;
+    if (pt) hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)nflat), dim3(256), 0, st, ws, (uint32_t)sg.blocks, sg.chunk, sse, run_if);
+    return launch_status();
 }
 
 }  // namespace antq
@@ -666,18 +673,12 @@ static int search_sse_multi_impl(const void *x, size_t rows, size_t row_len, con
     for (int t = 0; t < ntypes; t++)
         if (!plan_host[t] || !plan_dev[t]) return ANTQ_ERR_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
-    const int pr = per_row ? 1 : 0;
-#define ANTQ_SM(TT)                                                                                                     \
-    (ovp ? launch_search_multi<TT, true>(x, rows, row_len, xmax, pr, ratios, ncand, ntypes, gmax_host, plan_host, plan_dev, sse, ws, st, hx)   \
-         : launch_search_multi<TT, false>(x, rows, row_len, xmax, pr, ratios, ncand, ntypes, gmax_host, plan_host, plan_dev, sse, ws, st, hx))
-    switch (dtype) {
-    case ANTQ_F32: return ANTQ_SM(float);
-    case ANTQ_BF16: return ANTQ_SM(bf16_tag);
-    case ANTQ_F16: return ANTQ_SM(f16_tag);
-    default: return ANTQ_ERR_UNSUPPORTED;
-    }
-#undef ANTQ_SM
+    return with_dtype(dtype, [&](auto tag) {
+        return with_bool((flags & ANTQ_FLAG_OVP) != 0, [&](auto ovp) {
+            return launch_search_multi<decltype(tag), decltype(ovp)::value>(x, rows, row_len, xmax, per_row ? 1 : 0, ratios, ncand, ntypes, gmax_host,
+                                                                            plan_host, plan_dev, sse, ws, st, hx);
+        });
+    });
 }
 
 extern "C" int antq_search_sse_multi(const void *x, size_t rows, size_t row_len, const float *xmax, int per_row,
@@ -700,21 +701,12 @@ static int search_sse_impl(const void *x, size_t rows, size_t row_len, const flo
     PlanArgs pa;
     if (!plan_args_from_host(plan_host, pa)) return ANTQ_ERR_PLAN;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
-    const int pr = per_row ? 1 : 0;
-    switch (dtype) {
-    case ANTQ_F32:
-        return ovp ? launch_search<float, true>(x, rows, row_len, xmax, pr, ratios, ncand, gmax, pa, plan_host, plan_dev, sse, ws, st, hx)
-                   : launch_search<float, false>(x, rows, row_len, xmax, pr, ratios, ncand, gmax, pa, plan_host, plan_dev, sse, ws, st, hx);
-    case ANTQ_BF16:
-        return ovp ? launch_search<bf16_tag, true>(x, rows, row_len, xmax, pr, ratios, ncand, gmax, pa, plan_host, plan_dev, sse, ws, st, hx)
-                   : launch_search<bf16_tag, false>(x, rows, row_len, xmax, pr, ratios, ncand, gmax, pa, plan_host, plan_dev, sse, ws, st, hx);
-    case ANTQ_F16:
-        return ovp ? launch_search<f16_tag, true>(x, rows, row_len, xmax, pr, ratios, ncand, gmax, pa, plan_host, plan_dev, sse, ws, st, hx)
-                   : launch_search<f16_tag, false>(x, rows, row_len, xmax, pr, ratios, ncand, gmax, pa, plan_host, plan_dev, sse, ws, st, hx);
-    default:
-        return ANTQ_ERR_UNSUPPORTED;
-    }
+    return with_dtype(dtype, [&](auto tag) {
+        return with_bool((flags & ANTQ_FLAG_OVP) != 0, [&](auto ovp) {
+            return launch_search<decltype(tag), decltype(ovp)::value>(x, rows, row_len, xmax, per_row ? 1 : 0, ratios, ncand, gmax, pa, plan_host,
+                                                                      plan_dev, sse, ws, st, hx);
+        });
+    });
 }
 
 extern "C" int antq_search_sse(const void *x, size_t rows, size_t row_len, const float *xmax, int per_row,
@@ -736,7 +728,7 @@ extern "C" int antq_search_pick(const double *sse, const float *xmax, const floa
     if (blocks > 0x7fffffffull) return ANTQ_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(antq::k_search_pick, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), sse, xmax,
                        ratios, ncand, na, (double)row_len, best_score, best_alpha);
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return launch_status();
 }
 
 
@@ -802,7 +794,7 @@ extern "C" int antq_calibrate(const void *x, size_t rows, size_t row_len, int al
     bool xmax_in_hist = false;
     if (na == 1 && xmax_mode == ANTQ_XMAX_ABSMAX && !(flags & ANTQ_FLAG_OVP) && ncand > 0 && g_knob_hist_xmax)
         xmax_in_hist = dtype == ANTQ_BF16 ? hist_eligible<bf16_tag>(n_per, false, x, 0)
-                     : dtype == ANTQ_F16  ? hist_eligible<f16_tag>(n_per, false, x, 0) : false;
+                     : dtype == ANTQ_F16  ? hist_eligible<f16_tag>(n_per, false, x, 0) : false;      // (a bool, not a status: no with_dtype)
     HistXmax hx;                                   // (decided here, once; handed to the search explicitly)
     float *const zero = (xmax_mode == ANTQ_XMAX_ABSMAX && ncand > 0 && (!pr || xmax_in_hist)) ? xmax : nullptr;
     if (ncand > 0)
@@ -842,7 +834,7 @@ extern "C" int antq_calibrate(const void *x, size_t rows, size_t row_len, int al
             // 3 + 4 for a tensor with one scale: picks, scores and the type pick in one launch
             hipLaunchKernelGGL(k_calib_pick_one_scale, dim3(1), dim3(256), 0, st, sse, xmax, ratios, ncand, (double)n_per, ntypes, best,
                                alpha, score, type);
-            return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+            return launch_status();
         }
         // 3. per row: the first strict minimum (AQ:299-306), every type in one launch (blockIdx.y)
         const size_t pblocks = (na + 3) / 4;
@@ -852,7 +844,7 @@ extern "C" int antq_calibrate(const void *x, size_t rows, size_t row_len, int al
     }
     // 4. per tensor: the type with the smallest sum of best MSEs (AQ:326, :413-415)
     hipLaunchKernelGGL(k_calib_type_score_pick, dim3(1), dim3(256), 0, st, best, na, ntypes, score, type);
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return launch_status();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -922,11 +914,10 @@ static int launch_install_forward(const void *x, void *out, size_t n, unsigned f
     constexpr int EPL = IO<T>::EPL;
     const size_t nv = n / EPL;
     const unsigned blocks = (unsigned)std::min<size_t>((nv + 255) / 256, 256 * 16);
-    if (flags & ANTQ_FLAG_OVP)
-        hipLaunchKernelGGL((k_fq_select<T, true>), dim3(blocks), dim3(256), lds, st, static_cast<const uint4 *>(x), static_cast<uint4 *>(out), nv, type, alpha, sp);
-    else
-        hipLaunchKernelGGL((k_fq_select<T, false>), dim3(blocks), dim3(256), lds, st, static_cast<const uint4 *>(x), static_cast<uint4 *>(out), nv, type, alpha, sp);
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return with_bool((flags & ANTQ_FLAG_OVP) != 0, [&](auto ovp) {
+        hipLaunchKernelGGL((k_fq_select<T, decltype(ovp)::value>), dim3(blocks), dim3(256), lds, st, static_cast<const uint4 *>(x), static_cast<uint4 *>(out), nv, type, alpha, sp);
+        return launch_status();
+    });
 }
 }  // namespace antq
 
@@ -959,11 +950,7 @@ extern "C" int antq_calibrate_install(const void *x, void *out, size_t n, int dt
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_calib_install, dim3(1), dim3(256), 0, st, type, ntypes, alpha, score, grids, grid_len, grid_out, outl, outl_len,
                        outl_out, alpha_out, mse_out);
-    switch (dtype) {
-    case ANTQ_F32: return launch_install_forward<float>(x, out, n, flags, type, alpha, sp, lds, st);
-    case ANTQ_BF16: return launch_install_forward<bf16_tag>(x, out, n, flags, type, alpha, sp, lds, st);
-    default: return launch_install_forward<f16_tag>(x, out, n, flags, type, alpha, sp, lds, st);
-    }
+    return with_dtype(dtype, [&](auto tag) { return launch_install_forward<decltype(tag)>(x, out, n, flags, type, alpha, sp, lds, st); });   // (any other dtype was refused above)
 }
 
 extern "C" size_t antq_calibrate_batch_workspace_bytes(const antq_calib_job *jobs, int n)
