@@ -26,9 +26,9 @@
 //            the buffer without a workgroup barrier; address = i + (i >> 4): every layout nearly conflict-free).  The
 //            first step of a merge (partner i ^ (2^s - 1)) is folded into the transposing READ (the upper half block is read
 //            mirrored), so every comparator sorts ascending: v_min_u32 + v_max_u32 per pair.
-//   sums     x in fixed point (2^-38 of the row statistic's binade, exact for every element within 2^15 of it: antq_k_sweep.h),
-//            prefix sums as 64-bit integers at every second sorted position (every fourth with the pair rule: sort_psh); a
-//            probe adds the one (three) elements in between
+//   sums     x in fixed point (2^-38 of the row statistic's binade, exact for every element within 2^15 of it: clip_fixed),
+//            prefix sums as 64-bit integers at every second sorted position, with and without the pair rule; a probe adds
+//            the one element in between
 //   search   work item = (codebook, candidate, group of 4 thresholds): 4 interleaved binary searches, the closed form's
 //            terms in double in ONE fixed order -- the sums of a (codebook, candidate) do not depend on which other codebooks
 //            or candidates share the launch
@@ -47,9 +47,9 @@
 #include <type_traits>
 
 #include "antq_device.h"
+#include "antq_k_cliptype.h"
 #include "antq_k_fakequant.h"
 #include "antq_k_search.h"
-#include "antq_k_sweep.h"
 
 namespace antq {
 
@@ -63,22 +63,45 @@ constexpr uint32_t kSortSent = 0xffffffffu;
 // group) items, kSortNC pair-correction items and kSortNL (type, candidate) literal sums per thread -- the launcher cuts the
 // candidate list into pieces that fit.
 constexpr int kSortNI = 6, kSortNC = 3, kSortNL = 2;
-constexpr uint32_t kSortTy = 332;                            // dwords of a type's block in LDS: values [66], thresholds T [64], scalars [130..139]
-                                                             // (n_thr, kout_pos, kout_neg, gmax, lim, m, nneg, even-mantissa masks [137..138]),
-                                                             // rounding boundaries M_k as doubles [140..267], the codebook in scan order
-                                                             // [268..331] (literal elements; codebooks of more than 64 values: from memory)
 constexpr uint32_t kSortGridLds = 64;
-// Prefix sums at every 2^PSH-th sorted position.  A probe converts the (up to 2^PSH - 1) keys between the stored position and
-// its own back to fixed point -- 10 instructions each, a quarter of a look-up at every fourth -- so every SECOND position is
-// kept (8 KB more LDS than every fourth).  With the pair rule that only fits next to three workgroups per CU because OliVe's
-// launches do not keep their 20 KB table of x-domain thresholds (sort_inline): a (codebook, candidate, threshold) is moved
-// into the x domain by the item that probes it -- once per chunk instead of once per row, which a row of several chunks
-// pays back through the cheaper probes -- and the pair rule's own look-ups work in the grid domain (RN(x / s) >= T_k <=> x >= X_k).
-__host__ __device__ constexpr int sort_psh(bool ovp) { (void)ovp; return 1; }
+// A type's block in LDS, in dwords: what sort_fill_type writes and SortTypeView reads
+constexpr uint32_t kTyValue = 0;                             // [66] values: [0] below the first threshold, [k + 1] at and above threshold k
+constexpr uint32_t kTyThr = 66;                              // [64] thresholds T in the grid domain
+constexpr uint32_t kTyNthr = 130, kTyKpos = 131, kTyKneg = 132, kTyGmax = 133, kTyLim = 134, kTyM = 135, kTyNneg = 136;   // scalars
+constexpr uint32_t kTyEven = 137;                            // [2] even-mantissa masks of the thresholds ([139]: unused, aligns what follows)
+constexpr uint32_t kTyBoundary = 140;                        // [64] rounding boundaries M_k as doubles
+constexpr uint32_t kTyGrid = 268;                            // [64] the codebook in scan order (literal elements; codebooks of more
+                                                             // than kSortGridLds values: from memory)
+constexpr uint32_t kSortTy = kTyGrid + kSortGridLds;         // dwords of a type's block
+static_assert(kTyThr == kTyValue + 66 && kTyNthr == kTyThr + 64 && kTyBoundary % 2 == 0 && kTyBoundary >= kTyEven + 2 &&
+              kTyGrid == kTyBoundary + 2 * 64 && kSortTy == 332, "a type's LDS block");
+struct SortTypeView {
+    float *v;
+    __device__ __forceinline__ const uint32_t *u() const { return reinterpret_cast<const uint32_t *>(v); }
+    __device__ __forceinline__ uint32_t nthr() const { return u()[kTyNthr]; }
+    __device__ __forceinline__ int kpos() const { return (int)u()[kTyKpos]; }
+    __device__ __forceinline__ int kneg() const { return (int)u()[kTyKneg]; }
+    __device__ __forceinline__ float gmax() const { return v[kTyGmax]; }
+    __device__ __forceinline__ float lim() const { return v[kTyLim]; }
+    __device__ __forceinline__ int m() const { return (int)u()[kTyM]; }
+    __device__ __forceinline__ uint32_t nneg() const { return u()[kTyNneg]; }
+    __device__ __forceinline__ float value(uint32_t i) const { return v[kTyValue + i]; }
+    __device__ __forceinline__ float thr(uint32_t i) const { return v[kTyThr + i]; }
+    __device__ __forceinline__ double boundary(uint32_t i) const { return reinterpret_cast<const double *>(v + kTyBoundary)[i]; }
+    __device__ __forceinline__ bool thr_even(uint32_t i) const { return ((u()[kTyEven + (i >> 5)] >> (i & 31u)) & 1u) != 0u; }
+    __device__ __forceinline__ float grid(uint32_t i) const { return v[kTyGrid + i]; }
+};
+// Prefix sums at every second sorted position.  A probe converts the key between the stored position and its own back to
+// fixed point -- 10 instructions, against three keys and a quarter of a look-up at every fourth (8 KB less LDS).  With the
+// pair rule that only fits next to three workgroups per CU because OliVe's launches do not keep their 20 KB table of
+// x-domain thresholds (sort_inline): a (codebook, candidate, threshold) is moved into the x domain by the item that probes
+// it -- once per chunk instead of once per row, which a row of several chunks pays back through the cheaper probes -- and
+// the pair rule's own look-ups work in the grid domain (RN(x / s) >= T_k <=> x >= X_k).
+constexpr int kSortPsh = 1;
 __host__ __device__ constexpr bool sort_inline(bool ovp) { return ovp; }
 
 struct SortTypes {
-    SweepType ty[kMaxTypes];
+    ClipType ty[kMaxTypes];
     uint32_t nneg[kMaxTypes];    // thresholds below zero (PlanHeader::h_nneg): the closed form is written around the cell that holds 0
     int ntypes;
     uint32_t nthr_pad;           // max n_thr over the types, rounded up to a multiple of kSortKS
@@ -93,12 +116,12 @@ __host__ __device__ inline SortLds sort_lds(uint32_t ntc, uint32_t nthr_pad, int
     SortLds L;
     uint32_t o = (uint32_t)kSortPad * 4u;                    // keys
     o = (o + 15u) & ~15u;
-    L.off_p4 = o;    o += (((uint32_t)kSortK >> sort_psh(ovp)) + 1u) * 8u;      // prefix sums, and the total
+    L.off_p4 = o;    o += (((uint32_t)kSortK >> kSortPsh) + 1u) * 8u;      // prefix sums, and the total
     o = (o + 15u) & ~15u;
     L.off_x = o;     o += sort_inline(ovp) ? ntc * 2u * 4u : ntc * nthr_pad * 4u;     // thresholds as keys (inline: the two outlier bounds only)
     L.off_s = o;     o += ntc * 4u;
     o = (o + 15u) & ~15u;
-    L.off_v = o;     o += (uint32_t)ntypes * kSortTy * 4u;   // per type: values [66], thresholds T [64], n_thr, kout_pos, kout_neg, gmax, lim, m
+    L.off_v = o;     o += (uint32_t)ntypes * kSortTy * 4u;   // per type: a block of kSortTy dwords
     o = (o + 15u) & ~15u;
     L.off_misc = o;  o += 256u;                              // scan scratch, counters
     L.total = o;
@@ -114,7 +137,7 @@ __device__ __forceinline__ uint32_t sort_key(float x)        // order of the uns
 __device__ __forceinline__ float sort_unkey(uint32_t k) { return u2f((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 __device__ __forceinline__ long long sort_key_fixed(uint32_t k, double F)
 {
-    return k == kSortSent ? 0ll : sweep_fixed(sort_unkey(k), F);
+    return k == kSortSent ? 0ll : clip_fixed(sort_unkey(k), F);
 }
 
 // x_threshold (antq_k_fakequant.h) with the rounding boundary M = (pred(T) + T) / 2 and T's mantissa parity precomputed per
@@ -128,59 +151,150 @@ __device__ __forceinline__ float sort_x_threshold(double M, bool t_even, double 
     return take ? xf : f_up(xf);
 }
 // a type's block: what every thread of a workgroup fills once (tid < 64: one threshold each; tid == 64: the scalars)
-__device__ __forceinline__ void sort_fill_type(float *v, const SweepType &ty, uint32_t nneg, uint32_t tid)
+__device__ __forceinline__ void sort_fill_type(SortTypeView V, const ClipType &ty, uint32_t nneg, uint32_t tid)
 {
+    float *v = V.v;
     uint32_t *vu = reinterpret_cast<uint32_t *>(v);
-    double *vm = reinterpret_cast<double *>(v + 140);
+    double *vm = reinterpret_cast<double *>(v + kTyBoundary);
     if (tid < 64u) {
         const uint32_t k = tid;
         float T = 0.0f;
         if (k < ty.n_thr) {
             const uint4 th = ty.tlist[k];
             T = u2f(th.x);
-            v[k + 1u] = u2f(th.z) + 0.0f;
-            if (k == 0u) v[0] = u2f(th.y) + 0.0f;
+            v[kTyValue + k + 1u] = u2f(th.z) + 0.0f;
+            if (k == 0u) v[kTyValue] = u2f(th.y) + 0.0f;
         } else {                                         // beyond the last threshold: the last value again (A = B = 0)
-            v[k + 1u] = ty.n_thr ? u2f(ty.tlist[ty.n_thr - 1u].z) + 0.0f : 0.0f;
+            v[kTyValue + k + 1u] = ty.n_thr ? u2f(ty.tlist[ty.n_thr - 1u].z) + 0.0f : 0.0f;
         }
-        v[66u + k] = T;
+        v[kTyThr + k] = T;
         vm[k] = 0.5 * ((double)f_dn(T) + (double)T);
-        v[268u + k] = k < ty.m ? ty.grid[k] : 0.0f;
+        v[kTyGrid + k] = k < ty.m ? ty.grid[k] : 0.0f;
         const unsigned long long ev = __ballot((f2u(T) & 1u) == 0u);
-        if (k == 0u) { vu[137] = (uint32_t)ev; vu[138] = (uint32_t)(ev >> 32); }
+        if (k == 0u) { vu[kTyEven] = (uint32_t)ev; vu[kTyEven + 1u] = (uint32_t)(ev >> 32); }
     }
     if (tid == 64u) {
-        vu[130] = ty.n_thr;
-        vu[131] = (uint32_t)ty.kout_pos;
-        vu[132] = (uint32_t)ty.kout_neg;
-        v[133] = ty.gmax;
-        v[134] = ty.lim;
-        vu[135] = ty.m;
-        vu[136] = nneg < ty.n_thr ? nneg : ty.n_thr;
+        vu[kTyNthr] = ty.n_thr;
+        vu[kTyKpos] = (uint32_t)ty.kout_pos;
+        vu[kTyKneg] = (uint32_t)ty.kout_neg;
+        v[kTyGmax] = ty.gmax;
+        v[kTyLim] = ty.lim;
+        vu[kTyM] = ty.m;
+        vu[kTyNneg] = nneg < ty.n_thr ? nneg : ty.n_thr;
     }
 }
-__device__ __forceinline__ uint32_t sort_threshold_key(const float *v, uint32_t k, double sd)
+__device__ __forceinline__ uint32_t sort_threshold_key(SortTypeView V, uint32_t k, double sd)
 {
-    const uint32_t *vu = reinterpret_cast<const uint32_t *>(v);
-    const double M = reinterpret_cast<const double *>(v + 140)[k];
-    const bool even = ((vu[137u + (k >> 5)] >> (k & 31u)) & 1u) != 0u;
-    return sort_key(sort_x_threshold(M, even, sd));
+    return sort_key(sort_x_threshold(V.boundary(k), V.thr_even(k), sd));
+}
+
+// (type, candidate) of a flat index without an integer division (~20 instructions each on this machine; two of them per
+// threshold were a tenth of the kernel): at most kMaxTypes = 4 types
+__device__ __forceinline__ uint32_t sort_type_of(uint32_t tc, uint32_t ncand)
+{
+    return (tc >= ncand ? 1u : 0u) + (tc >= 2u * ncand ? 1u : 0u) + (tc >= 3u * ncand ? 1u : 0u);
+}
+
+// the codebook of type t in memory (constant indices into the kernel argument)
+__device__ __forceinline__ const float *sort_type_grid(const SortTypes &st, uint32_t t)
+{
+    const float *g = st.ty[0].grid;
+#pragma unroll
+    for (int u = 1; u < kMaxTypes; u++) g = (uint32_t)u == t ? st.ty[u].grid : g;
+    return g;
+}
+
+// inclusive scan over the lanes of a wavefront
+template <typename V>
+__device__ __forceinline__ V wave_scan_incl(V v, uint32_t lane)
+{
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const V tv = __shfl_up(v, off, 64);
+        if (lane >= (uint32_t)off) v += tv;
+    }
+    return v;
+}
+
+// The cell an element falls in, J = #{k < n : x >= X_k}, by bisection: over the x-domain thresholds as keys, or -- where a
+// launch does not keep those (sort_inline) -- over the grid-domain thresholds: RN(x / s) >= T_k <=> x >= X_k
+__device__ __forceinline__ uint32_t sort_cell_of_key(const uint32_t *X, uint32_t n, uint32_t kx)
+{
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (kx >= X[mid]) lo = mid + 1u; else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ uint32_t sort_cell_of_d(SortTypeView V, uint32_t n, float d)
+{
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (d >= V.thr(mid)) lo = mid + 1u; else hi = mid;
+    }
+    return lo;
 }
 
 // the reference scan (quant_kernel.cu:25-37) for a literal element: the codebook from LDS where it fits (a scan that waits for
 // a load from memory per value took 2000 cycles per element and candidate: 5 ms for a 64 x 1024 tensor with one Inf row)
-__device__ __forceinline__ float sort_literal_q(float xv, float s, const float *v, const float *grid, int m, float &d)
+__device__ __forceinline__ float sort_literal_q(float xv, float s, SortTypeView V, const float *grid, int m, float &d)
 {
-    if (m > (int)kSortGridLds) return sweep_literal_q(xv, s, grid, m, d);
+    if (m > (int)kSortGridLds) return clip_literal_q(xv, s, grid, m, d);
     d = xv / s;
     float sub_min = 102400.0f, z_min = 0.0f;
 #pragma unroll 4
     for (int i = 0; i < m; i++) {
-        const float g = v[268 + i];
+        const float g = V.grid((uint32_t)i);
         const float sub_v = fabsf(d - g);
         if (sub_v <= sub_min) { sub_min = sub_v; z_min = g; }
     }
     return z_min;
+}
+
+// One (type, candidate) as the literal elements see it.  INL: the cell from the grid-domain thresholds, otherwise from the
+// x-domain thresholds X of this (type, candidate).
+// An element that is a step-function element for THIS candidate (|x / s| < lim) contributes what the closed form would have
+// given it -- (O_J - x)^2 in double -- so a candidate's sum does not depend (beyond 1e-13) on whether the launch's smallest
+// scale sent the element here; elsewhere: the reference sequence.
+template <bool INL>
+struct SortLiteral {
+    SortTypeView V;
+    const uint32_t *X;
+    const float *grid;       // the codebook in memory
+    int m;
+    uint32_t nthr;
+    float s, lim;
+    __device__ __forceinline__ uint32_t cell_of(float xv, float d) const
+    {
+        return INL ? sort_cell_of_d(V, nthr, d) : sort_cell_of_key(X, nthr, sort_key(xv));
+    }
+    // q before any pair rule; d = x / s; tab: a step-function element for this candidate
+    __device__ __forceinline__ float q_of(float xv, float &d, bool &tab) const
+    {
+        d = xv / s;
+        tab = fabsf(d) < lim;
+        if (tab) return V.value(cell_of(xv, d));
+        return sort_literal_q(xv, s, V, grid, m, d);
+    }
+    __device__ __forceinline__ double term_of(float q, float d, bool tab, float xv) const
+    {
+        if (tab) {
+            const double e = (double)(q * s) - (double)xv;
+            return e * e;
+        }
+        return clip_literal_term(q, d, s, xv);
+    }
+};
+// OliVe's pair rule (OQ:315-318): the correction v^2 - (O(v) - v)^2 of a pair's victim (key kv), whose output is 0 * s (exact)
+template <bool INL>
+__device__ __forceinline__ double sort_victim_correction(uint32_t kv, float s, SortTypeView V, uint32_t nthr, const uint32_t *X)
+{
+    const float vv = sort_unkey(kv);
+    const uint32_t J = INL ? sort_cell_of_d(V, nthr, vv / s) : sort_cell_of_key(X, nthr, kv);
+    const double O = (double)(V.value(J) * s), dv = (double)vv;
+    return dv * dv - (O - dv) * (O - dv);
 }
 
 // ---- the sorting network -------------------------------------------------------------------------------------------------
@@ -326,40 +440,25 @@ k_search_sorted(const uint4 *__restrict__ x, size_t vpr, size_t rows, const floa
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t ntypes = (uint32_t)st.ntypes, ntc = ntypes * ncand, nthr_pad = st.nthr_pad, nkg = nthr_pad / (uint32_t)kSortKS;
     const uint32_t nitems = ntc * nkg;
-    // (type, candidate) of a flat index without an integer division (~20 instructions each on this machine; two of them per
-    // threshold were a tenth of the kernel): at most kMaxTypes = 4 types
-    auto type_of = [&](uint32_t tc) { return (tc >= ncand ? 1u : 0u) + (tc >= 2u * ncand ? 1u : 0u) + (tc >= 3u * ncand ? 1u : 0u); };
     const SortLds L = sort_lds(ntc, nthr_pad, st.ntypes, OVP);
     char *base = reinterpret_cast<char *>(smem);
     uint32_t *sK = reinterpret_cast<uint32_t *>(base);
     long long *sP4 = reinterpret_cast<long long *>(base + L.off_p4);
     uint32_t *sX = reinterpret_cast<uint32_t *>(base + L.off_x);          // [ntc][nthr_pad] keys of the x-domain thresholds
     float *sS = reinterpret_cast<float *>(base + L.off_s);               // [ntc]
-    float *sV = reinterpret_cast<float *>(base + L.off_v);               // per type: [0..65] values, [66..129] thresholds T
+    float *sV = reinterpret_cast<float *>(base + L.off_v);               // per type: a block of kSortTy dwords
     unsigned long long *sScan = reinterpret_cast<unsigned long long *>(base + L.off_misc);      // [4] counts, [4..8] sums
     long long *sScanI = reinterpret_cast<long long *>(base + L.off_misc + 64);
     double *sScanD = reinterpret_cast<double *>(base + L.off_misc + 128);
     int *sFlag = reinterpret_cast<int *>(base + L.off_misc + 192);
 
+    auto ty = [&](uint32_t t) { return SortTypeView{sV + t * kSortTy}; };
     // per type: values, grid-domain thresholds, rounding boundaries and scalars (once per workgroup; constant indices into the
     // kernel argument)
 #pragma unroll
     for (int t = 0; t < kMaxTypes; t++)
-        if (t < st.ntypes) sort_fill_type(sV + (uint32_t)t * kSortTy, st.ty[t], st.nneg[t], tid);
+        if (t < st.ntypes) sort_fill_type(ty((uint32_t)t), st.ty[t], st.nneg[t], tid);
     __syncthreads();
-    auto ty_nthr = [&](uint32_t t) { return reinterpret_cast<const uint32_t *>(sV + t * kSortTy)[130]; };
-    auto ty_kpos = [&](uint32_t t) { return (int)reinterpret_cast<const uint32_t *>(sV + t * kSortTy)[131]; };
-    auto ty_kneg = [&](uint32_t t) { return (int)reinterpret_cast<const uint32_t *>(sV + t * kSortTy)[132]; };
-    auto ty_gmax = [&](uint32_t t) { return sV[t * kSortTy + 133u]; };
-    auto ty_lim = [&](uint32_t t) { return sV[t * kSortTy + 134u]; };
-    auto ty_nneg = [&](uint32_t t) { return reinterpret_cast<const uint32_t *>(sV + t * kSortTy)[136]; };
-    auto ty_m = [&](uint32_t t) { return (int)reinterpret_cast<const uint32_t *>(sV + t * kSortTy)[135]; };
-    auto ty_grid = [&](uint32_t t) {
-        const float *g = st.ty[0].grid;
-#pragma unroll
-        for (int u = 1; u < kMaxTypes; u++) g = (uint32_t)u == t ? st.ty[u].grid : g;
-        return g;
-    };
 
     const size_t nchunks_row = (vpr + VPC - 1) / VPC;
     for (size_t row = PT ? 0 : blockIdx.x; row < rows; row += PT ? 1 : gridDim.x) {
@@ -370,7 +469,7 @@ k_search_sorted(const uint4 *__restrict__ x, size_t vpr, size_t rows, const floa
         // AQ:541-549).  Said directly instead of through 4096 literal evaluations per candidate.
         if (!PT && (xm == 0.0f || xm != xm)) {
             for (uint32_t tc = tid; tc < ntc; tc += kSortNT) {
-                const uint32_t t = type_of(tc), c = tc - t * ncand;
+                const uint32_t t = sort_type_of(tc, ncand), c = tc - t * ncand;
                 sse[((size_t)t * ncand_all + c) * rows + row] = __builtin_nan("");
             }
             continue;
@@ -378,14 +477,14 @@ k_search_sorted(const uint4 *__restrict__ x, size_t vpr, size_t rows, const floa
         // ---- 1. candidate scales (AQ:300, :536): s = fl32(fl32(x_max * ratio_c) / gmax_t), usable and non-decreasing along c
         bool ok = true;
         for (uint32_t tc = tid; tc < ntc; tc += kSortNT) {
-            const uint32_t t = type_of(tc), c = tc - t * ncand;
-            const Scale sc = make_scale(xm * ratios[c], ty_gmax(t));
+            const uint32_t t = sort_type_of(tc, ncand), c = tc - t * ncand;
+            const Scale sc = make_scale(xm * ratios[c], ty(t).gmax());
             sS[tc] = sc.s;
             ok = ok && sc.ok && (sc.s > 0.0f);
         }
         __syncthreads();
         for (uint32_t tc = tid; tc < ntc; tc += kSortNT) {
-            const uint32_t t = type_of(tc), c = tc - t * ncand;
+            const uint32_t t = sort_type_of(tc, ncand), c = tc - t * ncand;
             if (c > 0u) ok = ok && (sS[tc] >= sS[tc - 1u]);
         }
         if (tid == 0u) *sFlag = 0;
@@ -398,19 +497,18 @@ k_search_sorted(const uint4 *__restrict__ x, size_t vpr, size_t rows, const floa
         if constexpr (INL) {
             // (per (type, candidate) only the two bounds of the outlier region: key >= kp a positive outlier, key < kn a negative one)
             for (uint32_t tc = tid; tc < ntc; tc += kSortNT) {
-                const uint32_t t = type_of(tc);
-                const float *v = sV + t * kSortTy;
+                const SortTypeView V = ty(sort_type_of(tc, ncand));
                 const double sd = (double)sS[tc];
-                sX[2u * tc] = (usable && ty_kpos(t) >= 0) ? sort_threshold_key(v, (uint32_t)ty_kpos(t), sd) : kSortSent;
-                sX[2u * tc + 1u] = (usable && ty_kneg(t) >= 0) ? sort_threshold_key(v, (uint32_t)ty_kneg(t), sd) : 0u;
+                sX[2u * tc] = (usable && V.kpos() >= 0) ? sort_threshold_key(V, (uint32_t)V.kpos(), sd) : kSortSent;
+                sX[2u * tc + 1u] = (usable && V.kneg() >= 0) ? sort_threshold_key(V, (uint32_t)V.kneg(), sd) : 0u;
             }
         }
         const uint32_t q_thr = kSortNT / nthr_pad, r_thr = kSortNT - q_thr * nthr_pad;      // (uniform: scalar divisions)
         for (uint32_t p = tid, tc = tid / nthr_pad, k = tid - (tid / nthr_pad) * nthr_pad; !INL && p < ntc * nthr_pad; p += kSortNT) {
-            const uint32_t t = type_of(tc);
+            const uint32_t t = sort_type_of(tc, ncand);
             uint32_t key = kSortSent;
-            if (usable && k < ty_nthr(t)) {
-                key = sort_threshold_key(sV + t * kSortTy, k, (double)sS[tc]);
+            if (usable && k < ty(t).nthr()) {
+                key = sort_threshold_key(ty(t), k, (double)sS[tc]);
             }
             sX[p] = key;
             k += r_thr;
@@ -431,18 +529,18 @@ k_search_sorted(const uint4 *__restrict__ x, size_t vpr, size_t rows, const floa
         float Lx = 0.0f;                                    // |x| < Lx: a step-function element for EVERY candidate of every type
         if (usable) {
             Lx = __builtin_ldexpf(0.999f, ex + 8);          // ... whose fixed-point image stays below 2^46
-            for (uint32_t t = 0; t < ntypes; t++) Lx = fminf(Lx, ty_lim(t) * sS[t * ncand] * 0.999f);
+            for (uint32_t t = 0; t < ntypes; t++) Lx = fminf(Lx, ty(t).lim() * sS[t * ncand] * 0.999f);
         }
         __syncthreads();
         float XoP = __builtin_inff(), XoN = -__builtin_inff();            // OliVe: outlier under the smallest scale of SOME type
         if (OVP && usable) {
             for (uint32_t t = 0; t < ntypes; t++) {
                 if (INL) {
-                    if (ty_kpos(t) >= 0) XoP = fminf(XoP, sort_unkey(sX[2u * (t * ncand)]));
-                    if (ty_kneg(t) >= 0) XoN = fmaxf(XoN, sort_unkey(sX[2u * (t * ncand) + 1u]));
+                    if (ty(t).kpos() >= 0) XoP = fminf(XoP, sort_unkey(sX[2u * (t * ncand)]));
+                    if (ty(t).kneg() >= 0) XoN = fmaxf(XoN, sort_unkey(sX[2u * (t * ncand) + 1u]));
                 } else {
-                    if (ty_kpos(t) >= 0) XoP = fminf(XoP, sort_unkey(sX[(t * ncand) * nthr_pad + (uint32_t)ty_kpos(t)]));
-                    if (ty_kneg(t) >= 0) XoN = fmaxf(XoN, sort_unkey(sX[(t * ncand) * nthr_pad + (uint32_t)ty_kneg(t)]));
+                    if (ty(t).kpos() >= 0) XoP = fminf(XoP, sort_unkey(sX[(t * ncand) * nthr_pad + (uint32_t)ty(t).kpos()]));
+                    if (ty(t).kneg() >= 0) XoN = fmaxf(XoN, sort_unkey(sX[(t * ncand) * nthr_pad + (uint32_t)ty(t).kneg()]));
                 }
             }
         }
@@ -488,12 +586,8 @@ k_search_sorted(const uint4 *__restrict__ x, size_t vpr, size_t rows, const floa
                 }
             }
             // counts of the chunk, and this thread's places in the lists: one packed scan (fields of 16 bits, <= 4096 each)
-            unsigned long long pk = (unsigned long long)nreg | (unsigned long long)nlit << 16 | (unsigned long long)ncap << 32, inc = pk;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const unsigned long long tv = (unsigned long long)__shfl_up((long long)inc, off, 64);
-                if (lane >= (uint32_t)off) inc += tv;
-            }
+            const unsigned long long pk = (unsigned long long)nreg | (unsigned long long)nlit << 16 | (unsigned long long)ncap << 32;
+            const unsigned long long inc = wave_scan_incl(pk, lane);
             const uint32_t par = (nch_done & 1u) * 4u;
             nch_done++;
             if (lane == 63u) sScan[par + wave] = inc;
@@ -525,85 +619,46 @@ k_search_sorted(const uint4 *__restrict__ x, size_t vpr, size_t rows, const floa
                 }
                 __syncthreads();
                 if (tot_lit) {
-                    // An element that is a step-function element for THIS candidate (|x / s| < lim) contributes what the closed
-                    // form would have given it -- (O_J - x)^2 in double -- so a candidate's sum does not depend (beyond 1e-13) on
-                    // whether the launch's smallest scale sent the element here; elsewhere: the reference sequence.
                     for (uint32_t tc = tid, ui = 0; tc < ntc; tc += kSortNT, ui++) {
-                        const uint32_t t = type_of(tc);
-                        const float *grid = ty_grid(t);
-                        const int gm = ty_m(t);
-                        const float s = sS[tc], lim = usable ? ty_lim(t) : 0.0f;
-                        const uint32_t *X = sX + (INL ? 0u : tc * nthr_pad);
-                        const float *v = sV + t * kSortTy;
-                        const uint32_t nthr_t = ty_nthr(t);
-                        auto q_of = [&](float xv, float &d, bool &tab) -> float {
-                            d = xv / s;
-                            tab = fabsf(d) < lim;
-                            if (tab) {
-                                const uint32_t kx = sort_key(xv);
-                                uint32_t lo = 0, hi = nthr_t;
-                                while (lo < hi) {             // (inline thresholds: RN(x / s) >= T_k <=> x >= X_k)
-                                    const uint32_t mid = (lo + hi) >> 1;
-                                    if (INL ? d >= v[66u + mid] : kx >= X[mid]) lo = mid + 1u; else hi = mid;
-                                }
-                                return v[lo];
-                            }
-                            return sort_literal_q(xv, s, v, grid, gm, d);
-                        };
-                        auto term_of = [&](float q, float d, bool tab, float xv) -> double {
-                            if (tab) {
-                                const double e = (double)(q * s) - (double)xv;
-                                return e * e;
-                            }
-                            return sweep_term(q, d, s, xv);
-                        };
+                        const uint32_t t = sort_type_of(tc, ncand);
+                        const SortLiteral<INL> lt{ty(t), sX + (INL ? 0u : tc * nthr_pad), sort_type_grid(st, t), ty(t).m(), ty(t).nthr(),
+                                                  sS[tc], usable ? ty(t).lim() : 0.0f};
                         double sum_l = 0.0;
                         for (uint32_t i = 0; i < tot_lit; i += OVP ? 2u : 1u) {
                             const float xa_ = sList[i];
                             float da, db = 0.0f;
                             bool ta, tb = false;
-                            float qa = q_of(xa_, da, ta), qb = 0.0f;
+                            float qa = lt.q_of(xa_, da, ta), qb = 0.0f;
                             if (OVP) {
                                 const float xb_ = sList[i + 1u];
-                                qb = q_of(xb_, db, tb);
+                                qb = lt.q_of(xb_, db, tb);
                                 const bool me = fabsf(qa) > 32.0f, mo = fabsf(qb) > 32.0f;      // OQ:314
                                 const bool ve = mo && !me;
                                 qa = qa * (ve ? 0.0f : 1.0f);
                                 qb = qb * (me ? 0.0f : 1.0f);
-                                sum_l += term_of(qb, db, tb, xb_);
+                                sum_l += lt.term_of(qb, db, tb, xb_);
                             }
-                            sum_l += term_of(qa, da, ta, xa_);
+                            sum_l += lt.term_of(qa, da, ta, xa_);
                         }
 #pragma unroll
                         for (int u = 0; u < kSortNL; u++) lit[u] += (uint32_t)u == ui ? sum_l : 0.0;
                     }
                 }
                 if (OVP && tot_cap) {
-                    // work item (type, candidate, j): the pairs j, j + 4, ... in list order
+                    // work item (type, candidate, j): the pairs j, j + 4, ... in list order (four lanes per (type, candidate) over
+                    // the whole chunk's list; the short kernel: one lane, at most four pairs per lane on the list)
                     for (uint32_t it = tid, ui = 0; it < 4u * ntc; it += kSortNT, ui++) {
-                        const uint32_t tc = it >> 2, j0 = it & 3u, t = type_of(tc);
+                        const uint32_t tc = it >> 2, j0 = it & 3u, t = sort_type_of(tc, ncand);
                         const uint32_t *X = sX + (INL ? 0u : tc * nthr_pad);
                         const float s = sS[tc];
-                        const float *v = sV + t * kSortTy;
-                        const uint32_t nthr_t = ty_nthr(t);
-                        const uint32_t kp = INL ? sX[2u * tc] : (ty_kpos(t) >= 0 ? X[ty_kpos(t)] : kSortSent);      // key >= kp: a positive outlier
-                        const uint32_t kn = INL ? sX[2u * tc + 1u] : (ty_kneg(t) >= 0 ? X[ty_kneg(t)] : 0u);       // key <  kn: a negative outlier
+                        const uint32_t nthr_t = ty(t).nthr();
+                        const uint32_t kp = INL ? sX[2u * tc] : (ty(t).kpos() >= 0 ? X[ty(t).kpos()] : kSortSent);      // key >= kp: a positive outlier
+                        const uint32_t kn = INL ? sX[2u * tc + 1u] : (ty(t).kneg() >= 0 ? X[ty(t).kneg()] : 0u);       // key <  kn: a negative outlier
                         double sum_c = 0.0;
                         for (uint32_t i = j0; i < tot_cap; i += 4u) {
                             const uint32_t ka = sK[kSortK - 2u - 2u * i], kb = sK[kSortK - 1u - 2u * i];
                             const bool me = ka >= kp || ka < kn, mo = kb >= kp || kb < kn;
-                            if (me || mo) {
-                                const uint32_t kv = me ? kb : ka;                                  // the victim (OQ:315-318)
-                                const float vv = sort_unkey(kv);
-                                const float dvv = vv / s;
-                                uint32_t lo = 0, hi = nthr_t;
-                                while (lo < hi) {
-                                    const uint32_t mid = (lo + hi) >> 1;
-                                    if (INL ? dvv >= v[66u + mid] : kv >= X[mid]) lo = mid + 1u; else hi = mid;
-                                }
-                                const double O = (double)(v[lo] * s), dv = (double)vv;
-                                sum_c += dv * dv - (O - dv) * (O - dv);
-                            }
+                            if (me || mo) sum_c += sort_victim_correction<INL>(me ? kb : ka, s, ty(t), nthr_t, X);     // (the victim)
                         }
 #pragma unroll
                         for (int u = 0; u < kSortNC; u++) corr[u] += (uint32_t)u == ui ? sum_c : 0.0;
@@ -619,7 +674,7 @@ k_search_sorted(const uint4 *__restrict__ x, size_t vpr, size_t rows, const floa
 #pragma unroll
                 for (int q = 0; q < kSortEPT / 4; q++) dst[q] = make_uint4(k[4 * q], k[4 * q + 1], k[4 * q + 2], k[4 * q + 3]);
             }
-            constexpr int PSH = sort_psh(OVP), NG = kSortEPT >> PSH;
+            constexpr int PSH = kSortPsh, NG = kSortEPT >> PSH;
             long long g[NG], mine = 0;
 #pragma unroll
             for (int q = 0; q < NG; q++) {
@@ -628,12 +683,7 @@ k_search_sorted(const uint4 *__restrict__ x, size_t vpr, size_t rows, const floa
                 for (int e = 0; e < (1 << PSH); e++) g[q] += sort_key_fixed(k[(q << PSH) + e], F);
                 mine += g[q];
             }
-            long long incs = mine;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const long long tv = __shfl_up(incs, off, 64);
-                if (lane >= (uint32_t)off) incs += tv;
-            }
+            const long long incs = wave_scan_incl(mine, lane);
             if (lane == 63u) sScanI[wave] = incs;
             __syncthreads();
             long long pre = incs - mine;
@@ -651,9 +701,9 @@ k_search_sorted(const uint4 *__restrict__ x, size_t vpr, size_t rows, const floa
             const double Stot = (double)Stot_i * unit, dn = (double)Kreg;
             const uint32_t q_it = kSortNT / nkg, r_it = kSortNT - q_it * nkg;
             for (uint32_t it = tid, ui = 0, tc = tid / nkg, kg = tid - (tid / nkg) * nkg; it < nitems; it += kSortNT, ui++) {
-                const uint32_t t = type_of(tc);
+                const uint32_t t = sort_type_of(tc, ncand);
                 const float s = sS[tc];
-                const float *v = sV + t * kSortTy + kg * (uint32_t)kSortKS;
+                const float *v = ty(t).v + kTyValue + kg * (uint32_t)kSortKS;
                 const uint32_t *X = sX + (INL ? 0u : tc * nthr_pad + kg * (uint32_t)kSortKS);
                 // (the running ADDRESS is the search state: a probe is ds_read_b32 with an immediate offset, a step is compare +
                 //  select + add -- an index would cost a shift-add per probe on top)
@@ -663,14 +713,14 @@ k_search_sorted(const uint4 *__restrict__ x, size_t vpr, size_t rows, const floa
                 for (int j = 0; j < kSortKS; j++) {
                     if constexpr (INL) {
                         const uint32_t kk = kg * (uint32_t)kSortKS + (uint32_t)j;
-                        Xk[j] = (usable && kk < ty_nthr(t)) ? sort_threshold_key(sV + t * kSortTy, kk, (double)s) : kSortSent;
+                        Xk[j] = (usable && kk < ty(t).nthr()) ? sort_threshold_key(ty(t), kk, (double)s) : kSortSent;
                     } else {
                         Xk[j] = X[j];
                     }
                     ap[j] = sK;
                 }
 #pragma unroll
-                for (int step = kSortK / 2; step >= 1; step >>= 1) {
+                for (int step = kSortK / 2; step >= 1; step >>= 1) {        // 13 probes: 4096 keys (the short kernel: 11 over its 1024)
                     uint32_t kv[kSortKS];
 #pragma unroll
                     for (int j = 0; j < kSortKS; j++) kv[j] = ap[j][step - 1];
@@ -679,21 +729,18 @@ k_search_sorted(const uint4 *__restrict__ x, size_t vpr, size_t rows, const floa
                 }
 #pragma unroll
                 for (int j = 0; j < kSortKS; j++) pos[j] = (uint32_t)(ap[j] - sK) + (ap[j][0] < Xk[j] ? 1u : 0u);
-                const uint32_t nb = ty_nneg(t);
+                const uint32_t nb = ty(t).nneg();
                 double part = 0.0;
                 if (kg == 0u) {
-                    const double Ob_ = (double)(sV[t * kSortTy + nb] * s);
+                    // (one index from sV: the view's two-step address moves this kernel's scratch from 72 to 184 bytes with the pair rule)
+                    const double Ob_ = (double)(sV[t * kSortTy + kTyValue + nb] * s);
                     part = dn * Ob_ * Ob_ - 2.0 * Ob_ * Stot;
                 }
 #pragma unroll
                 for (int j = 0; j < kSortKS; j++) {
                     const uint32_t p = pos[j];
                     long long slt = sP4[p >> PSH];
-                    if constexpr (PSH == 1) {
-                        if (p & 1u) slt += sort_key_fixed(sK[p - 1u], F);
-                    } else {
-                        for (uint32_t i = p & ~3u; i < p; i++) slt += sort_key_fixed(sK[i], F);
-                    }
+                    if (p & 1u) slt += sort_key_fixed(sK[p - 1u], F);
                     const bool below = kg * (uint32_t)kSortKS + (uint32_t)j < nb;        // a threshold below zero: the elements BELOW it
                     const double N = below ? -(double)p : (double)(Kreg - p);
                     const double S = (double)(below ? -slt : Stot_i - slt) * unit;
@@ -754,7 +801,7 @@ k_search_sorted(const uint4 *__restrict__ x, size_t vpr, size_t rows, const floa
             for (int u = 0; u < kSortNL; u++) l = (uint32_t)u == ui ? lit[u] : l;
             sum += l;
             if (OVP) sum += (fC[4u * tc] + fC[4u * tc + 1u]) + (fC[4u * tc + 2u] + fC[4u * tc + 3u]);
-            const uint32_t t = type_of(tc), c = tc - t * ncand;       // (ratios / sse point at this piece's first candidate)
+            const uint32_t t = sort_type_of(tc, ncand), c = tc - t * ncand;       // (ratios / sse point at this piece's first candidate)
             sse[((size_t)t * ncand_all + c) * rows + row] = sum;
         }
         __syncthreads();
@@ -792,31 +839,18 @@ k_search_sorted_short(const uint4 *__restrict__ x, uint32_t vpr, size_t rows, co
     uint32_t *sK = reinterpret_cast<uint32_t *>(wb);                                   // this wavefront's keys
     long long *sP4 = reinterpret_cast<long long *>(wb + ((uint32_t)kSortKSh + (uint32_t)(kSortKSh >> kSortR)) * 4u);
     float *sS = reinterpret_cast<float *>(wb + ((uint32_t)kSortKSh + (uint32_t)(kSortKSh >> kSortR)) * 4u + ((uint32_t)kSortKSh / 2u + 2u) * 8u);
+    auto ty = [&](uint32_t t) { return SortTypeView{sV + t * kSortTy}; };
 #pragma unroll
     for (int t = 0; t < kMaxTypes; t++)
-        if (t < st.ntypes) sort_fill_type(sV + (uint32_t)t * kSortTy, st.ty[t], st.nneg[t], tid);
+        if (t < st.ntypes) sort_fill_type(ty((uint32_t)t), st.ty[t], st.nneg[t], tid);
     __syncthreads();                                        // (the only workgroup barrier: from here on every wavefront is on its own)
-    auto ty_nthr = [&](uint32_t t) { return reinterpret_cast<const uint32_t *>(sV + t * kSortTy)[130]; };
-    auto ty_kpos = [&](uint32_t t) { return (int)reinterpret_cast<const uint32_t *>(sV + t * kSortTy)[131]; };
-    auto ty_kneg = [&](uint32_t t) { return (int)reinterpret_cast<const uint32_t *>(sV + t * kSortTy)[132]; };
-    auto ty_gmax = [&](uint32_t t) { return sV[t * kSortTy + 133u]; };
-    auto ty_lim = [&](uint32_t t) { return sV[t * kSortTy + 134u]; };
-    auto ty_m = [&](uint32_t t) { return (int)reinterpret_cast<const uint32_t *>(sV + t * kSortTy)[135]; };
-    auto ty_nneg = [&](uint32_t t) { return reinterpret_cast<const uint32_t *>(sV + t * kSortTy)[136]; };
-    auto ty_grid = [&](uint32_t t) {
-        const float *g = st.ty[0].grid;
-#pragma unroll
-        for (int u = 1; u < kMaxTypes; u++) g = (uint32_t)u == t ? st.ty[u].grid : g;
-        return g;
-    };
-    auto type_of = [&](uint32_t tc) { return (tc >= ncand ? 1u : 0u) + (tc >= 2u * ncand ? 1u : 0u) + (tc >= 3u * ncand ? 1u : 0u); };
 
     for (size_t row = (size_t)blockIdx.x * 4u + wave; row < rows; row += (size_t)gridDim.x * 4u) {
         const float xm = xmax[row];
         const uint4 *xr = x + row * (size_t)vpr;
         if (xm == 0.0f || xm != xm) {                        // (a zero / NaN statistic: NaN for every candidate, see above)
             for (uint32_t tc = lane; tc < ntc; tc += 64u) {
-                const uint32_t t = type_of(tc), c = tc - t * ncand;
+                const uint32_t t = sort_type_of(tc, ncand), c = tc - t * ncand;
                 sse[((size_t)t * ncand_all + c) * rows + row] = __builtin_nan("");
             }
             continue;
@@ -824,14 +858,14 @@ k_search_sorted_short(const uint4 *__restrict__ x, uint32_t vpr, size_t rows, co
         // ---- candidate scales
         bool ok = true;
         for (uint32_t tc = lane; tc < ntc; tc += 64u) {
-            const uint32_t t = type_of(tc), c = tc - t * ncand;
-            const Scale sc = make_scale(xm * ratios[c], ty_gmax(t));
+            const uint32_t t = sort_type_of(tc, ncand), c = tc - t * ncand;
+            const Scale sc = make_scale(xm * ratios[c], ty(t).gmax());
             sS[tc] = sc.s;
             ok = ok && sc.ok && (sc.s > 0.0f);
         }
         sort_sync<true>();
         for (uint32_t tc = lane; tc < ntc; tc += 64u) {
-            const uint32_t t = type_of(tc), c = tc - t * ncand;
+            const uint32_t t = sort_type_of(tc, ncand), c = tc - t * ncand;
             if (c > 0u) ok = ok && (sS[tc] >= sS[tc - 1u]);
         }
         const bool usable = __ballot(ok) == ~0ull;
@@ -841,14 +875,14 @@ k_search_sorted_short(const uint4 *__restrict__ x, uint32_t vpr, size_t rows, co
         float Lx = 0.0f;
         if (usable) {
             Lx = __builtin_ldexpf(0.999f, ex + 8);
-            for (uint32_t t = 0; t < ntypes; t++) Lx = fminf(Lx, ty_lim(t) * sS[t * ncand] * 0.999f);
+            for (uint32_t t = 0; t < ntypes; t++) Lx = fminf(Lx, ty(t).lim() * sS[t * ncand] * 0.999f);
         }
         float XoP = __builtin_inff(), XoN = -__builtin_inff();            // OliVe: an outlier under the smallest scale of SOME type
         if (OVP && usable) {
             for (uint32_t t = 0; t < ntypes; t++) {
                 const double sd0 = (double)sS[t * ncand];
-                if (ty_kpos(t) >= 0) XoP = fminf(XoP, sort_unkey(sort_threshold_key(sV + t * kSortTy, (uint32_t)ty_kpos(t), sd0)));
-                if (ty_kneg(t) >= 0) XoN = fmaxf(XoN, sort_unkey(sort_threshold_key(sV + t * kSortTy, (uint32_t)ty_kneg(t), sd0)));
+                if (ty(t).kpos() >= 0) XoP = fminf(XoP, sort_unkey(sort_threshold_key(ty(t), (uint32_t)ty(t).kpos(), sd0)));
+                if (ty(t).kneg() >= 0) XoN = fmaxf(XoN, sort_unkey(sort_threshold_key(ty(t), (uint32_t)ty(t).kneg(), sd0)));
             }
         }
         // ---- the row: 16 elements per lane
@@ -928,12 +962,7 @@ k_search_sorted_short(const uint4 *__restrict__ x, uint32_t vpr, size_t rows, co
                 g[q] = sort_key_fixed(k[2 * q], F) + sort_key_fixed(k[2 * q + 1], F);
                 mine += g[q];
             }
-            long long incs = mine;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const long long tv = __shfl_up(incs, off, 64);
-                if (lane >= (uint32_t)off) incs += tv;
-            }
+            const long long incs = wave_scan_incl(mine, lane);
             long long pre = incs - mine;
 #pragma unroll
             for (int q = 0; q < 8; q++) {
@@ -950,13 +979,7 @@ k_search_sorted_short(const uint4 *__restrict__ x, uint32_t vpr, size_t rows, co
         const bool cap_list = OVP && tot_cap != 0u && tot_cap <= 32u && __ballot(my_cap > 4u) == 0ull;
         float *sL = reinterpret_cast<float *>(sK + kSortKSh);
         if (cap_list) {
-            uint32_t inc = my_cap;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t tv = (uint32_t)__shfl_up((int)inc, off, 64);
-                if (lane >= (uint32_t)off) inc += tv;
-            }
-            const uint32_t at = inc - my_cap;
+            const uint32_t at = wave_scan_incl(my_cap, lane) - my_cap;
             uint32_t *sC = sK + kSortKSh;
 #pragma unroll
             for (int u = 0; u < 4; u++)
@@ -964,13 +987,7 @@ k_search_sorted_short(const uint4 *__restrict__ x, uint32_t vpr, size_t rows, co
             sort_sync<true>();
         }
         if (lit_list) {
-            uint32_t inc = my_lit;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t tv = (uint32_t)__shfl_up((int)inc, off, 64);
-                if (lane >= (uint32_t)off) inc += tv;
-            }
-            const uint32_t at = inc - my_lit;
+            const uint32_t at = wave_scan_incl(my_lit, lane) - my_lit;
             if (my_lit > 0u) sL[at] = lx0;
             if (my_lit > 1u) sL[at + 1u] = lx1;
             sort_sync<true>();
@@ -978,11 +995,11 @@ k_search_sorted_short(const uint4 *__restrict__ x, uint32_t vpr, size_t rows, co
         const double Stot = (double)Stot_i * unit, dn = (double)Kreg;
         // ---- one lane per (codebook, candidate): its threshold groups in order, then the literal elements
         for (uint32_t tc = lane; tc < ntc; tc += 64u) {
-            const uint32_t t = type_of(tc), c = tc - t * ncand;
+            const uint32_t t = sort_type_of(tc, ncand), c = tc - t * ncand;
             const float s = sS[tc];
             const double sd = (double)s;
-            const float *v = sV + t * kSortTy;
-            const uint32_t nthr_t = ty_nthr(t), nb = ty_nneg(t);
+            const SortTypeView V = ty(t);
+            const uint32_t nthr_t = V.nthr(), nb = V.nneg();
             double sum = Q;
             if (Kreg) {
                 for (uint32_t kg = 0; kg < nkg; kg++) {
@@ -990,13 +1007,13 @@ k_search_sorted_short(const uint4 *__restrict__ x, uint32_t vpr, size_t rows, co
 #pragma unroll
                     for (int j = 0; j < kSortKS; j++) {
                         const uint32_t kk = kg * (uint32_t)kSortKS + (uint32_t)j;
-                        Xk[j] = (usable && kk < nthr_t) ? sort_threshold_key(v, kk, sd) : kSortSent;
+                        Xk[j] = (usable && kk < nthr_t) ? sort_threshold_key(V, kk, sd) : kSortSent;
                     }
                     const uint32_t *ap[kSortKS];
 #pragma unroll
                     for (int j = 0; j < kSortKS; j++) ap[j] = sK;
 #pragma unroll
-                    for (int step = kSortKSh / 2; step >= 1; step >>= 1) {
+                    for (int step = kSortKSh / 2; step >= 1; step >>= 1) {      // 11 probes: this wavefront's 1024 keys
                         uint32_t kv[kSortKS];
 #pragma unroll
                         for (int j = 0; j < kSortKS; j++) kv[j] = ap[j][step - 1];
@@ -1007,7 +1024,7 @@ k_search_sorted_short(const uint4 *__restrict__ x, uint32_t vpr, size_t rows, co
                     for (int j = 0; j < kSortKS; j++) pos[j] = (uint32_t)(ap[j] - sK) + (ap[j][0] < Xk[j] ? 1u : 0u);
                     double part = 0.0;
                     if (kg == 0u) {
-                        const double Ob_ = (double)(v[nb] * s);
+                        const double Ob_ = (double)(V.value(nb) * s);
                         part = dn * Ob_ * Ob_ - 2.0 * Ob_ * Stot;
                     }
 #pragma unroll
@@ -1018,7 +1035,7 @@ k_search_sorted_short(const uint4 *__restrict__ x, uint32_t vpr, size_t rows, co
                         const bool below = kk < nb;
                         const double N = below ? -(double)p : (double)(Kreg - p);
                         const double S = (double)(below ? -slt : Stot_i - slt) * unit;
-                        const double Oa = (double)(v[kk] * s), Ob = (double)(v[kk + 1u] * s);
+                        const double Oa = (double)(V.value(kk) * s), Ob = (double)(V.value(kk + 1u) * s);
                         part += (Ob - Oa) * ((Ob + Oa) * N - 2.0 * S);
                     }
                     sum += part;
@@ -1026,22 +1043,12 @@ k_search_sorted_short(const uint4 *__restrict__ x, uint32_t vpr, size_t rows, co
             }
             if constexpr (OVP) {
                 // the pair rule (OQ:311-320): victims' corrections from the list -- or, with the literal pairs, from the row
-                const uint32_t kp = (usable && ty_kpos(t) >= 0) ? sort_threshold_key(v, (uint32_t)ty_kpos(t), sd) : kSortSent;
-                const uint32_t kn = (usable && ty_kneg(t) >= 0) ? sort_threshold_key(v, (uint32_t)ty_kneg(t), sd) : 0u;
-                auto cell_of = [&](float d) {                 // RN(x / s) >= T_k  <=>  x >= X_k
-                    uint32_t lo = 0, hi = nthr_t;
-                    while (lo < hi) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        if (d >= v[66u + mid]) lo = mid + 1u; else hi = mid;
-                    }
-                    return lo;
-                };
+                const uint32_t kp = (usable && V.kpos() >= 0) ? sort_threshold_key(V, (uint32_t)V.kpos(), sd) : kSortSent;
+                const uint32_t kn = (usable && V.kneg() >= 0) ? sort_threshold_key(V, (uint32_t)V.kneg(), sd) : 0u;
                 auto correction = [&](uint32_t ka, uint32_t kb) -> double {
                     const bool me = ka >= kp || ka < kn, mo = kb >= kp || kb < kn;
                     if (!(me || mo)) return 0.0;
-                    const float vv = sort_unkey(me ? kb : ka);                 // the victim (OQ:315-318)
-                    const double O = (double)(v[cell_of(vv / s)] * s), dv = (double)vv;
-                    return dv * dv - (O - dv) * (O - dv);
+                    return sort_victim_correction<true>(me ? kb : ka, s, V, nthr_t, nullptr);     // the victim: the other member
                 };
                 double sum_c = 0.0, sum_l = 0.0;
                 if (cap_list) {
@@ -1049,21 +1056,8 @@ k_search_sorted_short(const uint4 *__restrict__ x, uint32_t vpr, size_t rows, co
                     for (uint32_t i = 0; i < tot_cap; i++) sum_c += correction(sC[2u * i], sC[2u * i + 1u]);
                 }
                 if (tot_lit != 0u || (tot_cap != 0u && !cap_list)) {
-                    const float *grid = ty_grid(t);
-                    const int gm = ty_m(t);
-                    const float lim = usable ? ty_lim(t) : 0.0f;
-                    auto q_of = [&](float xv, float &d, bool &tab) -> float {
-                        d = xv / s;
-                        tab = fabsf(d) < lim;
-                        return tab ? v[cell_of(d)] : sort_literal_q(xv, s, v, grid, gm, d);
-                    };
-                    auto term_of = [&](float q, float d, bool tab, float xv) -> double {
-                        if (tab) {
-                            const double er = (double)(q * s) - (double)xv;
-                            return er * er;
-                        }
-                        return sweep_term(q, d, s, xv);
-                    };
+                    // (no list of the row's literal pairs, as the 4096-key kernel keeps: the row is read again)
+                    const SortLiteral<true> lt{V, nullptr, sort_type_grid(st, t), V.m(), nthr_t, s, usable ? V.lim() : 0.0f};
                     for (uint32_t vi = 0; vi < vpr; vi++) {
                         float xf[EPL];
                         IO<T>::unpack(xr[vi], xf);
@@ -1073,13 +1067,13 @@ k_search_sorted_short(const uint4 *__restrict__ x, uint32_t vpr, size_t rows, co
                             if (!(fabsf(a) < Lx) || !(fabsf(b) < Lx)) {      // a literal pair: the reference sequence with the pair rule
                                 float da, db;
                                 bool ta, tb;
-                                float qa = q_of(a, da, ta), qb = q_of(b, db, tb);
+                                float qa = lt.q_of(a, da, ta), qb = lt.q_of(b, db, tb);
                                 const bool me = fabsf(qa) > 32.0f, mo = fabsf(qb) > 32.0f;      // OQ:314
                                 const bool ve = mo && !me;
                                 qa = qa * (ve ? 0.0f : 1.0f);
                                 qb = qb * (me ? 0.0f : 1.0f);
-                                sum_l += term_of(qb, db, tb, b);
-                                sum_l += term_of(qa, da, ta, a);
+                                sum_l += lt.term_of(qb, db, tb, b);
+                                sum_l += lt.term_of(qa, da, ta, a);
                             } else if (!cap_list) {
                                 sum_c += correction(sort_key(a), sort_key(b));
                             }
@@ -1089,24 +1083,13 @@ k_search_sorted_short(const uint4 *__restrict__ x, uint32_t vpr, size_t rows, co
                 sum += sum_c;
                 sum += sum_l;
             } else if (tot_lit) {
-                const float *grid = ty_grid(t);
-                const int gm = ty_m(t);
-                const float lim = usable ? ty_lim(t) : 0.0f;
+                const SortLiteral<true> lt{V, nullptr, sort_type_grid(st, t), V.m(), nthr_t, s, usable ? V.lim() : 0.0f};
                 double sum_l = 0.0;
                 auto lit_term = [&](float xv) {
-                    float d = xv / s;
-                    if (fabsf(d) < lim) {                     // a step-function element for THIS candidate: (O_J - x)^2 in double
-                        uint32_t lo = 0, hi = nthr_t;
-                        while (lo < hi) {                     // RN(x / s) >= T_k  <=>  x >= X_k: the cell from the grid-domain thresholds
-                            const uint32_t mid = (lo + hi) >> 1;
-                            if (d >= v[66u + mid]) lo = mid + 1u; else hi = mid;
-                        }
-                        const double er = (double)(v[lo] * s) - (double)xv;
-                        sum_l += er * er;
-                    } else {
-                        const float q = sort_literal_q(xv, s, v, grid, gm, d);
-                        sum_l += sweep_term(q, d, s, xv);
-                    }
+                    float d;
+                    bool tab;
+                    const float q = lt.q_of(xv, d, tab);
+                    sum_l += lt.term_of(q, d, tab, xv);
                 };
                 if (lit_list) {
                     for (uint32_t i = 0; i < tot_lit; i++) lit_term(sL[i]);

@@ -32,6 +32,7 @@
 #define ANTQ_K_SWEEP_H
 
 #include "antq_device.h"
+#include "antq_k_cliptype.h"
 #include "antq_k_fakequant.h"
 #include "antq_k_search.h"
 
@@ -41,48 +42,10 @@ constexpr int kSweepMaxThr = 64;
 constexpr int kSweepMaxCand = 128;
 constexpr int kSweepRep = 4;             // replicas of the static histogram (lane & 3): a quarter of the same-address conflicts
 
-struct SweepType {
-    const uint4 *tlist;      // device: HThr[n_thr]
-    const float *grid;       // device: the codebook in scan order (literal path)
-    uint32_t n_thr, m;
-    float gmax, lim;         // lim: |x / s| below this -> the step function is the whole story (HArgs::lim)
-    int kout_pos, kout_neg;  // OliVe: the threshold between the last normal value and the first outlier, per sign (-1: none)
-};
-
 __host__ __device__ inline size_t sweep_lds_bytes(uint32_t nthr, uint32_t cp)
 {
     // sEs[nthr * cp] (i64) sHs[4][66] (i64) | sX[nthr * cp] (float) sEn[nthr * cp] (i32) sHn[4][66] (u32) sS[cp] sT[64] sV[66]
     return 8 * ((size_t)nthr * cp + 66 * kSweepRep) + 4 * (2 * (size_t)nthr * cp + 66 * kSweepRep + (size_t)cp + 64 + 66);
-}
-
-// the reference sequence for one element at one scale (quant_kernel.cu:25-37 scan, AQ:541-549): q before any pair rule
-__device__ __forceinline__ float sweep_literal_q(float xv, float s, const float *__restrict__ grid, int m, float &d)
-{
-    d = xv / s;
-    float sub_min = 102400.0f, z_min = 0.0f;
-#pragma unroll 1
-    for (int i = 0; i < m; i++) {
-        const float g = grid[i];
-        const float sub_v = fabsf(d - g);
-        if (sub_v <= sub_min) { sub_min = sub_v; z_min = g; }
-    }
-    return z_min;
-}
-__device__ __forceinline__ double sweep_term(float q, float d, float s, float xv)
-{
-    const float tt = (q - d) + d;
-    const float df = fabsf(tt * s - xv);
-    // widened BEFORE squaring: a literal element's term is as exact as the closed form's terms around it (squared in float, a
-    // far-clipped element -- the largest term of its row -- carried a 2^-24 rounding into the row's sum, and 1e30 gave Inf)
-    return (double)df * (double)df;
-}
-
-// x in fixed point, units of 2^(ex - 38), as a 64-bit integer: |x| < 2^(ex + 8) -> |x * F| < 2^46, so adding 1.5 * 2^52 leaves
-// rint(x * F) in the low 52 bits of the double (round to nearest even: one fixed rule -- every run forms the same integer)
-__device__ __forceinline__ long long sweep_fixed(float xv, double F)
-{
-    const double d = (double)xv * F + 6755399441055744.0;
-    return (long long)(__double_as_longlong(d) & 0x000fffffffffffffll) - 0x0008000000000000ll;
 }
 
 // cells of a per-tensor workgroup slab (64-bit each): Es, En, Hs[66], Hn[66] | doubles: Q, exc[128]
@@ -162,7 +125,7 @@ __device__ __forceinline__ void sweep_finish(uint32_t lane, uint32_t nthr, uint3
 template <typename T, bool OVP, bool PT = false>
 __global__ void __launch_bounds__(64)
 k_search_sweep(const uint4 *__restrict__ x, size_t vpr, size_t rows, const float *__restrict__ xmax,
-               const float *__restrict__ ratios, double *__restrict__ sse, SweepType ty, uint32_t ncand, uint32_t cp,
+               const float *__restrict__ ratios, double *__restrict__ sse, ClipType ty, uint32_t ncand, uint32_t cp,
                long long *__restrict__ pt_slabs = nullptr, int fbits = 38)
 {
     constexpr int EPL = IO<T>::EPL;
@@ -262,7 +225,7 @@ k_search_sweep(const uint4 *__restrict__ x, size_t vpr, size_t rows, const float
                 }
                 return sV[lo];
             }
-            return sweep_literal_q(xv, sc_, ty.grid, (int)ty.m, d);
+            return clip_literal_q(xv, sc_, ty.grid, (int)ty.m, d);
         };
         // G elements of one lane side by side
         auto group = [&](const float (&xf)[G], bool live) {
@@ -303,7 +266,7 @@ k_search_sweep(const uint4 *__restrict__ x, size_t vpr, size_t rows, const float
                 const bool reg = reg0 && xv != 0.0f;
                 zeros += (uint32_t)__builtin_popcountll(__ballot(reg0 && xv == 0.0f));
                 Q = __builtin_fma((double)xv, (double)xv, Q);
-                xi[e] = sweep_fixed(xv, F);
+                xi[e] = clip_fixed(xv, F);
                 if (reg) {
                     atomicAdd(&myHn[J0[e]], 1u);
                     atomicAdd(reinterpret_cast<unsigned long long *>(&myHs[J0[e]]), (unsigned long long)xi[e]);
@@ -394,8 +357,8 @@ k_search_sweep(const uint4 *__restrict__ x, size_t vpr, size_t rows, const float
                                 qa = qa * (ve ? 0.0f : 1.0f);
                                 qb = qb * (me ? 0.0f : 1.0f);
                             }
-                            double term = sweep_term(qa, da, s, xa_);
-                            if (OVP) term += sweep_term(qb, db, s, xb_);
+                            double term = clip_literal_term(qa, da, s, xa_);
+                            if (OVP) term += clip_literal_term(qb, db, s, xb_);
                             if (h) exc1 += term; else exc0 += term;
                         }
                     }
@@ -475,7 +438,7 @@ k_sweep_pt_total(const long long *__restrict__ slabs, uint32_t nslab, uint32_t p
 
 static __global__ void __launch_bounds__(64)
 k_sweep_pt_finish(const long long *__restrict__ tot, const float *__restrict__ xmax, const float *__restrict__ ratios,
-                  double *__restrict__ sse, SweepType ty, uint32_t ncand, uint32_t cp, int fbits)
+                  double *__restrict__ sse, ClipType ty, uint32_t ncand, uint32_t cp, int fbits)
 {
     extern __shared__ __attribute__((aligned(16))) uint4 smem[];
     const uint32_t lane = threadIdx.x, nthr = ty.n_thr, cells = nthr * cp;

@@ -10,6 +10,7 @@
 #include "antq_k_fakequant.h"
 #include "antq_k_search.h"
 #include "antq_k_hist.h"
+#include "antq_k_cliptype.h"
 #include "antq_k_sweep.h"
 #include "antq_k_sortsearch.h"
 
@@ -177,6 +178,33 @@ static SearchGrid search_grid(size_t units, size_t unit_work, bool pt, int n, in
     return best;
 }
 
+// ---- a codebook's descriptor for the step-function searches (antq_k_cliptype.h), from its plan ---------------------------
+// nneg (may be null): the thresholds below zero.  false: a threshold list the kernels' searches cannot take (not ascending, or
+// more than one threshold between the normal values and the outliers of a sign); the caller has checked the plan's kind
+// (sweep_type_ok / sort_type_ok).
+static bool fill_clip_type(ClipType &ty, uint32_t *nneg, const void *plan_host, const void *plan_dev, float gmax)
+{
+    const PlanHeader *ph = static_cast<const PlanHeader *>(plan_host);
+    const HThr *tl = plan_tlist(plan_host);
+    ty.tlist = reinterpret_cast<const uint4 *>(static_cast<const char *>(plan_dev) + ph->tlist_off);
+    ty.grid = reinterpret_cast<const float *>(plan_tab_ptr(plan_dev));
+    ty.n_thr = ph->h_nthr;
+    ty.m = ph->m;
+    ty.gmax = gmax;
+    const float flim = ph->fastlim * 0.99999f;
+    ty.lim = flim < ph->xlim ? flim : ph->xlim;
+    ty.kout_pos = ty.kout_neg = -1;
+    if (nneg) *nneg = 0;
+    for (uint32_t k = 0; k < ph->h_nthr; k++) {
+        const bool lo_out = (tl[k].flags & 1u) != 0u, hi_out = (tl[k].flags & 2u) != 0u;
+        if (k > 0 && !(tl[k].T > tl[k - 1].T)) return false;                     // (ascending: what the kernels' searches assume)
+        if (nneg && tl[k].T < 0.0f) *nneg = k + 1u;
+        if (!lo_out && hi_out) { if (ty.kout_pos >= 0 || !(tl[k].T > 0.0f)) return false; ty.kout_pos = (int)k; }
+        if (lo_out && !hi_out) { if (ty.kout_neg >= 0 || !(tl[k].T < 0.0f)) return false; ty.kout_neg = (int)k; }
+    }
+    return true;
+}
+
 // ---- the threshold sweep (antq_k_sweep.h): per-row scales, every codebook with a threshold list ------------------------
 // ANTQ_ERR_UNSUPPORTED: not this launch (the caller goes on to the direct kernels).  Where it is taken (knob 19 = 1, the
 // default): rows of 2048 .. 65536 elements and codebooks of at most 20 thresholds.  Measured, 70 candidates x 3 ANT codebooks
@@ -208,31 +236,15 @@ static int launch_sweep(const void *x, size_t rows, size_t row_len, const float 
 {
     constexpr int EPL = IO<T>::EPL;
     if (!sweep_shape_ok<T, OVP>(x, rows, row_len, ncand, ntypes)) return ANTQ_ERR_UNSUPPORTED;
-    SweepType ty[kMaxTypes];
+    ClipType ty[kMaxTypes];
     memset(ty, 0, sizeof(ty));
     // candidate lists longer than the kernel's tables (128) go out in pieces: a candidate's sums are formed from exact integer
     // counts, so they do not depend on which other candidates share its launch (as long as no element changes between the
     // step-function and the literal class, which the smallest scale of the piece decides)
     const uint32_t cp_max = (uint32_t)std::min(ncand, kSweepMaxCand) + 1u;
     for (int t = 0; t < ntypes; t++) {
-        const PlanHeader *ph = static_cast<const PlanHeader *>(plan_host[t]);
-        if (!sweep_type_ok(plan_host[t], gmax[t])) return ANTQ_ERR_UNSUPPORTED;
-        const HThr *tl = plan_tlist(plan_host[t]);
-        ty[t].tlist = reinterpret_cast<const uint4 *>(static_cast<const char *>(plan_dev[t]) + ph->tlist_off);
-        ty[t].grid = reinterpret_cast<const float *>(plan_tab_ptr(plan_dev[t]));
-        ty[t].n_thr = ph->h_nthr;
-        ty[t].m = ph->m;
-        ty[t].gmax = gmax[t];
-        const float flim = ph->fastlim * 0.99999f;
-        ty[t].lim = flim < ph->xlim ? flim : ph->xlim;
-        ty[t].kout_pos = ty[t].kout_neg = -1;
-        for (uint32_t k = 0; k < ph->h_nthr; k++) {
-            const bool lo_out = (tl[k].flags & 1u) != 0u, hi_out = (tl[k].flags & 2u) != 0u;
-            if (k > 0 && !(tl[k].T > tl[k - 1].T)) return ANTQ_ERR_UNSUPPORTED;                   // (ascending: what the kernel's searches assume)
-            if (!lo_out && hi_out) { if (ty[t].kout_pos >= 0 || !(tl[k].T > 0.0f)) return ANTQ_ERR_UNSUPPORTED; ty[t].kout_pos = (int)k; }
-            if (lo_out && !hi_out) { if (ty[t].kout_neg >= 0 || !(tl[k].T < 0.0f)) return ANTQ_ERR_UNSUPPORTED; ty[t].kout_neg = (int)k; }
-        }
-        if (sweep_lds_bytes(ph->h_nthr, cp_max) > 64 * 1024) return ANTQ_ERR_UNSUPPORTED;
+        if (!sweep_type_ok(plan_host[t], gmax[t]) || !fill_clip_type(ty[t], nullptr, plan_host[t], plan_dev[t], gmax[t])) return ANTQ_ERR_UNSUPPORTED;
+        if (sweep_lds_bytes(ty[t].n_thr, cp_max) > 64 * 1024) return ANTQ_ERR_UNSUPPORTED;
     }
     const unsigned blocks = (unsigned)std::min<size_t>(rows, (size_t)1 << 20);
     for (int t = 0; t < ntypes; t++)             // one codebook per launch: [ncand][rows] doubles each
@@ -261,30 +273,14 @@ static int launch_sweep_pt(const void *x, size_t n, const float *xmax, const flo
 {
     constexpr int EPL = IO<T>::EPL;
     if (!sweep_pt_shape_ok<T>(x, n, ncand) || ntypes < 1 || ntypes > kMaxTypes || !ws || (OVP && g_knob_sweep != 2)) return ANTQ_ERR_UNSUPPORTED;
-    SweepType ty[kMaxTypes];
+    ClipType ty[kMaxTypes];
     memset(ty, 0, sizeof(ty));
     const uint32_t cp = (uint32_t)ncand + 1u;
     uint32_t cells_max = 0;
     for (int t = 0; t < ntypes; t++) {
-        const PlanHeader *ph = static_cast<const PlanHeader *>(plan_host[t]);
-        if (!sweep_type_ok(plan_host[t], gmax[t])) return ANTQ_ERR_UNSUPPORTED;
-        const HThr *tl = plan_tlist(plan_host[t]);
-        ty[t].tlist = reinterpret_cast<const uint4 *>(static_cast<const char *>(plan_dev[t]) + ph->tlist_off);
-        ty[t].grid = reinterpret_cast<const float *>(plan_tab_ptr(plan_dev[t]));
-        ty[t].n_thr = ph->h_nthr;
-        ty[t].m = ph->m;
-        ty[t].gmax = gmax[t];
-        const float flim = ph->fastlim * 0.99999f;
-        ty[t].lim = flim < ph->xlim ? flim : ph->xlim;
-        ty[t].kout_pos = ty[t].kout_neg = -1;
-        for (uint32_t k = 0; k < ph->h_nthr; k++) {
-            const bool lo_out = (tl[k].flags & 1u) != 0u, hi_out = (tl[k].flags & 2u) != 0u;
-            if (k > 0 && !(tl[k].T > tl[k - 1].T)) return ANTQ_ERR_UNSUPPORTED;
-            if (!lo_out && hi_out) { if (ty[t].kout_pos >= 0 || !(tl[k].T > 0.0f)) return ANTQ_ERR_UNSUPPORTED; ty[t].kout_pos = (int)k; }
-            if (lo_out && !hi_out) { if (ty[t].kout_neg >= 0 || !(tl[k].T < 0.0f)) return ANTQ_ERR_UNSUPPORTED; ty[t].kout_neg = (int)k; }
-        }
-        if (sweep_lds_bytes(ph->h_nthr, cp) > 64 * 1024) return ANTQ_ERR_UNSUPPORTED;
-        cells_max = std::max(cells_max, sweep_slab_cells(ph->h_nthr, cp));
+        if (!sweep_type_ok(plan_host[t], gmax[t]) || !fill_clip_type(ty[t], nullptr, plan_host[t], plan_dev[t], gmax[t])) return ANTQ_ERR_UNSUPPORTED;
+        if (sweep_lds_bytes(ty[t].n_thr, cp) > 64 * 1024) return ANTQ_ERR_UNSUPPORTED;
+        cells_max = std::max(cells_max, sweep_slab_cells(ty[t].n_thr, cp));
     }
     const size_t nv = n / EPL;
     const size_t ws_bytes = antq_search_workspace_bytes();
@@ -327,27 +323,8 @@ static bool sort_fill_types(SortTypes &stt, int ntypes, const float *gmax, const
     stt.ntypes = ntypes;
     uint32_t nmax = 0;
     for (int t = 0; t < ntypes; t++) {
-        if (!sort_type_ok(plan_host[t], gmax[t])) return false;
-        const PlanHeader *ph = static_cast<const PlanHeader *>(plan_host[t]);
-        const HThr *tl = plan_tlist(plan_host[t]);
-        SweepType &ty = stt.ty[t];
-        ty.tlist = reinterpret_cast<const uint4 *>(static_cast<const char *>(plan_dev[t]) + ph->tlist_off);
-        ty.grid = reinterpret_cast<const float *>(plan_tab_ptr(plan_dev[t]));
-        ty.n_thr = ph->h_nthr;
-        ty.m = ph->m;
-        ty.gmax = gmax[t];
-        const float flim = ph->fastlim * 0.99999f;
-        ty.lim = flim < ph->xlim ? flim : ph->xlim;
-        ty.kout_pos = ty.kout_neg = -1;
-        stt.nneg[t] = 0;
-        for (uint32_t k = 0; k < ph->h_nthr; k++) {
-            const bool lo_out = (tl[k].flags & 1u) != 0u, hi_out = (tl[k].flags & 2u) != 0u;
-            if (k > 0 && !(tl[k].T > tl[k - 1].T)) return false;                     // (ascending: what the kernel's searches assume)
-            if (tl[k].T < 0.0f) stt.nneg[t] = k + 1u;
-            if (!lo_out && hi_out) { if (ty.kout_pos >= 0 || !(tl[k].T > 0.0f)) return false; ty.kout_pos = (int)k; }
-            if (lo_out && !hi_out) { if (ty.kout_neg >= 0 || !(tl[k].T < 0.0f)) return false; ty.kout_neg = (int)k; }
-        }
-        nmax = std::max(nmax, ph->h_nthr);
+        if (!sort_type_ok(plan_host[t], gmax[t]) || !fill_clip_type(stt.ty[t], &stt.nneg[t], plan_host[t], plan_dev[t], gmax[t])) return false;
+        nmax = std::max(nmax, stt.ty[t].n_thr);
     }
     stt.nthr_pad = (nmax + (uint32_t)kSortKS - 1u) / (uint32_t)kSortKS * (uint32_t)kSortKS;
     return true;
