@@ -58,9 +58,10 @@ def lib():
                              "antq_search_pick", "antq_alpha_grad", "antq_nearest_plan", "antq_nearest_hinted",
                              "antq_search_sse_multi", "antq_plan_eval_host_a", "antq_moments", "antq_xmax_3sigma",
                              "antq_calibrate", "antq_prefetch_kernels", "antq_plan_eval_host_h", "antq_calibrate_batch", "antq_absmax_into", "antq_fakequant_f64",
-                             "antq_absmax_t", "antq_alpha_grad_t", "antq_calibrate_install"):
+                             "antq_absmax_t", "antq_alpha_grad_t", "antq_calibrate_install", "antq_decode4_batch_build", "antq_decode4_batch"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
+                L.antq_decode4_batch_capacity.restype = ctypes.c_size_t
                 L.antq_search_workspace_bytes.restype = ctypes.c_size_t
                 L.antq_calibrate_workspace_bytes.restype = ctypes.c_size_t
                 L.antq_calibrate_batch_workspace_bytes.restype = ctypes.c_size_t
@@ -284,6 +285,14 @@ class Plan:
             t = torch.from_numpy(self.host).to(device)
             self._dev[key] = t
             self._dev_ptr[key] = t.data_ptr()
+        return t
+
+    def grid_dev(self, device):
+        """The grid itself (scan order, float32) on `device`: what antq_decode4_batch takes instead of a plan."""
+        key = ("grid", device.index if device.index is not None else torch.cuda.current_device())
+        t = self._dev.get(key)
+        if t is None:
+            t = self._dev[key] = torch.from_numpy(self.grid).to(device)
         return t
 
     def eval_host(self, d):
@@ -1003,3 +1012,63 @@ class Batch:
                     out.append(("antq::k_fq_batch_dyn16<%s,%s>" % (t, o), fam[4]))
         out += [("antq_fakequant (own launch)", 0)] * len(self.singles)
         return out
+
+
+# ---------------------------------------------------------------------------------
+# batched decode: many packed tensors, one kernel
+# ---------------------------------------------------------------------------------
+class _DecodeJob(ctypes.Structure):          # include/antq.h: antq_decode_job
+    _fields_ = [("codes_dev", ctypes.c_void_p), ("out_dev", ctypes.c_void_p), ("alpha_dev", ctypes.c_void_p),
+                ("rows", ctypes.c_size_t), ("row_len", ctypes.c_size_t), ("alpha_per_row", ctypes.c_int),
+                ("gmax", ctypes.c_float), ("grid_dev", ctypes.c_void_p), ("m", ctypes.c_int), ("n_normal", ctypes.c_int)]
+
+
+class DecodeBatch:
+    """The fake-quant images of many packed 4-bit tensors in ONE launch (antq_decode4_batch), the counterpart of Batch.
+
+    jobs: iterable of tuples (codes, out, alpha, plan, gmax, rows, row_len, per_row, n_normal); codes uint8 of
+    rows * row_len / 2 bytes, alpha float32, all tensors on one device, every `out` of one dtype (float32 / bfloat16 /
+    float16).  ovp: OliVe's pair rule for every job (n_normal is read only then).  Each job has its own codebook.  Jobs
+    with unaligned buffers ride in the same launch.  The descriptor table is built once and stays resident."""
+
+    def __init__(self, jobs, ovp=False):
+        jobs = [tuple(j) for j in jobs]
+        if not jobs:
+            raise AntqError("empty batch")
+        o0 = jobs[0][1]
+        _require_gpu(o0, "out")
+        dt = _DTYPES.get(o0.dtype)
+        if dt is None or dt == F64:
+            raise AntqError("unsupported dtype %s" % o0.dtype)
+        self.device, self.dtype, self.ovp = o0.device, dt, bool(ovp)
+        self._keep = jobs                       # keeps tensors and plans alive
+        arr = (_DecodeJob * len(jobs))()
+        for k, (codes, out, alpha, plan, gmax, rows, row_len, per_row, n_normal) in enumerate(jobs):
+            for t, name in ((codes, "codes"), (out, "out"), (alpha, "alpha")):
+                _require_gpu(t, name)
+                if t.device != self.device:
+                    raise AntqError("every tensor of a batch must live on one device")
+            if out.dtype != o0.dtype:
+                raise AntqError("every out of a decode batch must have one dtype")
+            if codes.dtype != torch.uint8 or codes.numel() * 2 != rows * row_len or out.numel() != rows * row_len:
+                raise AntqError("codes must be uint8 of rows*row_len/2 bytes, out rows*row_len elements")
+            if alpha.dtype != torch.float32 or alpha.numel() < (rows if per_row else 1):
+                raise AntqError("alpha must be float32, one per row (per_row) or one")
+            arr[k] = _DecodeJob(codes.data_ptr(), out.data_ptr(), alpha.data_ptr(), rows, row_len, 1 if per_row else 0, gmax,
+                                plan.grid_dev(self.device).data_ptr(), plan.grid.size, n_normal)
+        flags = FLAG_OVP if ovp else 0
+        cap = lib().antq_decode4_batch_capacity(arr, len(jobs), self.dtype)
+        host = np.zeros(max(cap, 1), dtype=np.uint8)
+        n = lib().antq_decode4_batch_build(arr, len(jobs), self.dtype, ctypes.c_uint(flags),
+                                           host.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(cap))
+        if n <= 0:
+            _check(n if n < 0 else -1, "antq_decode4_batch_build")
+        self.host = host[:n].copy()
+        self.dev = torch.from_numpy(self.host).to(self.device)
+
+    def run(self):
+        with _on_device(self.device):
+            rc = lib().antq_decode4_batch(ctypes.c_void_p(self.host.ctypes.data), ctypes.c_void_p(self.dev.data_ptr()),
+                                          ctypes.c_void_p(_stream_int(self.device)))
+        if rc:
+            _check(rc, "antq_decode4_batch")

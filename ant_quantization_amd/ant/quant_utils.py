@@ -6,6 +6,7 @@ import torch  # noqa: F401
 
 from .._utils import (get_ckpt_filename, get_ckpt_path, get_model, logger, make_set_weights_at_rest, set_weight_bank,  # noqa: F401
                       make_walkers, set_util_logging, tag_info)
+from ..packed import load_packed_state_dict, pack_model, packed_state_dict  # noqa: F401  (ours: 4-bit weights as codes)
 from .quant_modules import Quantizer as Q
 
 quant_args = {}

@@ -3,6 +3,7 @@
 #include "antq_host.h"
 #include "antq_dispatch.h"
 #include "antq_k_batch.h"
+#include "antq_k_decbatch.h"
 
 #include <type_traits>
 
@@ -359,6 +360,25 @@ extern "C" int antq_fakequant_batch(const void *batch_host, const void *batch_de
     hipStream_t st = static_cast<hipStream_t>(stream);
     return with_dtype((int)h->dtype, [&](auto tag) {
         return with_bool((h->flags & ANTQ_FLAG_OVP) != 0, [&](auto ovp) { return launch_batch<decltype(tag), decltype(ovp)::value>(h, descs, fmap, st); });
+    });
+}
+
+// The batched packed-4-bit decoder (antq_k_decbatch.h); the blob comes from antq_decode4_batch_build (antq_plan.cpp: pure host).
+extern "C" int antq_decode4_batch(const void *batch_host, const void *batch_dev, void *stream)
+{
+    if (!batch_host || !batch_dev) return ANTQ_ERR_ARG;
+    const DecHeader *h = static_cast<const DecHeader *>(batch_host);
+    if (h->magic != kDecMagic) return ANTQ_ERR_PLAN;
+    if (h->total_blocks == 0) return ANTQ_OK;
+    const char *pd = static_cast<const char *>(batch_dev);
+    const DecDesc *descs = reinterpret_cast<const DecDesc *>(pd + sizeof(DecHeader));
+    const uint32_t *map = reinterpret_cast<const uint32_t *>(pd + h->map_offset);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return with_dtype((int)h->dtype, [&](auto tag) {
+        return with_bool((h->flags & ANTQ_FLAG_OVP) != 0, [&](auto ovp) {
+            hipLaunchKernelGGL((k_decode4_batch<decltype(tag), decltype(ovp)::value>), dim3(h->total_blocks * 4u), dim3(64u), 0, st, descs, map);
+            return launch_status();
+        });
     });
 }
 

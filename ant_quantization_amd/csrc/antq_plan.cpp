@@ -27,6 +27,7 @@
 
 #include "../../include/antq.h"
 #include "antq_internal.h"
+#include "antq_decbatch.h"
 
 namespace antq {
 namespace {
@@ -818,4 +819,17 @@ extern "C" int antq_plan_eval_host_h(const void *blob, const uint16_t *x16, size
         for (size_t i = b; i < e1; i++) { out16[i] = (uint16_t)o[i - b]; if (path) path[i] = pth[i - b]; }
     }
     return ANTQ_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// The batched packed-4-bit decoder's descriptor blob (antq_decbatch.h): pure host, like everything in this file.
+// ------------------------------------------------------------------------------------
+extern "C" size_t antq_decode4_batch_capacity(const antq_decode_job *jobs, int n, int dtype)
+{
+    return antq::dec_batch_capacity(jobs, n, dtype);
+}
+
+extern "C" int antq_decode4_batch_build(const antq_decode_job *jobs, int n, int dtype, unsigned flags, void *batch_host, size_t capacity)
+{
+    return antq::dec_batch_build(jobs, n, dtype, flags, batch_host, capacity);
 }

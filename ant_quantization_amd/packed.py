@@ -1,0 +1,286 @@
+"""Packed 4-bit weights: a calibrated model whose weights exist as codes (SURVEY 8f N4 at the module surface).
+
+`antq_encode4` turns a calibrated weight into the quantised tensor itself -- two codes per byte, OliVe's identifier 15 for
+the victim of a pair -- and `decode4(encode4(w))` is bit-identical to the fake-quantised weight the layer computes on every
+forward under the condition include/antq.h states for the codec: finite, positive scales and |w / scale| within twice the
+outermost grid value (elements beyond the scan's range encode as 0).  Calibration gives that: alpha is a clip ratio of at
+least 0.5 times the row's abs-max (w_low / a_low are 75 by default).  A channel whose alpha is 0 or not finite, or a clip
+window below 50 %, can make a packed layer differ from its fake-quant twin in the clipped elements.  `PackedBank(model)` keeps those codes instead of re-quantising: it takes the place of `weight_bank.WeightBank`
+behind the same `q._bank` / `lookup()` protocol of `tensor_forward`, encodes every suitable weight once, and produces the
+decoded images with ONE `antq_decode4_batch` launch per (device, dtype, pair rule) group.  Codes are frozen weights by
+definition, so the schedule is resident: the images are decoded at construction, again after `.to()` / `.half()` moved or
+retyped the buffers, and on `invalidate()`; a forward on an unchanged model launches nothing for packed layers.
+
+Suitable = a steady-state quantiser whose codebook and row length the 4-bit codec accepts.  Everything else -- 8-bit layers
+(`set_8_bit_layer_n/_l`), rows that are no multiple of 8 elements (conv1: K = 147), OliVe's unsigned codebook of 16 normal
+values (no code left for the identifier), `base` / `outlier` modes, float64 -- keeps its float weight and its per-layer
+fake-quant launch, and is listed in `.skipped` with the reason, as WeightBank does.
+
+A forward that wants gradients through a packed quantiser raises AntqError: there is no float weight to train.
+
+`release_weights=True` points each packed layer's `weight.data` at the bank's decoded buffer, so the float original is
+freed: a packed layer then holds codes + one quantised copy instead of weight + quantised copy.  `state_dict()` of such a
+model holds FAKE-QUANTISED weights, not the originals; `packed_state_dict(model)` is the checkpoint to write.
+
+The scale a layer is decoded with is the quantiser's `alpha` as it is when the images are decoded (read as float32).
+
+Checkpoint: `packed_state_dict(model)` = the quantiser state the reference's checkpoints already carry (same keys) plus
+`<layer>.quant_weight.codes` (uint8, numel / 2 bytes) for packed layers and `<layer>.weight` only for skipped ones;
+`load_packed_state_dict(model, sd)` loads it into a freshly wrapped, uncalibrated model without re-encoding.
+"""
+import torch
+
+from . import _lib
+from ._model import load_ant_state_dict
+from .weight_bank import _weight_layers
+
+__all__ = ["PackedBank", "pack_model", "packed_state_dict", "load_packed_state_dict"]
+
+CODES_KEY = "quant_weight.codes"
+
+
+def _codebook(q):
+    """(plan, gmax, n_normal, ovp) of a steady-state quantiser as the codec takes them."""
+    plan = q._ensure_plan()
+    ovp = getattr(q, "_no_outlier", True) is False
+    return plan, float(q._gmax), (int(q.quant_grid.numel()) if ovp else 0), ovp
+
+
+def _settle(q):
+    """A quantiser whose state came from a checkpoint: learn on the host what its first forward would (one read-back)."""
+    q._hm_get('bit')
+    if q._hm_get('has_inited_quant_para') != 0:
+        q._ensure_plan()
+        q._steady = True
+
+
+class PackedBank:
+    def __init__(self, model, release_weights=False, codes=None):
+        """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict)."""
+        self.model = model
+        self.release_weights = bool(release_weights)
+        self.entries = {}          # id(quantiser) -> dict
+        self.skipped = []          # (layer name, reason): layers that keep their float weight and per-layer launch
+        self.launches = 0          # decode launches so far (one per (device, dtype, pair rule) group and refresh)
+        self.dirty = True
+        self._batches = []
+        self._ptr_key = None
+        try:
+            for name, mod, q, w in _weight_layers(model):
+                reason = self._unsuitable(q, w)
+                if reason is None and codes is not None and name not in codes:
+                    reason = "no codes in the checkpoint"
+                if reason:
+                    if codes is not None and name in codes:
+                        raise _lib.AntqError("PackedBank: stored codes for layer %s, which cannot be packed (%s)" % (name, reason))
+                    self.skipped.append((name, reason))
+                    continue
+                per_row = bool(q.is_perchannel)
+                rows, row_len = (w.shape[0], w.numel() // w.shape[0]) if per_row else (1, w.numel())
+                plan, gmax, n_normal, ovp = _codebook(q)
+                if codes is not None:
+                    c = codes[name].to(w.device).contiguous()
+                    if c.dtype != torch.uint8 or c.numel() * 2 != w.numel():
+                        raise _lib.AntqError("PackedBank: codes of layer %s must be uint8 of numel/2 bytes" % name)
+                else:
+                    with torch.no_grad():
+                        alpha = q.alpha.detach().reshape(-1).to(torch.float32).contiguous()
+                        c = _lib.encode4(w.detach(), alpha, plan, gmax, rows, row_len, per_row, n_normal=n_normal, ovp=ovp)
+                self.entries[id(q)] = dict(name=name, q=q, mod=mod, rows=rows, row_len=row_len, per_row=per_row, codes=c,
+                                           out=torch.empty_like(w, memory_format=torch.contiguous_format))
+            if not self.entries:
+                raise _lib.AntqError("PackedBank: no weight quantiser to pack (run one forward to calibrate first): %r" % (self.skipped,))
+            for e in self.entries.values():
+                old = e["q"]._bank
+                if old is not None and old is not self:
+                    old.detach()
+                e["q"]._bank = self
+            self.refresh()
+        except BaseException:      # (out of memory half way through: leave nothing attached)
+            self.detach()
+            raise
+        _no_auto_bank(model)
+
+    def __deepcopy__(self, memo):       # (a copy of the model starts without a bank, like WeightBank's)
+        return None
+
+    def __reduce__(self):
+        return (type(None), ())
+
+    @staticmethod
+    def _unsuitable(q, w):
+        """Why this layer stays float (None: it can be packed).  What the codec refuses comes first, where the weight lives
+        last: the answer for a model's layers is the same before and after it moved to the GPU."""
+        if q.mode in ("base", "outlier"):
+            return "mode %s" % q.mode
+        if not (q.is_enable and q.is_enable_weight):
+            return "quantisation disabled"
+        if not q._steady:
+            return "not calibrated yet"
+        if w.dtype not in _lib._DTYPES or w.dtype == torch.float64:
+            return "dtype %s" % w.dtype
+        row_len = w.numel() // w.shape[0] if q.is_perchannel else w.numel()
+        if row_len == 0 or row_len % 8 != 0:
+            return "row length %d is not a multiple of 8" % row_len
+        plan, _, n_normal, ovp = _codebook(q)
+        m = int(plan.grid.size)
+        if ovp:
+            if n_normal > 15:
+                return "%d normal values leave no code for the pair identifier" % n_normal
+            if m - n_normal > 15:
+                return "%d outlier values (the 4-bit codec holds 15)" % (m - n_normal)
+        elif m > 16:
+            return "codebook of %d values (the 4-bit codec holds 16)" % m
+        if not w.is_cuda or not w.is_contiguous():
+            return "weight not resident / not contiguous"
+        return None
+
+    # ------------------------------------------------------------------ bookkeeping
+    def invalidate(self):
+        """The next lookup decodes every packed weight again (one launch per group)."""
+        self.dirty = True
+
+    mark_dirty = invalidate
+
+    def nbytes(self):
+        """(bytes of codes, bytes of decoded images)"""
+        return (sum(e["codes"].numel() for e in self.entries.values()),
+                sum(e["out"].numel() * e["out"].element_size() for e in self.entries.values()))
+
+    def detach(self):
+        for e in self.entries.values():
+            if e["q"]._bank is self:
+                e["q"]._bank = None
+        self.entries.clear()
+        self._batches = []
+
+    def _pointers(self):
+        return tuple((e["mod"].weight.dtype, e["mod"].weight.device, e["out"].data_ptr(), e["q"].alpha.data_ptr(), e["q"].alpha.dtype,
+                      id(e["q"]._ensure_plan()), e["q"]._gmax) for e in self.entries.values())
+
+    def _build(self):
+        """(Re)build the descriptor tables: one batch per (device, dtype, pair rule)."""
+        groups = {}
+        for e in self.entries.values():
+            q, w = e["q"], e["mod"].weight
+            if e["out"].dtype != w.dtype or e["out"].device != w.device:      # .half() / .to(device) since
+                e["out"] = torch.empty(w.shape, dtype=w.dtype, device=w.device)
+                e["codes"] = e["codes"].to(w.device)
+            plan, gmax, n_normal, ovp = _codebook(q)
+            alpha = q.alpha.detach().reshape(-1)
+            e["alpha32"] = None
+            if alpha.dtype != torch.float32 or not alpha.is_contiguous() or alpha.device != w.device:
+                # (a 16-bit model's alpha: the kernel reads a float32 copy, brought up to date in place at every refresh)
+                alpha = e["alpha32"] = alpha.to(device=w.device, dtype=torch.float32).contiguous()
+            groups.setdefault((w.device, w.dtype, ovp), []).append(
+                (e["codes"], e["out"], alpha, plan, gmax, e["rows"], e["row_len"], e["per_row"], n_normal))
+        self._batches = [_lib.DecodeBatch(jobs, ovp=ovp) for (_, _, ovp), jobs in groups.items()]
+        self._ptr_key = self._pointers()
+
+    # ------------------------------------------------------------------ the one launch
+    @torch.no_grad()
+    def refresh(self):
+        if not self._batches or self._ptr_key != self._pointers():
+            self._build()
+        else:
+            for e in self.entries.values():
+                if e["alpha32"] is not None:
+                    e["alpha32"].copy_(e["q"].alpha.detach().reshape(-1))
+        for b in self._batches:
+            b.run()
+            self.launches += 1
+        self.dirty = False
+        if self.release_weights:
+            for e in self.entries.values():
+                w = e["mod"].weight
+                if w.data_ptr() != e["out"].data_ptr():
+                    w.data = e["out"]        # the float original is freed; weight now IS the fake-quantised image
+
+    def lookup(self, q, tensor, training=None):
+        """Called from tensor_forward in steady state (the WeightBank protocol): the decoded image of this quantiser's
+        weight, or None when the call has to take the per-layer path (not this layer's weight, quantiser re-armed)."""
+        e = self.entries.get(id(q))
+        if e is None or tensor is not e["mod"].weight:
+            return None
+        if training is None:
+            training = torch.is_grad_enabled() and (tensor.requires_grad or q.alpha.requires_grad)
+        if training:
+            raise _lib.AntqError("layer %s is packed: its weight exists as 4-bit codes, there is no float weight to train "
+                                 "(run the forward under torch.no_grad())" % e["name"])
+        if not q._steady or not (q.is_enable and q.is_enable_weight):
+            return None
+        out = e["out"]
+        if self.dirty or out.dtype != tensor.dtype or out.device != tensor.device:
+            self.refresh()
+            out = e["out"]
+        return out
+
+
+def _no_auto_bank(model):
+    """The automatic weight bank steps aside (as for set_weights_at_rest(resident=False)), and the choice stays with the
+    module: a deep copy carries the mark, so its forward hook does not arm a fresh AutoBank for it."""
+    ab = getattr(model, "_antq_auto_bank", None)
+    if ab is not None:
+        ab.disable()
+    object.__setattr__(model, "_antq_no_auto_bank", True)
+
+
+def _bank_of(model):
+    for _, _, q, _ in _weight_layers(model):
+        if isinstance(q._bank, PackedBank):
+            return q._bank
+    return None
+
+
+def pack_model(model, release_weights=False):
+    """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
+    (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons."""
+    return PackedBank(model, release_weights=release_weights)
+
+
+def packed_state_dict(model):
+    """The checkpoint of a packed model: state_dict() without the packed layers' `.weight`, plus their codes."""
+    bank = _bank_of(model)
+    if bank is None:
+        raise _lib.AntqError("packed_state_dict: the model is not packed (pack_model first)")
+    return _packed_keys(model.state_dict(), {e["name"]: e["codes"] for e in bank.entries.values()})
+
+
+def _packed_keys(sd, codes):
+    """state_dict `sd` -> packed layout: `<layer>.weight` of every layer in `codes` leaves, `<layer>.quant_weight.codes` comes."""
+    sd = type(sd)(sd)
+    for name, c in codes.items():
+        prefix = name + "." if name else ""
+        sd.pop(prefix + "weight", None)
+        sd[prefix + CODES_KEY] = c
+    return sd
+
+
+def load_packed_state_dict(model, sd, release_weights=True):
+    """Load a packed checkpoint into a freshly wrapped, uncalibrated model living on the GPU: the quantiser state is
+    installed the way load_ant_state_dict + load_state_dict do (scales keep the dtype they were stored with), a PackedBank is attached from the stored codes without
+    re-encoding, and the weights are materialised by the batched decode (release_weights=False: copied into the layers'
+    own float weights instead of replacing them).  Returns the bank."""
+    suffix = "." + CODES_KEY
+    codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}
+    rest = {k: v for k, v in sd.items() if not k.endswith(suffix)}
+    load_ant_state_dict(model, rest)
+    missing, unexpected = model.load_state_dict(rest, strict=False)
+    want_missing = {(n + "." if n else "") + "weight" for n in codes}
+    if unexpected or set(missing) != want_missing:
+        raise _lib.AntqError("load_packed_state_dict: checkpoint and model disagree (missing %s, unexpected %s)"
+                             % (sorted(set(missing) ^ want_missing), sorted(unexpected)))
+    # load_state_dict copies INTO the Parameters, so a bf16 / f16 model would round the checkpoint's float32 scales to its own
+    # dtype (calibration leaves float32 alphas in such a model): install them as stored, the codes were made with those
+    for name, module in model.named_modules():
+        a = rest.get(name + ".alpha")
+        if a is not None and hasattr(module, "quant_grid") and module.alpha.dtype != a.dtype:
+            module.alpha.data = a.detach().clone().to(module.alpha.device)
+    for _, _, q, _ in _weight_layers(model):
+        _settle(q)
+    bank = PackedBank(model, release_weights=release_weights, codes=codes)
+    if not release_weights:
+        with torch.no_grad():
+            for e in bank.entries.values():
+                e["mod"].weight.data.copy_(e["out"])
+    return bank

@@ -421,16 +421,17 @@ class FlushHook:
 
     def __call__(self, module, inputs, output):
         auto = module.__dict__.get("_antq_auto_bank")
-        if auto is None:
-            try:
+        if auto is None and not module.__dict__.get("_antq_no_auto_bank"):   # (the mark: packed.pack_model chose for this
+            try:                                                               #  module and its copies: no automatic bank)
                 auto = AutoBank(module)
                 object.__setattr__(module, "_antq_auto_bank", auto)
             except Exception:          # noqa: BLE001  (exotic containers: the per-layer schedule simply stays)
                 return
-        if auto.queue:
-            auto.flush()
-        if auto.bank is not None and not auto.bank.resident:
-            auto.bank.dirty = True
+        if auto is not None:
+            if auto.queue:
+                auto.flush()
+            if auto.bank is not None and not auto.bank.resident:
+                auto.bank.dirty = True
         from . import core
         if core.search_memo.entries:
             core.search_memo.clear()       # (shared activations are shared within ONE forward: nothing outlives it)

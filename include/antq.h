@@ -42,6 +42,8 @@ extern "C" {
  * antq_prefetch_kernels added.  5: antq_calibrate_batch / antq_calibrate_batch_workspace_bytes and antq_absmax_into added (nothing else changed).
  * 7 (round 6): antq_absmax_t / antq_alpha_grad_t (whole-tensor reductions in ONE launch through a caller-owned ticket block,
  * ANTQ_REDUCE_WS_BYTES) and antq_calibrate_install added (nothing else changed).
+ * Still 7: antq_decode4_batch_capacity / antq_decode4_batch_build / antq_decode4_batch added (the batched packed decoder; nothing
+ * that existed changed, so callers built against 7 keep working).
  * A caller built against another version must not call in: the blobs / argument lists differ. */
 #define ANTQ_ABI_VERSION 7
 
@@ -431,6 +433,40 @@ int antq_decode4(const uint8_t *codes_dev, void *out_dev, size_t rows, size_t ro
                  const float *alpha_dev, int alpha_per_row, float gmax,
                  const void *plan_host, const void *plan_dev, int n_normal,
                  unsigned flags, int dtype, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Batched decode: many packed tensors (the 54 weights of a ResNet-50, the row blocks of an LLM) -> their fake-quant images
+ * in ONE launch, the decode-side counterpart of antq_fakequant_batch.  Job i's output is bit-identical to antq_decode4 on
+ * that job alone: fl((g[c] + 0.0f) * (alpha / gmax)) with the pair rule above, bf16 / f16 rounded to nearest even.
+ *   antq_decode4_batch_build : pure host code, touches no HIP; writes the descriptor blob (returns its size in bytes).  All
+ *                      jobs share dtype (F32 / BF16 / F16) and flags (0 or ANTQ_FLAG_OVP); every job has its own
+ *                      codebook.  The codebook is passed as grid_dev -- m floats on the device, the grid in the order a
+ *                      plan is built from (ANT: the sorted grid; OliVe: cat(normal, outliers)) -- not as a plan: the
+ *                      decoder needs nothing else of a plan, and the builder stays free of the plan format.
+ *                      1 <= n <= 65535 jobs (capacity returns 0, build ANTQ_ERR_ARG otherwise); a flag bit other than
+ *                      ANTQ_FLAG_OVP: ANTQ_ERR_ARG.
+ *                      Refusals as in antq_decode4, reported here, before anything is launched: row_len % 8 != 0, m > 16,
+ *                      n_normal outside 1..15 or more than 15 outliers (ANTQ_FLAG_OVP): ANTQ_ERR_UNSUPPORTED; a null
+ *                      pointer, an empty job: ANTQ_ERR_ARG; out_dev not aligned to its element: ANTQ_ERR_ALIGN; capacity
+ *                      too small: ANTQ_ERR_PLAN.  Jobs whose codes_dev is not 4-byte or whose out_dev is not 16-byte
+ *                      aligned run element-granular inside the same launch.  n_normal is read with ANTQ_FLAG_OVP only.
+ *   antq_decode4_batch : one launch for all jobs; batch_dev is the caller's device copy of the blob.  No allocation, no
+ *                      synchronisation; stream-ordered and capturable.
+ * ------------------------------------------------------------------------- */
+typedef struct antq_decode_job {
+    const uint8_t *codes_dev;   /* rows*row_len/2 bytes, element 2k in the low nibble */
+    void          *out_dev;
+    const float   *alpha_dev;   /* rows floats (alpha_per_row) or 1 */
+    size_t         rows, row_len;
+    int            alpha_per_row;
+    float          gmax;
+    const float   *grid_dev;    /* m floats: the plan's grid as antq_decode4 reads it */
+    int            m, n_normal; /* n_normal only with ANTQ_FLAG_OVP */
+} antq_decode_job;
+size_t antq_decode4_batch_capacity(const antq_decode_job *jobs, int n, int dtype);   /* bytes antq_decode4_batch_build needs; 0: bad arguments */
+int    antq_decode4_batch_build(const antq_decode_job *jobs, int n, int dtype, unsigned flags,
+                                void *batch_host, size_t capacity);
+int    antq_decode4_batch(const void *batch_host, const void *batch_dev, void *stream);
 
 /* -------------------------------------------------------------------------
  * OliVe's clip statistic on ONE read (replaces t.mean() + t.std() of olive_quantization/antquant/quant_modules.py:193-197
