@@ -23,6 +23,7 @@ FLAG_UNORDERED = 4     # antq_fakequant: the launch may start while earlier laun
 IDX_NONE = -1
 IDX_VICTIM = -2
 MAX_GRID = 1024
+LINEAR4_MAX_M = 8      # include/antq.h ANTQ_LINEAR4_MAX_M: input rows antq_linear4 takes
 PLAN_MAX_BYTES = 128 + 4 * MAX_GRID + 16 * 3072 + 20 * 1024 + 16 * 64
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16, torch.float64: F64}
@@ -58,7 +59,8 @@ def lib():
                              "antq_search_pick", "antq_alpha_grad", "antq_nearest_plan", "antq_nearest_hinted",
                              "antq_search_sse_multi", "antq_plan_eval_host_a", "antq_moments", "antq_xmax_3sigma",
                              "antq_calibrate", "antq_prefetch_kernels", "antq_plan_eval_host_h", "antq_calibrate_batch", "antq_absmax_into", "antq_fakequant_f64",
-                             "antq_absmax_t", "antq_alpha_grad_t", "antq_calibrate_install", "antq_decode4_batch_build", "antq_decode4_batch"):
+                             "antq_absmax_t", "antq_alpha_grad_t", "antq_calibrate_install", "antq_decode4_batch_build", "antq_decode4_batch",
+                             "antq_linear4"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
                 L.antq_decode4_batch_capacity.restype = ctypes.c_size_t
@@ -77,6 +79,7 @@ def lib():
                 L.antq_alpha_grad.argtypes = [vp, vp, vp, sz, sz, ci, vp, vp, ci, vp]
                 L.antq_calibrate_install.argtypes = [vp, vp, sz, ci, ci, vp, vp, vp, cu, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp]
                 L.antq_copy.argtypes = [vp, vp, sz, vp]
+                L.antq_linear4.argtypes = [vp, vp, vp, vp, sz, sz, sz, vp, ci, cf, vp, ci, ci, cu, ci, vp]
                 # development: ANTQ_DEBUG_KNOBS="14=2,0=8" applies antq_debug_set(key, value) pairs to the loading thread
                 # (the knobs are thread-local; tools/fuzz_campaign.sh forces code paths with it)
                 for kv in [k for k in os.environ.get("ANTQ_DEBUG_KNOBS", "").split(",") if "=" in k]:
@@ -891,12 +894,15 @@ def encode4(x, alpha, plan, gmax, rows, row_len, per_row, n_normal=0, ovp=False)
     return codes
 
 
-def decode4(codes, alpha, plan, gmax, rows, row_len, per_row, dtype, n_normal=0, ovp=False):
+def decode4(codes, alpha, plan, gmax, rows, row_len, per_row, dtype, n_normal=0, ovp=False, out=None):
     _require_gpu(codes, "codes")
     dt = _DTYPES.get(dtype)
     if dt is None or dt == F64:
         raise AntqError("unsupported dtype %s" % dtype)
-    out = torch.empty(rows * row_len, dtype=dtype, device=codes.device)
+    if out is None:
+        out = torch.empty(rows * row_len, dtype=dtype, device=codes.device)
+    elif not (out.is_cuda and out.device == codes.device and out.dtype == dtype and out.numel() == rows * row_len and out.is_contiguous()):
+        raise AntqError("out must be a contiguous tensor of rows*row_len elements of `dtype` on the codes' device")
     pd = plan.dev(codes.device)
     with _on_device(codes.device):
         rc = lib().antq_decode4(_vp(codes), _vp(out), ctypes.c_size_t(rows), ctypes.c_size_t(row_len), _vp(alpha),
@@ -905,6 +911,45 @@ def decode4(codes, alpha, plan, gmax, rows, row_len, per_row, dtype, n_normal=0,
                                 _stream(codes.device))
     _check(rc, "antq_decode4")
     return out.view(rows, row_len)
+
+
+def linear4(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):
+    """y = x . W^T (+ bias) straight from the packed 4-bit codes of W [N, K] (antq_linear4): x is [..., K] with at most
+    LINEAR4_MAX_M rows, W[n, k] is bit for bit the element decode4 writes in x's dtype, products and sum in fp32.
+    alpha: float32, N scales (per_row) or one; grid_dev: the codebook on the device (Plan.grid_dev).  Returns [..., N]."""
+    _require_gpu(x, "x")
+    _require_gpu(codes, "codes")
+    _require_gpu(alpha, "alpha")
+    _require_gpu(grid_dev, "grid_dev")
+    dt = _DTYPES.get(x.dtype)
+    if dt is None or dt == F64:
+        raise AntqError("unsupported dtype %s" % x.dtype)
+    if K <= 0 or x.numel() % K != 0 or (x.dim() and x.shape[-1] != K):
+        raise AntqError("x must be [..., K]")
+    M = x.numel() // K
+    if codes.dtype != torch.uint8 or codes.numel() * 2 != N * K:
+        raise AntqError("codes must be uint8 of N*K/2 bytes")
+    if alpha.dtype != torch.float32 or alpha.numel() < (N if per_row else 1) or grid_dev.dtype != torch.float32:
+        raise AntqError("alpha must be float32, one per row (per_row) or one; grid_dev float32")
+    if bias is not None:
+        _require_gpu(bias, "bias")
+        if bias.dtype != x.dtype or bias.numel() != N:
+            raise AntqError("bias must hold N elements of x's dtype")
+    for t in (codes, alpha, grid_dev, bias, out):
+        if t is not None and t.device != x.device:
+            raise AntqError("every tensor of linear4 must live on one device")
+    shape = tuple(x.shape[:-1]) + (N,)
+    if out is None:
+        out = torch.empty(shape, dtype=x.dtype, device=x.device)
+    elif not (out.is_cuda and out.dtype == x.dtype and out.numel() == M * N and out.is_contiguous()):
+        raise AntqError("out must be a contiguous tensor of x's dtype with M*N elements on x's device")
+    with _on_device(x.device):
+        rc = lib().antq_linear4(codes.data_ptr(), x.data_ptr(), _ptr(bias), out.data_ptr(), M, N, K, alpha.data_ptr(),
+                                1 if per_row else 0, gmax, grid_dev.data_ptr(), grid_dev.numel(), n_normal,
+                                FLAG_OVP if ovp else 0, dt, _stream_int(x.device))
+    if rc:
+        _check(rc, "antq_linear4")
+    return out
 
 
 # ---------------------------------------------------------------------------------

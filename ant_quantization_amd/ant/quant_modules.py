@@ -572,6 +572,9 @@ class LinearQuantizer(nn.Module):
             self.quant_input.prefetch_sign(input)
         weight = self.quant_weight(self.weight, input)
         input = self.quant_input(input, self.weight)
+        bank = self.quant_weight._bank
+        if bank is not None and bank.fused_linear:         # packed.pack_model(fused_linear=True): few rows run from the codes
+            return bank.linear(self, input, weight)
         return F.linear(input, weight, self.bias)
 
 

@@ -4,6 +4,7 @@
 #include "antq_dispatch.h"
 #include "antq_k_batch.h"
 #include "antq_k_decbatch.h"
+#include "antq_k_linear4.h"
 
 #include <type_traits>
 
@@ -378,6 +379,45 @@ extern "C" int antq_decode4_batch(const void *batch_host, const void *batch_dev,
         return with_bool((h->flags & ANTQ_FLAG_OVP) != 0, [&](auto ovp) {
             hipLaunchKernelGGL((k_decode4_batch<decltype(tag), decltype(ovp)::value>), dim3(h->total_blocks * 4u), dim3(64u), 0, st, descs, map);
             return launch_status();
+        });
+    });
+}
+
+// y = x . W^T (+ bias) for 1 .. ANTQ_LINEAR4_MAX_M rows of x from the packed codes of W (antq_k_linear4.h).  Every check
+// comes before anything touches HIP.
+extern "C" int antq_linear4(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
+                            const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
+                            unsigned flags, int dtype, void *stream)
+{
+    if (!codes || !x || !y || !alpha || !grid || m < 1) return ANTQ_ERR_ARG;
+    if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_ARG;
+    if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
+    if (M == 0 || N == 0) return ANTQ_OK;
+    const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
+    if (M > ANTQ_LINEAR4_MAX_M || K == 0 || K % 8 != 0) return ANTQ_ERR_UNSUPPORTED;
+    if (ovp) { if (n_normal < 1 || n_normal > 15 || m - n_normal > 15 || m - n_normal < 0) return ANTQ_ERR_UNSUPPORTED; }
+    else if (m > 16) return ANTQ_ERR_UNSUPPORTED;
+    if (N > 0x7fffffffull || K > 0x7ffffff8ull) return ANTQ_ERR_UNSUPPORTED;      // (rows and row length in 32 bits)
+    const uintptr_t esz = (dtype == ANTQ_F32) ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(codes) % 4 || reinterpret_cast<uintptr_t>(y) % esz ||
+        reinterpret_cast<uintptr_t>(bias) % esz)
+        return ANTQ_ERR_ALIGN;
+    const bool vec = K % 32 == 0 && reinterpret_cast<uintptr_t>(codes) % 16 == 0;     // 16 B of codes per lane
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int mt = M <= 2 ? (int)M : (M <= 4 ? 4 : 8);           // rows the kernel computes: 3 runs as 4, 5 .. 7 as 8
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return with_bool(ovp, [&](auto o) {
+            return with_value<1, 2, 4, 8>(mt, [&](auto mm) {
+                return with_bool(vec, [&](auto v) {
+                    constexpr int MT = decltype(mm)::value;
+                    const unsigned blocks = (unsigned)((N + lin4_rows(MT) - 1) / lin4_rows(MT));
+                    launch_k(false, k_linear4<T, decltype(o)::value, MT, decltype(v)::value>, dim3(blocks), dim3(64u), 0, st,
+                             reinterpret_cast<const uint32_t *>(codes), x, bias, y, (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha,
+                             per_row ? 1 : 0, gmax, grid, (uint32_t)m, ovp ? n_normal : 0);
+                    return launch_status();
+                });
+            });
         });
     });
 }

@@ -27,8 +27,21 @@ The scale a layer is decoded with is the quantiser's `alpha` as it is when the i
 Checkpoint: `packed_state_dict(model)` = the quantiser state the reference's checkpoints already carry (same keys) plus
 `<layer>.quant_weight.codes` (uint8, numel / 2 bytes) for packed layers and `<layer>.weight` only for skipped ones;
 `load_packed_state_dict(model, sd)` loads it into a freshly wrapped, uncalibrated model without re-encoding.
+
+`fused_linear=True` lets the packed Linear layers compute with the codes: a no-grad call whose quantised input has at most
+`_lib.LINEAR4_MAX_M` rows (LLM decode, batch 1) and is a contiguous, 16-byte-aligned GPU tensor of the layer's dtype runs
+`antq_linear4` -- y = x . W^T + bias straight from the codes, W being bit for bit the decoded image, the sum in fp32 in the
+kernel's own fixed order (so the result is that of F.linear on the image up to the rounding of an fp32 sum, not its bits).
+Every other call runs F.linear on the image as before.  `.fused_calls` counts the calls the kernel served.
+`keep_images=False` (with fused_linear only) drops the decoded images of those layers: a call with more rows decodes that
+one layer with `antq_decode4` into ONE scratch buffer owned by the bank -- sized to the largest such layer per (device,
+dtype) -- and runs F.linear on it.  The scratch is valid only until the next such layer's call on the same stream: nothing
+may keep a reference to it (a captured graph is fine, a side stream or autograd through the input is not).  With
+`release_weights=True` such a layer's `weight.data` becomes an empty tensor (the bank remembers the shape): a deep copy
+of such a model has no weights to fall back on, and a forward with the layer's quantiser disabled raises AntqError.  Conv layers and skipped layers behave as without the options.
 """
 import torch
+import torch.nn.functional as F
 
 from . import _lib
 from ._model import load_ant_state_dict
@@ -55,10 +68,16 @@ def _settle(q):
 
 
 class PackedBank:
-    def __init__(self, model, release_weights=False, codes=None):
+    def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True):
         """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict)."""
+        if not keep_images and not fused_linear:
+            raise _lib.AntqError("PackedBank: keep_images=False needs fused_linear=True (nothing else computes from the codes)")
         self.model = model
         self.release_weights = bool(release_weights)
+        self.fused_linear = bool(fused_linear)   # Linear layers with few input rows compute from the codes (antq_linear4)
+        self.keep_images = bool(keep_images)
+        self.fused_calls = 0       # forwards antq_linear4 served
+        self._scratch = {}         # (device, dtype) -> the one decode buffer of the layers without an image
         self.entries = {}          # id(quantiser) -> dict
         self.skipped = []          # (layer name, reason): layers that keep their float weight and per-layer launch
         self.launches = 0          # decode launches so far (one per (device, dtype, pair rule) group and refresh)
@@ -86,8 +105,11 @@ class PackedBank:
                     with torch.no_grad():
                         alpha = q.alpha.detach().reshape(-1).to(torch.float32).contiguous()
                         c = _lib.encode4(w.detach(), alpha, plan, gmax, rows, row_len, per_row, n_normal=n_normal, ovp=ovp)
+                fusable = self.fused_linear and w.dim() == 2 and getattr(mod, "in_features", None) == w.shape[1] and w.shape[1] % 8 == 0
+                image = self.keep_images or not fusable
                 self.entries[id(q)] = dict(name=name, q=q, mod=mod, rows=rows, row_len=row_len, per_row=per_row, codes=c,
-                                           out=torch.empty_like(w, memory_format=torch.contiguous_format))
+                                           fusable=fusable, shape=tuple(w.shape), dtype=w.dtype, device=w.device,
+                                           out=torch.empty_like(w, memory_format=torch.contiguous_format) if image else None)
             if not self.entries:
                 raise _lib.AntqError("PackedBank: no weight quantiser to pack (run one forward to calibrate first): %r" % (self.skipped,))
             for e in self.entries.values():
@@ -143,9 +165,10 @@ class PackedBank:
     mark_dirty = invalidate
 
     def nbytes(self):
-        """(bytes of codes, bytes of decoded images)"""
+        """(bytes of codes, bytes of decoded images and of the scratch buffers that stand in for dropped ones)"""
         return (sum(e["codes"].numel() for e in self.entries.values()),
-                sum(e["out"].numel() * e["out"].element_size() for e in self.entries.values()))
+                sum(t.numel() * t.element_size() for t in [e["out"] for e in self.entries.values() if e["out"] is not None]
+                    + list(self._scratch.values())))
 
     def detach(self):
         for e in self.entries.values():
@@ -155,32 +178,40 @@ class PackedBank:
         self._batches = []
 
     def _pointers(self):
-        return tuple((e["mod"].weight.dtype, e["mod"].weight.device, e["out"].data_ptr(), e["q"].alpha.data_ptr(), e["q"].alpha.dtype,
+        return tuple((e["mod"].weight.dtype, e["mod"].weight.device, e["out"].data_ptr() if e["out"] is not None else 0, e["q"].alpha.data_ptr(), e["q"].alpha.dtype,
                       id(e["q"]._ensure_plan()), e["q"]._gmax) for e in self.entries.values())
 
     def _build(self):
         """(Re)build the descriptor tables: one batch per (device, dtype, pair rule)."""
-        groups = {}
+        groups, need = {}, {}
         for e in self.entries.values():
             q, w = e["q"], e["mod"].weight
-            if e["out"].dtype != w.dtype or e["out"].device != w.device:      # .half() / .to(device) since
-                e["out"] = torch.empty(w.shape, dtype=w.dtype, device=w.device)
+            if e["dtype"] != w.dtype or e["device"] != w.device:      # .half() / .to(device) since
+                if e["out"] is not None:
+                    e["out"] = torch.empty(e["shape"], dtype=w.dtype, device=w.device)
                 e["codes"] = e["codes"].to(w.device)
+                e["dtype"], e["device"] = w.dtype, w.device
             plan, gmax, n_normal, ovp = _codebook(q)
             alpha = q.alpha.detach().reshape(-1)
             e["alpha32"] = None
             if alpha.dtype != torch.float32 or not alpha.is_contiguous() or alpha.device != w.device:
                 # (a 16-bit model's alpha: the kernel reads a float32 copy, brought up to date in place at every refresh)
                 alpha = e["alpha32"] = alpha.to(device=w.device, dtype=torch.float32).contiguous()
+            e["alpha"] = alpha
+            if e["out"] is None:           # no image: the codes are the weight (linear); one scratch per (device, dtype) stands in
+                need[(w.device, w.dtype)] = max(need.get((w.device, w.dtype), 0), e["rows"] * e["row_len"])
+                continue
             groups.setdefault((w.device, w.dtype, ovp), []).append(
                 (e["codes"], e["out"], alpha, plan, gmax, e["rows"], e["row_len"], e["per_row"], n_normal))
         self._batches = [_lib.DecodeBatch(jobs, ovp=ovp) for (_, _, ovp), jobs in groups.items()]
+        self._scratch = {k: (self._scratch[k] if k in self._scratch and self._scratch[k].numel() == n
+                             else torch.empty(n, dtype=k[1], device=k[0])) for k, n in need.items()}
         self._ptr_key = self._pointers()
 
     # ------------------------------------------------------------------ the one launch
     @torch.no_grad()
     def refresh(self):
-        if not self._batches or self._ptr_key != self._pointers():
+        if self._ptr_key is None or self._ptr_key != self._pointers():
             self._build()
         else:
             for e in self.entries.values():
@@ -193,7 +224,10 @@ class PackedBank:
         if self.release_weights:
             for e in self.entries.values():
                 w = e["mod"].weight
-                if w.data_ptr() != e["out"].data_ptr():
+                if e["out"] is None:
+                    if w.numel():
+                        w.data = torch.empty(0, dtype=w.dtype, device=w.device)     # the codes are all there is
+                elif w.data_ptr() != e["out"].data_ptr():
                     w.data = e["out"]        # the float original is freed; weight now IS the fake-quantised image
 
     def lookup(self, q, tensor, training=None):
@@ -209,11 +243,50 @@ class PackedBank:
                                  "(run the forward under torch.no_grad())" % e["name"])
         if not q._steady or not (q.is_enable and q.is_enable_weight):
             return None
-        out = e["out"]
-        if self.dirty or out.dtype != tensor.dtype or out.device != tensor.device:
+        if self.dirty or e["dtype"] != tensor.dtype or e["device"] != tensor.device:
             self.refresh()
-            out = e["out"]
-        return out
+        if e["out"] is None:
+            # (a layer without an image: the weight itself stands in until linear() below, which every call of such a layer
+            # reaches; the mark tells it that this call was served here -- a disabled quantiser hands back the same tensor)
+            e["served"] = True
+            return tensor
+        return e["out"]
+
+    def _image(self, e):
+        """The decoded image of a layer that keeps none, in the bank's scratch buffer (valid until the next such call)."""
+        q = e["q"]
+        plan, gmax, n_normal, ovp = _codebook(q)
+        buf = self._scratch[(e["device"], e["dtype"])][:e["rows"] * e["row_len"]]
+        _lib.decode4(e["codes"], e["alpha"], plan, gmax, e["rows"], e["row_len"], e["per_row"], e["dtype"], n_normal=n_normal,
+                     ovp=ovp, out=buf)
+        return buf.view(e["shape"])
+
+    def linear(self, mod, input, weight):
+        """The output of a LinearQuantizer whose weight quantiser this bank serves (fused_linear): `input` after quant_input,
+        `weight` what quant_weight returned.  From the codes when the call qualifies, F.linear on the image otherwise."""
+        q = mod.quant_weight
+        e = self.entries.get(id(q))
+        if e is not None and e["out"] is None:     # (lookup()'s own conditions again: a mark left by a call that failed is stale)
+            served = e.pop("served", False) and weight is mod.weight and q._steady and q.is_enable and q.is_enable_weight
+        else:
+            served = e is not None and weight is e["out"]
+        if not served or not e["fusable"]:         # not served by lookup(): the per-layer path's tensor, or the float weight
+            if e is not None and e["out"] is None and mod.weight.numel() == 0:
+                raise _lib.AntqError("layer %s was packed with keep_images=False and release_weights=True: its float weight is "
+                                     "gone, so it cannot run with its quantiser disabled or re-calibrating (only from its "
+                                     "codes)" % e["name"])
+            return F.linear(input, weight, mod.bias)
+        K = e["shape"][1]
+        bias = mod.bias
+        if (input.is_cuda and input.dtype == e["dtype"] and input.device == e["device"] and input.dim() >= 1 and input.shape[-1] == K
+                and 0 < input.numel() <= _lib.LINEAR4_MAX_M * K and input.is_contiguous() and input.data_ptr() % 16 == 0
+                and not (torch.is_grad_enabled() and (input.requires_grad or (bias is not None and bias.requires_grad)))
+                and (bias is None or (bias.dtype == input.dtype and bias.is_contiguous() and bias.device == input.device))):
+            plan, gmax, n_normal, ovp = _codebook(e["q"])
+            self.fused_calls += 1
+            return _lib.linear4(e["codes"], input, e["alpha"], plan.grid_dev(e["device"]), gmax, e["shape"][0], K, e["per_row"],
+                                bias=None if bias is None else bias.detach(), n_normal=n_normal, ovp=ovp)
+        return F.linear(input, weight if e["out"] is not None else self._image(e), bias)
 
 
 def _no_auto_bank(model):
@@ -232,10 +305,12 @@ def _bank_of(model):
     return None
 
 
-def pack_model(model, release_weights=False):
+def pack_model(model, release_weights=False, fused_linear=False, keep_images=True):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
-    (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons."""
-    return PackedBank(model, release_weights=release_weights)
+    (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
+    fused_linear: Linear layers called with at most _lib.LINEAR4_MAX_M input rows compute from the codes (antq_linear4);
+    keep_images=False (with fused_linear): those layers keep no decoded image -- see the module docstring."""
+    return PackedBank(model, release_weights=release_weights, fused_linear=fused_linear, keep_images=keep_images)
 
 
 def packed_state_dict(model):
@@ -256,11 +331,13 @@ def _packed_keys(sd, codes):
     return sd
 
 
-def load_packed_state_dict(model, sd, release_weights=True):
+def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, keep_images=True):
     """Load a packed checkpoint into a freshly wrapped, uncalibrated model living on the GPU: the quantiser state is
     installed the way load_ant_state_dict + load_state_dict do (scales keep the dtype they were stored with), a PackedBank is attached from the stored codes without
     re-encoding, and the weights are materialised by the batched decode (release_weights=False: copied into the layers'
-    own float weights instead of replacing them).  Returns the bank."""
+    own float weights instead of replacing them).  fused_linear / keep_images: as in pack_model.  Returns the bank."""
+    if not keep_images and not fused_linear:
+        raise _lib.AntqError("load_packed_state_dict: keep_images=False needs fused_linear=True")
     suffix = "." + CODES_KEY
     codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}
     rest = {k: v for k, v in sd.items() if not k.endswith(suffix)}
@@ -278,9 +355,9 @@ def load_packed_state_dict(model, sd, release_weights=True):
             module.alpha.data = a.detach().clone().to(module.alpha.device)
     for _, _, q, _ in _weight_layers(model):
         _settle(q)
-    bank = PackedBank(model, release_weights=release_weights, codes=codes)
+    bank = PackedBank(model, release_weights=release_weights, codes=codes, fused_linear=fused_linear, keep_images=keep_images)
     if not release_weights:
         with torch.no_grad():
             for e in bank.entries.values():
-                e["mod"].weight.data.copy_(e["out"])
+                e["mod"].weight.data.copy_(e["out"] if e["out"] is not None else bank._image(e))
     return bank

@@ -66,6 +66,8 @@ class _LazyPick:
 
 
 class WeightBank:
+    fused_linear = False           # (packed.PackedBank's option: the Linear wrappers ask their weight quantiser's bank)
+
     def __init__(self, model, resident=True):
         self.model = model
         self.resident = bool(resident)   # False: the reference's schedule (module docstring), what AutoBank builds by default

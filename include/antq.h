@@ -43,7 +43,7 @@ extern "C" {
  * 7 (round 6): antq_absmax_t / antq_alpha_grad_t (whole-tensor reductions in ONE launch through a caller-owned ticket block,
  * ANTQ_REDUCE_WS_BYTES) and antq_calibrate_install added (nothing else changed).
  * Still 7: antq_decode4_batch_capacity / antq_decode4_batch_build / antq_decode4_batch added (the batched packed decoder; nothing
- * that existed changed, so callers built against 7 keep working).
+ * that existed changed, so callers built against 7 keep working).  antq_linear4 (the packed 4-bit linear) added likewise.
  * A caller built against another version must not call in: the blobs / argument lists differ. */
 #define ANTQ_ABI_VERSION 7
 
@@ -467,6 +467,38 @@ size_t antq_decode4_batch_capacity(const antq_decode_job *jobs, int n, int dtype
 int    antq_decode4_batch_build(const antq_decode_job *jobs, int n, int dtype, unsigned flags,
                                 void *batch_host, size_t capacity);
 int    antq_decode4_batch(const void *batch_host, const void *batch_dev, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Packed 4-bit linear: y = x . W^T (+ bias) for 1 .. ANTQ_LINEAR4_MAX_M rows of x, computed straight from the codes of W
+ * (the consumer the codec exists for: a layer with few input rows streams its weights once, and the codes are a quarter
+ * of the bf16 image's bytes).  codes: N rows of K codes in antq_encode4's layout; alpha / gmax / grid / m / n_normal as in
+ * antq_decode_job, alpha_per_row: one scale per output row n.
+ *   W[n,k] is, bit for bit, the element antq_decode4 writes for the same codes, alpha, gmax, grid and flags in `dtype`:
+ *          fl((g[c] + 0.0f) * (alpha / gmax)) rounded to `dtype`, the pair rule applied -- not the unrounded product, and not
+ *          a scale factored out of the sum.
+ *   y[m,n] = round_dtype( sum_k x[m,k] * W[n,k] + bias[n] ), products and sum accumulated in fp32 (fused multiply-adds).
+ *   The order of the sum is the kernel's own, but fixed: the same input gives the same bits on every run, and y[m,.] does
+ *          not depend on M or on the other rows of x -- a row computed alone has the bits it has inside a call of 8.
+ *   No floating-point atomics, no split-K across workgroups, no inter-workgroup communication, no workspace, no allocation,
+ *          no synchronisation: stream-ordered and capturable into a graph.
+ * Checked before anything touches HIP, in this order:
+ *   ANTQ_ERR_ARG          a null codes / x / y / alpha / grid, m < 1, a bad dtype, a flag bit other than ANTQ_FLAG_OVP
+ *   ANTQ_OK, no launch    M == 0 or N == 0
+ *   ANTQ_ERR_UNSUPPORTED  M > ANTQ_LINEAR4_MAX_M; K == 0 or K % 8 != 0; the decoder's refusals: m > 16, with ANTQ_FLAG_OVP
+ *                         n_normal outside 1..15 or more than 15 outliers; N >= 2^31 or K >= 2^31
+ *   ANTQ_ERR_ALIGN        x_dev not 16-byte aligned, codes_dev not 4-byte aligned, y_dev / bias_dev not aligned to their element
+ * Codes are read 16 bytes per lane when K % 32 == 0 and codes_dev is 16-byte aligned, 4 bytes per lane otherwise (the order
+ * of the sum differs between the two, nothing else).  F32 / BF16 / F16.
+ * ------------------------------------------------------------------------- */
+#define ANTQ_LINEAR4_MAX_M 8
+int antq_linear4(const uint8_t *codes_dev,          /* N*K/2 bytes, antq_encode4's layout */
+                 const void *x_dev,                 /* [M, K] row-major, dtype */
+                 const void *bias_dev,              /* N elements of dtype, or NULL */
+                 void *y_dev,                       /* [M, N] row-major, dtype */
+                 size_t M, size_t N, size_t K,
+                 const float *alpha_dev, int alpha_per_row, float gmax,
+                 const float *grid_dev, int m, int n_normal,   /* as in antq_decode_job */
+                 unsigned flags /* 0 | ANTQ_FLAG_OVP */, int dtype /* F32 | BF16 | F16 */, void *stream);
 
 /* -------------------------------------------------------------------------
  * OliVe's clip statistic on ONE read (replaces t.mean() + t.std() of olive_quantization/antquant/quant_modules.py:193-197
