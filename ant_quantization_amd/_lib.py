@@ -877,13 +877,19 @@ def copy(src, dst):
     return dst
 
 
-def encode4(x, alpha, plan, gmax, rows, row_len, per_row, n_normal=0, ovp=False):
-    """Packed 4-bit codes (two per byte) of the quantised tensor: uint8 tensor of numel/2 bytes."""
+def encode4(x, alpha, plan, gmax, rows, row_len, per_row, n_normal=0, ovp=False, out=None):
+    """Packed 4-bit codes (two per byte) of the quantised tensor: uint8 tensor of numel/2 bytes.  out: a caller-owned
+    buffer for them (a view into a larger one will do; antq_encode4 wants it 4-byte aligned)."""
     _require_gpu(x, "x")
     dt = _DTYPES.get(x.dtype)
     if dt is None or dt == F64:
         raise AntqError("unsupported dtype %s" % x.dtype)
-    codes = torch.empty(x.numel() // 2, dtype=torch.uint8, device=x.device)
+    if out is None:
+        codes = torch.empty(x.numel() // 2, dtype=torch.uint8, device=x.device)
+    elif not (out.is_cuda and out.device == x.device and out.dtype == torch.uint8 and out.numel() == x.numel() // 2 and out.is_contiguous()):
+        raise AntqError("out must be a contiguous uint8 tensor of numel/2 bytes on x's device")
+    else:
+        codes = out
     pd = plan.dev(x.device)
     with _on_device(x.device):
         rc = lib().antq_encode4(_vp(x), _vp(codes), ctypes.c_size_t(rows), ctypes.c_size_t(row_len), _vp(alpha),
