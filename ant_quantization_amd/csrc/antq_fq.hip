@@ -52,7 +52,8 @@ static int launch_uniform(const void *x, void *out, int16_t *idx, size_t rows, s
         // leaves fewer idle lanes (rows of 128 vectors: 2; 144 / 288 / 576: 3)
         int U = (int)row_task_u((uint32_t)std::min<size_t>(vpr, 0x7fffffffu));
         if (DYN) U = vpr <= 128 ? 2 : vpr <= 192 ? 3 : (vpr <= 256 || (vpr > 512 && vpr <= 1024) || (vpr > 2048 && vpr <= 4096)) ? 4 : 8;
-        if (g_knob_u) U = DYN ? U : g_knob_u;
+        // (a forced U that is none of 8 / 4 / 3 / 2 runs the 1-vector kernel: the task size below must be the launched kernel's)
+        if (g_knob_u) U = DYN ? U : one_of<8, 4, 3, 2>(g_knob_u, 1);
         const bool wpr4 = DYN && vpr > 512 && vpr <= 2048;   // one row per workgroup: 4 wavefronts x U x 64 vectors
         const bool wpr16 = DYN && vpr > 2048;                // one row per 1024-thread workgroup: 16 wavefronts
         const size_t tpr = wpr16 ? 16 : wpr4 ? 4 : (vpr + (size_t)64 * U - 1) / ((size_t)64 * U);
@@ -92,8 +93,7 @@ static int launch_uniform(const void *x, void *out, int16_t *idx, size_t rows, s
                     });
                 });
         }
-        // (a forced U that is none of 8 / 4 / 3 / 2 launches the 1-vector kernel)
-        return with_value<8, 4, 3, 2, 1>(one_of<8, 4, 3, 2>(U, 1), [&](auto u) {
+        return with_value<8, 4, 3, 2, 1>(U, [&](auto u) {
             return xrow(k_fq_xrow<T, OVP, IDX, decltype(u)::value, DYN>, grid_dim, block, t_unordered);
         });
     }
@@ -109,7 +109,9 @@ static int launch_uniform(const void *x, void *out, int16_t *idx, size_t rows, s
             const double util = (double)vpr / (double)(((vpr + span - 1) / span) * span);
             if (util > best + 0.05) { best = util; U = cand; }
         }
-        if (g_knob_u) U = g_knob_u;
+        // (a forced U that is none of 8 / 4 / 2 runs the 1-vector kernel: the task size below must be the launched kernel's --
+        //  with knob 0 = 3 the tasks were cut for 3 vectors per lane and the 1-vector kernel left two thirds of each unwritten)
+        if (g_knob_u) U = one_of<8, 4, 2>(g_knob_u, 1);
     }
     const size_t tpr = (vpr + (size_t)64 * U - 1) / ((size_t)64 * U);
     const size_t total = rows * tpr;
@@ -127,8 +129,7 @@ static int launch_uniform(const void *x, void *out, int16_t *idx, size_t rows, s
         return launch_status();
     }
     const dim3 grid((unsigned)blocks), block(256);
-    // (a forced U that is none of 8 / 4 / 2 launches the 1-vector kernel)
-    return with_value<8, 4, 2, 1>(one_of<8, 4, 2>(U, 1), [&](auto u) {
+    return with_value<8, 4, 2, 1>(U, [&](auto u) {
         hipLaunchKernelGGL((k_fq_uniform<T, OVP, IDX, decltype(u)::value, DYN>), grid, block, lds, st, xv, ov, idx, (uint32_t)total,
                            (uint32_t)vpr, (uint32_t)tpr, alpha, per_row, gmax, ratio, alpha_out, pa, tab);
         return launch_status();
