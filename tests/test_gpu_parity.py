@@ -1148,6 +1148,7 @@ def test_float64_forward_is_the_reference_sequence_around_the_operator(antq_lib,
     then a TensorQuantizer fed a double tensor calibrates (on the float32 image) and returns float64."""
     import torch
     from ant_quantization_amd import core
+    from operator_cases import f64_forward_ref
     rng = np.random.default_rng(64)
     G, O = golden("ant_grids.npz"), golden("olive_grids.npz")
     gol = np.concatenate([O["flint_b4_s"], O["outlier_b4_s"]])
@@ -1163,19 +1164,7 @@ def test_float64_forward_is_the_reference_sequence_around_the_operator(antq_lib,
                 a_t = torch.from_numpy(alpha.reshape(-1, 1) if per_channel else alpha.reshape(())).to(dev)
                 out = core.fake_quant(xt, a_t, plan, gmax, per_channel, ovp=ovp)
                 assert out.dtype == torch.float64 and out.shape == xt.shape
-                scale = alpha.astype(np.float64).reshape(-1, 1) / gmax if per_channel else alpha.astype(np.float64) / gmax
-                d = (x2 / scale).reshape(shape) if per_channel else x / scale
-                q = oracle.nearest(d.reshape(-1), g.astype(np.float64))[0]
-                if ovp:                                          # OQ:311-320
-                    mask = np.abs(q) > 32
-                    vo = np.roll(mask, 1)
-                    vo[::2] = False
-                    ve = np.roll(mask & ~vo, -1)
-                    ve[1::2] = False
-                    q = q * (~(ve | vo))
-                q = q.reshape(shape)
-                t = (q - d) + d
-                ref = (t.reshape(shape[0], -1) * scale).reshape(shape) if per_channel else t * scale
+                ref = f64_forward_ref(oracle, x2, alpha, g, gmax, ovp, per_channel).reshape(shape)     # the numpy-float64 restatement
                 got = out.cpu().numpy()
                 assert np.array_equal(got.view(np.uint64), np.ascontiguousarray(ref).view(np.uint64)), (shape, ovp, per_channel)
     from ant_quantization_amd.ant import quant_modules as qm
