@@ -24,6 +24,7 @@ IDX_NONE = -1
 IDX_VICTIM = -2
 MAX_GRID = 1024
 LINEAR4_MAX_M = 8      # include/antq.h ANTQ_LINEAR4_MAX_M: input rows antq_linear4 takes
+LINEAR4_MM_MAX_M = 64  # include/antq.h ANTQ_LINEAR4_MM_MAX_M: input rows antq_linear4_mm takes
 PLAN_MAX_BYTES = 128 + 4 * MAX_GRID + 16 * 3072 + 20 * 1024 + 16 * 64
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16, torch.float64: F64}
@@ -60,7 +61,7 @@ def lib():
                              "antq_search_sse_multi", "antq_plan_eval_host_a", "antq_moments", "antq_xmax_3sigma",
                              "antq_calibrate", "antq_prefetch_kernels", "antq_plan_eval_host_h", "antq_calibrate_batch", "antq_absmax_into", "antq_fakequant_f64",
                              "antq_absmax_t", "antq_alpha_grad_t", "antq_calibrate_install", "antq_decode4_batch_build", "antq_decode4_batch",
-                             "antq_linear4"):
+                             "antq_linear4", "antq_linear4_mm"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
                 L.antq_decode4_batch_capacity.restype = ctypes.c_size_t
@@ -80,6 +81,7 @@ def lib():
                 L.antq_calibrate_install.argtypes = [vp, vp, sz, ci, ci, vp, vp, vp, cu, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp]
                 L.antq_copy.argtypes = [vp, vp, sz, vp]
                 L.antq_linear4.argtypes = [vp, vp, vp, vp, sz, sz, sz, vp, ci, cf, vp, ci, ci, cu, ci, vp]
+                L.antq_linear4_mm.argtypes = L.antq_linear4.argtypes
                 # development: ANTQ_DEBUG_KNOBS="14=2,0=8" applies antq_debug_set(key, value) pairs to the loading thread
                 # (the knobs are thread-local; tools/fuzz_campaign.sh forces code paths with it)
                 for kv in [k for k in os.environ.get("ANTQ_DEBUG_KNOBS", "").split(",") if "=" in k]:
@@ -919,20 +921,19 @@ def decode4(codes, alpha, plan, gmax, rows, row_len, per_row, dtype, n_normal=0,
     return out.view(rows, row_len)
 
 
-def linear4(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):
-    """y = x . W^T (+ bias) straight from the packed 4-bit codes of W [N, K] (antq_linear4): x is [..., K] with at most
-    LINEAR4_MAX_M rows, W[n, k] is bit for bit the element decode4 writes in x's dtype, products and sum in fp32.
-    alpha: float32, N scales (per_row) or one; grid_dev: the codebook on the device (Plan.grid_dev).  Returns [..., N]."""
+def _linear4_call(entry, max_m, allow_f32, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out):
     _require_gpu(x, "x")
     _require_gpu(codes, "codes")
     _require_gpu(alpha, "alpha")
     _require_gpu(grid_dev, "grid_dev")
     dt = _DTYPES.get(x.dtype)
-    if dt is None or dt == F64:
+    if dt is None or dt == F64 or (dt == F32 and not allow_f32):
         raise AntqError("unsupported dtype %s" % x.dtype)
     if K <= 0 or x.numel() % K != 0 or (x.dim() and x.shape[-1] != K):
         raise AntqError("x must be [..., K]")
     M = x.numel() // K
+    if max_m is not None and M > max_m:
+        raise AntqError("%s takes at most %d rows of x (got %d)" % (entry, max_m, M))
     if codes.dtype != torch.uint8 or codes.numel() * 2 != N * K:
         raise AntqError("codes must be uint8 of N*K/2 bytes")
     if alpha.dtype != torch.float32 or alpha.numel() < (N if per_row else 1) or grid_dev.dtype != torch.float32:
@@ -950,12 +951,26 @@ def linear4(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=
     elif not (out.is_cuda and out.dtype == x.dtype and out.numel() == M * N and out.is_contiguous()):
         raise AntqError("out must be a contiguous tensor of x's dtype with M*N elements on x's device")
     with _on_device(x.device):
-        rc = lib().antq_linear4(codes.data_ptr(), x.data_ptr(), _ptr(bias), out.data_ptr(), M, N, K, alpha.data_ptr(),
-                                1 if per_row else 0, gmax, grid_dev.data_ptr(), grid_dev.numel(), n_normal,
-                                FLAG_OVP if ovp else 0, dt, _stream_int(x.device))
+        rc = getattr(lib(), entry)(codes.data_ptr(), x.data_ptr(), _ptr(bias), out.data_ptr(), M, N, K, alpha.data_ptr(),
+                                   1 if per_row else 0, gmax, grid_dev.data_ptr(), grid_dev.numel(), n_normal,
+                                   FLAG_OVP if ovp else 0, dt, _stream_int(x.device))
     if rc:
-        _check(rc, "antq_linear4")
+        _check(rc, entry)
     return out
+
+
+def linear4(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):
+    """y = x . W^T (+ bias) straight from the packed 4-bit codes of W [N, K] (antq_linear4): x is [..., K] with at most
+    LINEAR4_MAX_M rows, W[n, k] is bit for bit the element decode4 writes in x's dtype, products and sum in fp32.
+    alpha: float32, N scales (per_row) or one; grid_dev: the codebook on the device (Plan.grid_dev).  Returns [..., N]."""
+    return _linear4_call("antq_linear4", None, True, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
+
+
+def linear4_mm(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):
+    """linear4 on the matrix cores (antq_linear4_mm): x is [..., K] with at most LINEAR4_MM_MAX_M rows, bfloat16 or float16
+    (float32 raises AntqError).  Same W, fp32 accumulation in the MFMA accumulator; the order of the sum is not linear4's,
+    so the same row has different low bits from the two.  A row's bits do not depend on the other rows or on their number."""
+    return _linear4_call("antq_linear4_mm", LINEAR4_MM_MAX_M, False, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
 
 
 # ---------------------------------------------------------------------------------

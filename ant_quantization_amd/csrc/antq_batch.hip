@@ -5,6 +5,7 @@
 #include "antq_k_batch.h"
 #include "antq_k_decbatch.h"
 #include "antq_k_linear4.h"
+#include "antq_k_linear4_mm.h"
 
 #include <type_traits>
 
@@ -416,6 +417,49 @@ extern "C" int antq_linear4(const uint8_t *codes, const void *x, const void *bia
                              reinterpret_cast<const uint32_t *>(codes), x, bias, y, (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha,
                              per_row ? 1 : 0, gmax, grid, (uint32_t)m, ovp ? n_normal : 0);
                     return launch_status();
+                });
+            });
+        });
+    });
+}
+
+// The same product for 1 .. ANTQ_LINEAR4_MM_MAX_M rows of x on the matrix cores (antq_k_linear4_mm.h; bf16 / f16).  Checks as
+// in antq_linear4, in its order, before anything touches HIP.
+extern "C" int antq_linear4_mm(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
+                               const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
+                               unsigned flags, int dtype, void *stream)
+{
+    if (!codes || !x || !y || !alpha || !grid || m < 1) return ANTQ_ERR_ARG;
+    if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_ARG;
+    if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
+    if (M == 0 || N == 0) return ANTQ_OK;
+    const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
+    if (dtype == ANTQ_F32) return ANTQ_ERR_UNSUPPORTED;           // (the f32-input MFMA runs at the VALU rate: antq_linear4's ground)
+    if (M > ANTQ_LINEAR4_MM_MAX_M || K == 0 || K % 8 != 0) return ANTQ_ERR_UNSUPPORTED;
+    if (ovp) { if (n_normal < 1 || n_normal > 15 || m - n_normal > 15 || m - n_normal < 0) return ANTQ_ERR_UNSUPPORTED; }
+    else if (m > 16) return ANTQ_ERR_UNSUPPORTED;
+    if (N > 0x7fffffffull || K > 0x7ffffff8ull) return ANTQ_ERR_UNSUPPORTED;      // (rows and row length in 32 bits)
+    if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(codes) % 4 || reinterpret_cast<uintptr_t>(y) % 2 ||
+        reinterpret_cast<uintptr_t>(bias) % 2)
+        return ANTQ_ERR_ALIGN;
+    const bool vec = K % 32 == 0 && reinterpret_cast<uintptr_t>(codes) % 16 == 0;     // 16 B of codes per lane
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int mt = mm_mtiles(M);
+    const int nt = one_of<1, 2, 4>(g_knob_mm_tile, mm_ntiles(M, N));
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if constexpr (std::is_same<T, float>::value) return (int)ANTQ_ERR_UNSUPPORTED;
+        else return with_bool(ovp, [&](auto o) {
+            return with_value<1, 2, 4>(mt, [&](auto mm) {
+                return with_value<1, 2, 4>(nt, [&](auto nn) {
+                    return with_bool(vec, [&](auto v) {
+                        constexpr int NT = decltype(nn)::value;
+                        const unsigned blocks = (unsigned)((N + 16 * NT - 1) / (16 * NT));
+                        launch_k(false, k_linear4_mm<T, decltype(o)::value, decltype(mm)::value, NT, decltype(v)::value>, dim3(blocks),
+                                 dim3(64u * kMmWaves), 0, st, reinterpret_cast<const uint32_t *>(codes), x, bias, y, (uint32_t)M, (uint32_t)N,
+                                 (uint32_t)K, alpha, per_row ? 1 : 0, gmax, grid, (uint32_t)m, ovp ? n_normal : 0);
+                        return launch_status();
+                    });
                 });
             });
         });

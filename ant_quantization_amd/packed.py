@@ -39,6 +39,23 @@ dtype) -- and runs F.linear on it.  The scratch is valid only until the next suc
 may keep a reference to it (a captured graph is fine, a side stream or autograd through the input is not).  With
 `release_weights=True` such a layer's `weight.data` becomes an empty tensor (the bank remembers the shape): a deep copy
 of such a model has no weights to fall back on, and a forward with the layer's quantiser disabled raises AntqError.  Conv layers and skipped layers behave as without the options.
+
+`fused_rows=R` (with fused_linear; LINEAR4_MAX_M < R <= LINEAR4_MM_MAX_M = 64) extends that to calls of 9 .. R rows of bfloat16 /
+float16 layers: they run `antq_linear4_mm`, the same product on the matrix cores (`.fused_mm_calls` counts them), and with
+`keep_images=False` decode nothing and leave the scratch buffer alone.  Calls of at most 8 rows still run `antq_linear4`,
+float32 layers and every other call keep the path described above.  The two kernels sum in different orders: the same row of x
+has different low bits from a 3-row and from a 9-row call (each within the bound of an fp32 sum, each independent of the other
+rows).  Subnormal weights are kept by the MFMA (measured), so W is the image there too.  Without `fused_rows` nothing changes.
+What the A/B found (profiles/packed_linear_mm.md): one MI355X, one run, M = 8 / 16 / 32 / 64, bf16 and f16, ANT flint-4 and
+OliVe; A = F.linear on the image, C = antq_decode4 into scratch + F.linear, B = antq_linear4_mm.  Largest M up to which B
+beats A / beats C in all four runs, per layer [N, K]: [4096, 4096] A 32, C 64; [16384, 4096] A 64, C 64; [4096, 16384] A 16, C
+64; [3072, 768] A 64, C 64; [768, 3072] A 16, C 32.  At M = 8 B is faster than antq_linear4 in 20 of 20 rows (1.27-1.82x), so
+M = 5 ... 8 would be better served by it (only M = 8 was timed; the routing keeps antq_linear4 up to 8 rows).  B never streams
+the codes at more than 21 % of 8 TB/s; its time grows with M (x is re-read from L2 by every workgroup) and with fewer, larger
+workgroups, and did not change with a deeper load ring: it appears bound by the x stream from L2 at M >= 32 and by parallelism
+and the table look-ups below -- inferred from the scaling, no hardware counters were collected.  Not measured: other M, the
+4-byte code path, per-tensor scales, a whole model, more than one run per point.  The 16-bit MFMA keeps subnormal operands
+(measured): W is the image there too.
 """
 import torch
 import torch.nn.functional as F
@@ -68,10 +85,13 @@ def _settle(q):
 
 
 class PackedBank:
-    def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True):
+    def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True, fused_rows=None):
         """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict)."""
         if not keep_images and not fused_linear:
             raise _lib.AntqError("PackedBank: keep_images=False needs fused_linear=True (nothing else computes from the codes)")
+        _check_fused_rows("PackedBank", fused_linear, fused_rows)
+        self.fused_rows = None if fused_rows is None else int(fused_rows)   # bf16 / f16 calls of 9 .. fused_rows rows: antq_linear4_mm
+        self.fused_mm_calls = 0    # forwards antq_linear4_mm served
         self.model = model
         self.release_weights = bool(release_weights)
         self.fused_linear = bool(fused_linear)   # Linear layers with few input rows compute from the codes (antq_linear4)
@@ -278,15 +298,32 @@ class PackedBank:
             return F.linear(input, weight, mod.bias)
         K = e["shape"][1]
         bias = mod.bias
+        max_rows = _lib.LINEAR4_MAX_M
+        if self.fused_rows is not None and e["dtype"] in (torch.bfloat16, torch.float16):
+            max_rows = self.fused_rows
         if (input.is_cuda and input.dtype == e["dtype"] and input.device == e["device"] and input.dim() >= 1 and input.shape[-1] == K
-                and 0 < input.numel() <= _lib.LINEAR4_MAX_M * K and input.is_contiguous() and input.data_ptr() % 16 == 0
+                and 0 < input.numel() <= max_rows * K and input.is_contiguous() and input.data_ptr() % 16 == 0
                 and not (torch.is_grad_enabled() and (input.requires_grad or (bias is not None and bias.requires_grad)))
                 and (bias is None or (bias.dtype == input.dtype and bias.is_contiguous() and bias.device == input.device))):
             plan, gmax, n_normal, ovp = _codebook(e["q"])
-            self.fused_calls += 1
-            return _lib.linear4(e["codes"], input, e["alpha"], plan.grid_dev(e["device"]), gmax, e["shape"][0], K, e["per_row"],
-                                bias=None if bias is None else bias.detach(), n_normal=n_normal, ovp=ovp)
+            if input.numel() <= _lib.LINEAR4_MAX_M * K:
+                self.fused_calls += 1
+                fn = _lib.linear4
+            else:
+                self.fused_mm_calls += 1
+                fn = _lib.linear4_mm
+            return fn(e["codes"], input, e["alpha"], plan.grid_dev(e["device"]), gmax, e["shape"][0], K, e["per_row"],
+                      bias=None if bias is None else bias.detach(), n_normal=n_normal, ovp=ovp)
         return F.linear(input, weight if e["out"] is not None else self._image(e), bias)
+
+
+def _check_fused_rows(who, fused_linear, fused_rows):
+    if fused_rows is None:
+        return
+    if not fused_linear:
+        raise _lib.AntqError("%s: fused_rows needs fused_linear=True" % who)
+    if not (isinstance(fused_rows, int) and not isinstance(fused_rows, bool) and _lib.LINEAR4_MAX_M < fused_rows <= _lib.LINEAR4_MM_MAX_M):
+        raise _lib.AntqError("%s: fused_rows must be an integer in (%d, %d] (got %r)" % (who, _lib.LINEAR4_MAX_M, _lib.LINEAR4_MM_MAX_M, fused_rows))
 
 
 def _no_auto_bank(model):
@@ -305,12 +342,24 @@ def _bank_of(model):
     return None
 
 
-def pack_model(model, release_weights=False, fused_linear=False, keep_images=True):
+def pack_model(model, release_weights=False, fused_linear=False, keep_images=True, fused_rows=None):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
     (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
     fused_linear: Linear layers called with at most _lib.LINEAR4_MAX_M input rows compute from the codes (antq_linear4);
-    keep_images=False (with fused_linear): those layers keep no decoded image -- see the module docstring."""
-    return PackedBank(model, release_weights=release_weights, fused_linear=fused_linear, keep_images=keep_images)
+    keep_images=False (with fused_linear): those layers keep no decoded image -- see the module docstring.
+    fused_rows=R (with fused_linear, 8 < R <= 64): bf16 / f16 calls of 9 .. R rows compute from the codes on the matrix cores
+    (antq_linear4_mm); a row's low bits differ between the two kernels.
+    Measured (profiles/packed_linear_mm.md): one MI355X, one run, M = 8 / 16 / 32 / 64, bf16 and f16, ANT flint-4 and
+    OliVe; A = F.linear on the image, C = antq_decode4 into scratch + F.linear, B = antq_linear4_mm.  Largest M up to
+    which B beats A / beats C in all four runs, per layer [N, K]: [4096, 4096] A 32, C 64; [16384, 4096] A 64, C 64;
+    [4096, 16384] A 16, C 64; [3072, 768] A 64, C 64; [768, 3072] A 16, C 32.  At M = 8 B is faster than antq_linear4 in
+    20 of 20 rows (1.27-1.82x), so M = 5 ... 8 would be better served by it (only M = 8 was timed; the routing keeps
+    antq_linear4 up to 8 rows).  B never streams the codes at more than 21 % of 8 TB/s; its time grows with M (x is
+    re-read from L2 by every workgroup) and with fewer, larger workgroups, and did not change with a deeper load ring: it
+    appears bound by the x stream from L2 at M >= 32 and by parallelism and the table look-ups below -- inferred from the
+    scaling, no hardware counters were collected.  Not measured: other M, the 4-byte code path, per-tensor scales, a whole
+    model, more than one run per point.  The 16-bit MFMA keeps subnormal operands (measured): W is the image there too."""
+    return PackedBank(model, release_weights=release_weights, fused_linear=fused_linear, keep_images=keep_images, fused_rows=fused_rows)
 
 
 def packed_state_dict(model):
@@ -331,13 +380,14 @@ def _packed_keys(sd, codes):
     return sd
 
 
-def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, keep_images=True):
+def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, keep_images=True, fused_rows=None):
     """Load a packed checkpoint into a freshly wrapped, uncalibrated model living on the GPU: the quantiser state is
     installed the way load_ant_state_dict + load_state_dict do (scales keep the dtype they were stored with), a PackedBank is attached from the stored codes without
     re-encoding, and the weights are materialised by the batched decode (release_weights=False: copied into the layers'
-    own float weights instead of replacing them).  fused_linear / keep_images: as in pack_model.  Returns the bank."""
+    own float weights instead of replacing them).  fused_linear / keep_images / fused_rows: as in pack_model.  Returns the bank."""
     if not keep_images and not fused_linear:
         raise _lib.AntqError("load_packed_state_dict: keep_images=False needs fused_linear=True")
+    _check_fused_rows("load_packed_state_dict", fused_linear, fused_rows)
     suffix = "." + CODES_KEY
     codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}
     rest = {k: v for k, v in sd.items() if not k.endswith(suffix)}
@@ -355,7 +405,8 @@ def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, 
             module.alpha.data = a.detach().clone().to(module.alpha.device)
     for _, _, q, _ in _weight_layers(model):
         _settle(q)
-    bank = PackedBank(model, release_weights=release_weights, codes=codes, fused_linear=fused_linear, keep_images=keep_images)
+    bank = PackedBank(model, release_weights=release_weights, codes=codes, fused_linear=fused_linear, keep_images=keep_images,
+                      fused_rows=fused_rows)
     if not release_weights:
         with torch.no_grad():
             for e in bank.entries.values():

@@ -43,7 +43,8 @@ extern "C" {
  * 7 (round 6): antq_absmax_t / antq_alpha_grad_t (whole-tensor reductions in ONE launch through a caller-owned ticket block,
  * ANTQ_REDUCE_WS_BYTES) and antq_calibrate_install added (nothing else changed).
  * Still 7: antq_decode4_batch_capacity / antq_decode4_batch_build / antq_decode4_batch added (the batched packed decoder; nothing
- * that existed changed, so callers built against 7 keep working).  antq_linear4 (the packed 4-bit linear) added likewise.
+ * that existed changed, so callers built against 7 keep working).  antq_linear4 (the packed 4-bit linear) added likewise,
+ * and antq_linear4_mm (its matrix-core form for up to 64 rows).
  * A caller built against another version must not call in: the blobs / argument lists differ. */
 #define ANTQ_ABI_VERSION 7
 
@@ -500,6 +501,37 @@ int antq_linear4(const uint8_t *codes_dev,          /* N*K/2 bytes, antq_encode4
                  const float *grid_dev, int m, int n_normal,   /* as in antq_decode_job */
                  unsigned flags /* 0 | ANTQ_FLAG_OVP */, int dtype /* F32 | BF16 | F16 */, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * The same product for 1 .. ANTQ_LINEAR4_MM_MAX_M rows of x on the matrix cores (v_mfma_f32_16x16x32_bf16 / _f16), BF16 and
+ * F16 only.  Parameters as antq_linear4.
+ *   W[n,k] is, bit for bit, the element antq_decode4 writes in `dtype` (the decoder's byte table is the MFMA operand; the scale
+ *          is never factored out of the sum).
+ *   y[m,n] = round_dtype( sum_k x[m,k] * W[n,k] + bias[n] ): products exact, the sum in fp32 in the MFMA accumulator, the bias
+ *          added in fp32, one rounding to `dtype`.
+ *   The bits of y[m,n] depend only on row m of x, row n of W, bias[n], K and the code path (below): not on M, not on N, not on
+ *          the other rows of x, not on the run.  K is split between the eight wavefronts of a workgroup by a rule of K alone and
+ *          their partial sums are combined through LDS in one fixed order.  The order of the sum is NOT antq_linear4's: the
+ *          same row has different low bits from the two entry points (both within the bound of an fp32 sum).
+ *   No floating-point atomics, no split of K across workgroups, no workspace, no allocation, no synchronisation: stream-ordered
+ *          and capturable into a graph.  Reads stay inside the buffers; padded rows contribute exactly +0 and are not stored.
+ *   Subnormal bf16 / f16 weights and inputs are kept by the 16-bit MFMA on gfx950 (measured on an MI355X: a one-hot x returns the
+ *          image's subnormal elements bit for bit), so W is the image there too: there is no departure to state.
+ * Checked before anything touches HIP, in this order:
+ *   ANTQ_ERR_ARG          as antq_linear4
+ *   ANTQ_OK, no launch    M == 0 or N == 0
+ *   ANTQ_ERR_UNSUPPORTED  dtype == ANTQ_F32 (the f32-input MFMA runs at the vector rate: such layers stay with antq_linear4);
+ *                         M > ANTQ_LINEAR4_MM_MAX_M; K == 0 or K % 8 != 0; the decoder's refusals; N >= 2^31 or K >= 2^31
+ *   ANTQ_ERR_ALIGN        as antq_linear4
+ * Codes are read 16 bytes per lane when K % 32 == 0 and codes_dev is 16-byte aligned, 4 bytes per lane otherwise (the order
+ * of the sum differs between the two, nothing else).  Measurements: profiles/packed_linear_mm.md.
+ * ------------------------------------------------------------------------- */
+#define ANTQ_LINEAR4_MM_MAX_M 64
+int antq_linear4_mm(const uint8_t *codes_dev, const void *x_dev, const void *bias_dev, void *y_dev,
+                    size_t M, size_t N, size_t K,
+                    const float *alpha_dev, int alpha_per_row, float gmax,
+                    const float *grid_dev, int m, int n_normal,
+                    unsigned flags /* 0 | ANTQ_FLAG_OVP */, int dtype /* BF16 | F16 */, void *stream);
+
 /* -------------------------------------------------------------------------
  * OliVe's clip statistic on ONE read (replaces t.mean() + t.std() of olive_quantization/antquant/quant_modules.py:193-197
  * and :213-218, which read the tensor at least three times before the clip search reads it again).
@@ -554,7 +586,8 @@ int antq_copy(const void *src_dev, void *dst_dev, size_t bytes, void *stream);
  *   key 20: the sorted-row clip search (round 6: per-row searches from rows of 128 elements, OliVe's pair rule from 576, fp32
  *           tensors with one scale from 1 M elements): 0 off, 1 (default), 2 every eligible launch (rows from 128 elements
  *           with or without the pair rule, one-scale fp32 tensors from 4096)
- *   key 21: 0 sends rows of <= 1024 elements through the 4096-key kernel instead of one row per wavefront (A/B) */
+ *   key 21: 0 sends rows of <= 1024 elements through the 4096-key kernel instead of one row per wavefront (A/B)
+ *   key 22: antq_linear4_mm: tiles of 16 output rows per workgroup, 1 / 2 / 4 (A/B; 0 = the launcher's rule; no result changes) */
 int antq_debug_set(int key, int value);
 
 /* Load the library's GPU code objects for the current device now (HIP would load each of them at the first launch of one
