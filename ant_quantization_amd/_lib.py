@@ -61,10 +61,12 @@ def lib():
                              "antq_search_sse_multi", "antq_plan_eval_host_a", "antq_moments", "antq_xmax_3sigma",
                              "antq_calibrate", "antq_prefetch_kernels", "antq_plan_eval_host_h", "antq_calibrate_batch", "antq_absmax_into", "antq_fakequant_f64",
                              "antq_absmax_t", "antq_alpha_grad_t", "antq_calibrate_install", "antq_decode4_batch_build", "antq_decode4_batch",
-                             "antq_linear4", "antq_linear4_mm"):
+                             "antq_linear4", "antq_linear4_mm", "antq_encode8", "antq_decode8", "antq_decode8_batch_build",
+                             "antq_decode8_batch"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
                 L.antq_decode4_batch_capacity.restype = ctypes.c_size_t
+                L.antq_decode8_batch_capacity.restype = ctypes.c_size_t
                 L.antq_search_workspace_bytes.restype = ctypes.c_size_t
                 L.antq_calibrate_workspace_bytes.restype = ctypes.c_size_t
                 L.antq_calibrate_batch_workspace_bytes.restype = ctypes.c_size_t
@@ -921,6 +923,48 @@ def decode4(codes, alpha, plan, gmax, rows, row_len, per_row, dtype, n_normal=0,
     return out.view(rows, row_len)
 
 
+def encode8(x, alpha, plan, gmax, rows, row_len, per_row, n_normal=0, ovp=False, out=None):
+    """Byte codes (one per element; OliVe's identifier is 255) of the quantised tensor: uint8 tensor of numel bytes.
+    out: a caller-owned buffer for them (a view at any byte offset will do)."""
+    _require_gpu(x, "x")
+    dt = _DTYPES.get(x.dtype)
+    if dt is None or dt == F64:
+        raise AntqError("unsupported dtype %s" % x.dtype)
+    if out is None:
+        codes = torch.empty(x.numel(), dtype=torch.uint8, device=x.device)
+    elif not (out.is_cuda and out.device == x.device and out.dtype == torch.uint8 and out.numel() == x.numel() and out.is_contiguous()):
+        raise AntqError("out must be a contiguous uint8 tensor of numel bytes on x's device")
+    else:
+        codes = out
+    pd = plan.dev(x.device)
+    with _on_device(x.device):
+        rc = lib().antq_encode8(_vp(x), _vp(codes), ctypes.c_size_t(rows), ctypes.c_size_t(row_len), _vp(alpha),
+                                ctypes.c_int(1 if per_row else 0), ctypes.c_float(gmax), plan.host_ptr(), _vp(pd),
+                                ctypes.c_int(n_normal), ctypes.c_uint(FLAG_OVP if ovp else 0), ctypes.c_int(dt),
+                                _stream(x.device))
+    _check(rc, "antq_encode8")
+    return codes
+
+
+def decode8(codes, alpha, plan, gmax, rows, row_len, per_row, dtype, n_normal=0, ovp=False, out=None):
+    _require_gpu(codes, "codes")
+    dt = _DTYPES.get(dtype)
+    if dt is None or dt == F64:
+        raise AntqError("unsupported dtype %s" % dtype)
+    if out is None:
+        out = torch.empty(rows * row_len, dtype=dtype, device=codes.device)
+    elif not (out.is_cuda and out.device == codes.device and out.dtype == dtype and out.numel() == rows * row_len and out.is_contiguous()):
+        raise AntqError("out must be a contiguous tensor of rows*row_len elements of `dtype` on the codes' device")
+    pd = plan.dev(codes.device)
+    with _on_device(codes.device):
+        rc = lib().antq_decode8(_vp(codes), _vp(out), ctypes.c_size_t(rows), ctypes.c_size_t(row_len), _vp(alpha),
+                                ctypes.c_int(1 if per_row else 0), ctypes.c_float(gmax), plan.host_ptr(), _vp(pd),
+                                ctypes.c_int(n_normal), ctypes.c_uint(FLAG_OVP if ovp else 0), ctypes.c_int(dt),
+                                _stream(codes.device))
+    _check(rc, "antq_decode8")
+    return out.view(rows, row_len)
+
+
 def _linear4_call(entry, max_m, allow_f32, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out):
     _require_gpu(x, "x")
     _require_gpu(codes, "codes")
@@ -1095,9 +1139,15 @@ class DecodeBatch:
     jobs: iterable of tuples (codes, out, alpha, plan, gmax, rows, row_len, per_row, n_normal); codes uint8 of
     rows * row_len / 2 bytes, alpha float32, all tensors on one device, every `out` of one dtype (float32 / bfloat16 /
     float16).  ovp: OliVe's pair rule for every job (n_normal is read only then).  Each job has its own codebook.  Jobs
-    with unaligned buffers ride in the same launch.  The descriptor table is built once and stays resident."""
+    with unaligned buffers ride in the same launch.  The descriptor table is built once and stays resident.
+    width=8: byte codes (antq_decode8_batch), codes of rows * row_len bytes."""
 
-    def __init__(self, jobs, ovp=False):
+    def __init__(self, jobs, ovp=False, width=4):
+        if width not in (4, 8):
+            raise AntqError("width must be 4 or 8")
+        self.width = width
+        per_byte = 2 if width == 4 else 1
+        entry = "antq_decode%d_batch" % width
         jobs = [tuple(j) for j in jobs]
         if not jobs:
             raise AntqError("empty batch")
@@ -1116,25 +1166,26 @@ class DecodeBatch:
                     raise AntqError("every tensor of a batch must live on one device")
             if out.dtype != o0.dtype:
                 raise AntqError("every out of a decode batch must have one dtype")
-            if codes.dtype != torch.uint8 or codes.numel() * 2 != rows * row_len or out.numel() != rows * row_len:
-                raise AntqError("codes must be uint8 of rows*row_len/2 bytes, out rows*row_len elements")
+            if codes.dtype != torch.uint8 or codes.numel() * per_byte != rows * row_len or out.numel() != rows * row_len:
+                raise AntqError("codes must be uint8 of rows*row_len%s bytes, out rows*row_len elements" % ("/2" if width == 4 else ""))
             if alpha.dtype != torch.float32 or alpha.numel() < (rows if per_row else 1):
                 raise AntqError("alpha must be float32, one per row (per_row) or one")
             arr[k] = _DecodeJob(codes.data_ptr(), out.data_ptr(), alpha.data_ptr(), rows, row_len, 1 if per_row else 0, gmax,
                                 plan.grid_dev(self.device).data_ptr(), plan.grid.size, n_normal)
         flags = FLAG_OVP if ovp else 0
-        cap = lib().antq_decode4_batch_capacity(arr, len(jobs), self.dtype)
+        cap = getattr(lib(), entry + "_capacity")(arr, len(jobs), self.dtype)
         host = np.zeros(max(cap, 1), dtype=np.uint8)
-        n = lib().antq_decode4_batch_build(arr, len(jobs), self.dtype, ctypes.c_uint(flags),
-                                           host.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(cap))
+        n = getattr(lib(), entry + "_build")(arr, len(jobs), self.dtype, ctypes.c_uint(flags),
+                                            host.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(cap))
         if n <= 0:
-            _check(n if n < 0 else -1, "antq_decode4_batch_build")
+            _check(n if n < 0 else -1, entry + "_build")
+        self._launch, self._name = getattr(lib(), entry), entry
         self.host = host[:n].copy()
         self.dev = torch.from_numpy(self.host).to(self.device)
 
     def run(self):
         with _on_device(self.device):
-            rc = lib().antq_decode4_batch(ctypes.c_void_p(self.host.ctypes.data), ctypes.c_void_p(self.dev.data_ptr()),
-                                          ctypes.c_void_p(_stream_int(self.device)))
+            rc = self._launch(ctypes.c_void_p(self.host.ctypes.data), ctypes.c_void_p(self.dev.data_ptr()),
+                              ctypes.c_void_p(_stream_int(self.device)))
         if rc:
-            _check(rc, "antq_decode4_batch")
+            _check(rc, self._name)

@@ -4,6 +4,7 @@
 #include "antq_dispatch.h"
 #include "antq_k_batch.h"
 #include "antq_k_decbatch.h"
+#include "antq_k_decbatch8.h"
 #include "antq_k_linear4.h"
 #include "antq_k_linear4_mm.h"
 
@@ -379,6 +380,53 @@ extern "C" int antq_decode4_batch(const void *batch_host, const void *batch_dev,
     return with_dtype((int)h->dtype, [&](auto tag) {
         return with_bool((h->flags & ANTQ_FLAG_OVP) != 0, [&](auto ovp) {
             hipLaunchKernelGGL((k_decode4_batch<decltype(tag), decltype(ovp)::value>), dim3(h->total_blocks * 4u), dim3(64u), 0, st, descs, map);
+            return launch_status();
+        });
+    });
+}
+
+// The byte-code decoder (antq_k_decbatch8.h).  One tensor: its descriptor is built here with the batch builder's own rule
+// (antq_decbatch8.h) and passed by value -- no blob, no workspace; every refusal comes before anything touches HIP.
+extern "C" int antq_decode8(const uint8_t *codes, void *out, size_t rows, size_t row_len, const float *alpha, int per_row,
+                            float gmax, const void *plan_host, const void *plan_dev, int n_normal, unsigned flags,
+                            int dtype, void *stream)
+{
+    if (!codes || !out || !alpha || !plan_host || !plan_dev) return ANTQ_ERR_ARG;
+    if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
+    if (rows == 0 || row_len == 0) return ANTQ_ERR_ARG;
+    PlanArgs pa;
+    if (!plan_args_from_host(plan_host, pa)) return ANTQ_ERR_PLAN;
+    antq_decode_job J;
+    memset(&J, 0, sizeof(J));
+    J.codes_dev = codes; J.out_dev = out; J.alpha_dev = alpha; J.rows = rows; J.row_len = row_len;
+    J.alpha_per_row = per_row ? 1 : 0; J.gmax = gmax;
+    J.grid_dev = reinterpret_cast<const float *>(plan_tab_ptr(plan_dev));
+    J.m = (int)pa.m; J.n_normal = n_normal;
+    DecDesc D;
+    const long long tasks = dec8_job_tasks(J, dtype, flags, &D);
+    if (tasks < 0) return (int)tasks;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return with_dtype(dtype, [&](auto tag) {
+        return with_bool((flags & ANTQ_FLAG_OVP) != 0, [&](auto ovp) {
+            hipLaunchKernelGGL((k_decode8<decltype(tag), decltype(ovp)::value>), dim3((unsigned)tasks), dim3(64u), 0, st, D);
+            return launch_status();
+        });
+    });
+}
+
+extern "C" int antq_decode8_batch(const void *batch_host, const void *batch_dev, void *stream)
+{
+    if (!batch_host || !batch_dev) return ANTQ_ERR_ARG;
+    const DecHeader *h = static_cast<const DecHeader *>(batch_host);
+    if (h->magic != kDec8Magic) return ANTQ_ERR_PLAN;
+    if (h->total_blocks == 0) return ANTQ_OK;
+    const char *pd = static_cast<const char *>(batch_dev);
+    const DecDesc *descs = reinterpret_cast<const DecDesc *>(pd + sizeof(DecHeader));
+    const uint32_t *map = reinterpret_cast<const uint32_t *>(pd + h->map_offset);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return with_dtype((int)h->dtype, [&](auto tag) {
+        return with_bool((h->flags & ANTQ_FLAG_OVP) != 0, [&](auto ovp) {
+            hipLaunchKernelGGL((k_decode8_batch<decltype(tag), decltype(ovp)::value>), dim3(h->total_blocks * 4u), dim3(64u), 0, st, descs, map);
             return launch_status();
         });
     });

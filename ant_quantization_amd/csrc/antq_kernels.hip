@@ -487,3 +487,24 @@ extern "C" int antq_decode4(const uint8_t *codes, void *out, size_t rows, size_t
 }
 
 
+// ======================================================================================
+// Byte-code encoder (antq_encode8; the decoder lives with the batched launch, antq_batch.hip)
+// ======================================================================================
+#include "antq_k_codec8.h"
+
+extern "C" int antq_encode8(const void *x, uint8_t *codes, size_t rows, size_t row_len, const float *alpha, int per_row,
+                            float gmax, const void *plan_host, const void *plan_dev, int n_normal, unsigned flags,
+                            int dtype, void *stream)
+{
+    if (!x || !codes || !alpha || !plan_host || !plan_dev) return ANTQ_ERR_ARG;
+    if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
+    if (rows == 0 || row_len == 0) return ANTQ_ERR_ARG;
+    if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_UNSUPPORTED;
+    PlanArgs pa;
+    if (!plan_args_from_host(plan_host, pa)) return ANTQ_ERR_PLAN;
+    const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return with_dtype(dtype, [&](auto tag) {
+        return launch_encode8<decltype(tag)>(x, codes, rows, row_len, alpha, per_row ? 1 : 0, gmax, pa, plan_host, plan_dev, n_normal, ovp, st);
+    });
+}

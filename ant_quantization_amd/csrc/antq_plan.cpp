@@ -28,6 +28,7 @@
 #include "../../include/antq.h"
 #include "antq_internal.h"
 #include "antq_decbatch.h"
+#include "antq_decbatch8.h"
 
 namespace antq {
 namespace {
@@ -832,4 +833,15 @@ extern "C" size_t antq_decode4_batch_capacity(const antq_decode_job *jobs, int n
 extern "C" int antq_decode4_batch_build(const antq_decode_job *jobs, int n, int dtype, unsigned flags, void *batch_host, size_t capacity)
 {
     return antq::dec_batch_build(jobs, n, dtype, flags, batch_host, capacity);
+}
+
+// The byte-code decoder's blob (antq_decbatch8.h): the same, one code per byte.
+extern "C" size_t antq_decode8_batch_capacity(const antq_decode_job *jobs, int n, int dtype)
+{
+    return antq::dec8_batch_capacity(jobs, n, dtype);
+}
+
+extern "C" int antq_decode8_batch_build(const antq_decode_job *jobs, int n, int dtype, unsigned flags, void *batch_host, size_t capacity)
+{
+    return antq::dec8_batch_build(jobs, n, dtype, flags, batch_host, capacity);
 }

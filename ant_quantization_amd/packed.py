@@ -56,6 +56,20 @@ workgroups, and did not change with a deeper load ring: it appears bound by the 
 and the table look-ups below -- inferred from the scaling, no hardware counters were collected.  Not measured: other M, the
 4-byte code path, per-tensor scales, a whole model, more than one run per point.  The 16-bit MFMA keeps subnormal operands
 (measured): W is the image there too.
+
+`byte_codes=True` (pack_model, PackedBank; off by default -- without it everything above is unchanged): a layer the 4-bit codec
+refuses for its codebook (the 5- to 8-bit layers of `set_8_bit_layer_n/_l`, OliVe's unsigned 16 + 15 values) or for its row
+length (4 mod 8, such as 20) and that the byte codec accepts -- at most 256 values, with OliVe at most 255 normal and 255 outlier
+values, rows of a multiple of 4 elements -- is encoded with `antq_encode8`, one code per byte, 255 the pair identifier: an entry
+with `width == 8`.  Layers the 4-bit codec accepts keep 4-bit codes.  What stays in `.skipped`: rows that are no multiple of 4
+(conv1: K = 147), `base` / `outlier` modes, float64, quantisers that are disabled or not calibrated.  Byte-coded layers are decoded
+by `antq_decode8_batch`, one more launch per (device, dtype, pair rule) group (`.launches` counts it).  The linear-from-codes
+kernels (`antq_linear4`, `antq_linear4_mm`) do not take byte codes: such a layer is never fusable, always keeps its decoded image
+(also under `keep_images=False`) and runs F.linear on it.  `release_weights`, `nbytes()` and the gradient error work on it as on
+any image-keeping layer.  `packed_state_dict` writes its codes as numel bytes; `load_packed_state_dict` takes the width from the
+stored size (numel / 2: 4-bit, numel: bytes; anything else raises AntqError naming the layer).  Measured
+(profiles/packed_bytes.md): BERT-base's 74 Linear layers with 8 pairs at 8 bit -- 0 instead of 8 weight launches per forward,
+checkpoint 48.9 instead of 60.1 MB, resident bytes 219.4 instead of 208.2 MB (codes are added, the image replaces the float weight).
 """
 import torch
 import torch.nn.functional as F
@@ -85,8 +99,12 @@ def _settle(q):
 
 
 class PackedBank:
-    def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True, fused_rows=None):
-        """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict)."""
+    def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True, fused_rows=None,
+                 byte_codes=False):
+        """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict);
+        a layer's code width is then the one its stored size says (numel / 2 bytes: 4-bit, numel bytes: byte codes).
+        byte_codes: layers the 4-bit codec refuses and the byte codec accepts are packed one code per byte (width 8)."""
+        self.byte_codes = bool(byte_codes)
         if not keep_images and not fused_linear:
             raise _lib.AntqError("PackedBank: keep_images=False needs fused_linear=True (nothing else computes from the codes)")
         _check_fused_rows("PackedBank", fused_linear, fused_rows)
@@ -100,13 +118,21 @@ class PackedBank:
         self._scratch = {}         # (device, dtype) -> the one decode buffer of the layers without an image
         self.entries = {}          # id(quantiser) -> dict
         self.skipped = []          # (layer name, reason): layers that keep their float weight and per-layer launch
-        self.launches = 0          # decode launches so far (one per (device, dtype, pair rule) group and refresh)
+        self.launches = 0          # decode launches so far (one per (device, dtype, pair rule, code width) group and refresh)
         self.dirty = True
         self._batches = []
         self._ptr_key = None
         try:
             for name, mod, q, w in _weight_layers(model):
-                reason = self._unsuitable(q, w)
+                if codes is not None and name in codes:
+                    # stored codes say their own width; the layer has to be packable at that width
+                    nc = int(codes[name].numel())
+                    if codes[name].dtype != torch.uint8 or (nc * 2 != w.numel() and nc != w.numel()):
+                        raise _lib.AntqError("PackedBank: codes of layer %s must be uint8 of numel/2 bytes (4-bit) or numel bytes "
+                                             "(byte codes); got %d %s values for %d elements" % (name, nc, codes[name].dtype, w.numel()))
+                    width, reason = self._width(q, w, only=8 if nc == w.numel() else 4)
+                else:
+                    width, reason = self._width(q, w, byte_codes=self.byte_codes)
                 if reason is None and codes is not None and name not in codes:
                     reason = "no codes in the checkpoint"
                 if reason:
@@ -119,15 +145,15 @@ class PackedBank:
                 plan, gmax, n_normal, ovp = _codebook(q)
                 if codes is not None:
                     c = codes[name].to(w.device).contiguous()
-                    if c.dtype != torch.uint8 or c.numel() * 2 != w.numel():
-                        raise _lib.AntqError("PackedBank: codes of layer %s must be uint8 of numel/2 bytes" % name)
                 else:
                     with torch.no_grad():
                         alpha = q.alpha.detach().reshape(-1).to(torch.float32).contiguous()
-                        c = _lib.encode4(w.detach(), alpha, plan, gmax, rows, row_len, per_row, n_normal=n_normal, ovp=ovp)
-                fusable = self.fused_linear and w.dim() == 2 and getattr(mod, "in_features", None) == w.shape[1] and w.shape[1] % 8 == 0
+                        enc = _lib.encode4 if width == 4 else _lib.encode8
+                        c = enc(w.detach(), alpha, plan, gmax, rows, row_len, per_row, n_normal=n_normal, ovp=ovp)
+                # (the linear-from-codes kernels take 4-bit codes only: a byte-coded layer always keeps its image)
+                fusable = width == 4 and self.fused_linear and w.dim() == 2 and getattr(mod, "in_features", None) == w.shape[1] and w.shape[1] % 8 == 0
                 image = self.keep_images or not fusable
-                self.entries[id(q)] = dict(name=name, q=q, mod=mod, rows=rows, row_len=row_len, per_row=per_row, codes=c,
+                self.entries[id(q)] = dict(name=name, q=q, mod=mod, rows=rows, row_len=row_len, per_row=per_row, codes=c, width=width,
                                            fusable=fusable, shape=tuple(w.shape), dtype=w.dtype, device=w.device,
                                            out=torch.empty_like(w, memory_format=torch.contiguous_format) if image else None)
             if not self.entries:
@@ -150,32 +176,59 @@ class PackedBank:
         return (type(None), ())
 
     @staticmethod
-    def _unsuitable(q, w):
+    def _unsuitable(q, w, byte_codes=False):
         """Why this layer stays float (None: it can be packed).  What the codec refuses comes first, where the weight lives
         last: the answer for a model's layers is the same before and after it moved to the GPU."""
+        return PackedBank._width(q, w, byte_codes=byte_codes)[1]
+
+    @staticmethod
+    def _width(q, w, byte_codes=False, only=None):
+        """(code width, None) of a layer that can be packed -- 4 where the 4-bit codec takes it, 8 (byte_codes only) where
+        that one refuses the codebook or the row length and the byte codec does not -- or (None, why it stays float).
+        only: the width stored codes have; the layer has to be packable at exactly that one."""
         if q.mode in ("base", "outlier"):
-            return "mode %s" % q.mode
+            return None, "mode %s" % q.mode
         if not (q.is_enable and q.is_enable_weight):
-            return "quantisation disabled"
+            return None, "quantisation disabled"
         if not q._steady:
-            return "not calibrated yet"
+            return None, "not calibrated yet"
         if w.dtype not in _lib._DTYPES or w.dtype == torch.float64:
-            return "dtype %s" % w.dtype
+            return None, "dtype %s" % w.dtype
         row_len = w.numel() // w.shape[0] if q.is_perchannel else w.numel()
-        if row_len == 0 or row_len % 8 != 0:
-            return "row length %d is not a multiple of 8" % row_len
-        plan, _, n_normal, ovp = _codebook(q)
-        m = int(plan.grid.size)
-        if ovp:
-            if n_normal > 15:
-                return "%d normal values leave no code for the pair identifier" % n_normal
-            if m - n_normal > 15:
-                return "%d outlier values (the 4-bit codec holds 15)" % (m - n_normal)
-        elif m > 16:
-            return "codebook of %d values (the 4-bit codec holds 16)" % m
+
+        def refusal(nibble):
+            if row_len == 0 or row_len % (8 if nibble else 4) != 0:
+                return "row length %d is not a multiple of %d" % (row_len, 8 if nibble else 4)
+            plan, _, n_normal, ovp = _codebook(q)
+            m = int(plan.grid.size)
+            if nibble:
+                if ovp:
+                    if n_normal > 15:
+                        return "%d normal values leave no code for the pair identifier" % n_normal
+                    if m - n_normal > 15:
+                        return "%d outlier values (the 4-bit codec holds 15)" % (m - n_normal)
+                elif m > 16:
+                    return "codebook of %d values (the 4-bit codec holds 16)" % m
+            elif ovp:
+                if n_normal > 255:
+                    return "%d normal values leave no byte code for the pair identifier" % n_normal
+                if m - n_normal > 255:
+                    return "%d outlier values (the byte codec holds 255)" % (m - n_normal)
+            elif m > 256:
+                return "codebook of %d values (the byte codec holds 256)" % m
+            return None
+
+        if only == 8:
+            width, reason = 8, refusal(False)
+        else:
+            width, reason = 4, refusal(True)
+            if reason is not None and byte_codes and only is None:
+                width, reason = 8, refusal(False)
+        if reason is not None:
+            return None, reason
         if not w.is_cuda or not w.is_contiguous():
-            return "weight not resident / not contiguous"
-        return None
+            return None, "weight not resident / not contiguous"
+        return width, None
 
     # ------------------------------------------------------------------ bookkeeping
     def invalidate(self):
@@ -202,7 +255,7 @@ class PackedBank:
                       id(e["q"]._ensure_plan()), e["q"]._gmax) for e in self.entries.values())
 
     def _build(self):
-        """(Re)build the descriptor tables: one batch per (device, dtype, pair rule)."""
+        """(Re)build the descriptor tables: one batch per (device, dtype, pair rule, code width)."""
         groups, need = {}, {}
         for e in self.entries.values():
             q, w = e["q"], e["mod"].weight
@@ -221,9 +274,9 @@ class PackedBank:
             if e["out"] is None:           # no image: the codes are the weight (linear); one scratch per (device, dtype) stands in
                 need[(w.device, w.dtype)] = max(need.get((w.device, w.dtype), 0), e["rows"] * e["row_len"])
                 continue
-            groups.setdefault((w.device, w.dtype, ovp), []).append(
+            groups.setdefault((w.device, w.dtype, ovp, e["width"]), []).append(
                 (e["codes"], e["out"], alpha, plan, gmax, e["rows"], e["row_len"], e["per_row"], n_normal))
-        self._batches = [_lib.DecodeBatch(jobs, ovp=ovp) for (_, _, ovp), jobs in groups.items()]
+        self._batches = [_lib.DecodeBatch(jobs, ovp=ovp, width=width) for (_, _, ovp, width), jobs in groups.items()]
         self._scratch = {k: (self._scratch[k] if k in self._scratch and self._scratch[k].numel() == n
                              else torch.empty(n, dtype=k[1], device=k[0])) for k, n in need.items()}
         self._ptr_key = self._pointers()
@@ -259,8 +312,8 @@ class PackedBank:
         if training is None:
             training = torch.is_grad_enabled() and (tensor.requires_grad or q.alpha.requires_grad)
         if training:
-            raise _lib.AntqError("layer %s is packed: its weight exists as 4-bit codes, there is no float weight to train "
-                                 "(run the forward under torch.no_grad())" % e["name"])
+            raise _lib.AntqError("layer %s is packed: its weight exists as %s codes, there is no float weight to train "
+                                 "(run the forward under torch.no_grad())" % (e["name"], "4-bit" if e["width"] == 4 else "byte"))
         if not q._steady or not (q.is_enable and q.is_enable_weight):
             return None
         if self.dirty or e["dtype"] != tensor.dtype or e["device"] != tensor.device:
@@ -342,9 +395,12 @@ def _bank_of(model):
     return None
 
 
-def pack_model(model, release_weights=False, fused_linear=False, keep_images=True, fused_rows=None):
+def pack_model(model, release_weights=False, fused_linear=False, keep_images=True, fused_rows=None, byte_codes=False):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
     (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
+    byte_codes: layers the 4-bit codec refuses for their codebook (5- to 8-bit layers, OliVe's unsigned 16 + 15) or their row
+    length (4 mod 8) are packed one code per byte (entries of width 8, one more decode launch per group); they always keep
+    their decoded image and run F.linear on it -- the linear-from-codes kernels below take 4-bit codes only.
     fused_linear: Linear layers called with at most _lib.LINEAR4_MAX_M input rows compute from the codes (antq_linear4);
     keep_images=False (with fused_linear): those layers keep no decoded image -- see the module docstring.
     fused_rows=R (with fused_linear, 8 < R <= 64): bf16 / f16 calls of 9 .. R rows compute from the codes on the matrix cores
@@ -359,7 +415,8 @@ def pack_model(model, release_weights=False, fused_linear=False, keep_images=Tru
     appears bound by the x stream from L2 at M >= 32 and by parallelism and the table look-ups below -- inferred from the
     scaling, no hardware counters were collected.  Not measured: other M, the 4-byte code path, per-tensor scales, a whole
     model, more than one run per point.  The 16-bit MFMA keeps subnormal operands (measured): W is the image there too."""
-    return PackedBank(model, release_weights=release_weights, fused_linear=fused_linear, keep_images=keep_images, fused_rows=fused_rows)
+    return PackedBank(model, release_weights=release_weights, fused_linear=fused_linear, keep_images=keep_images, fused_rows=fused_rows,
+                      byte_codes=byte_codes)
 
 
 def packed_state_dict(model):
@@ -383,8 +440,9 @@ def _packed_keys(sd, codes):
 def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, keep_images=True, fused_rows=None):
     """Load a packed checkpoint into a freshly wrapped, uncalibrated model living on the GPU: the quantiser state is
     installed the way load_ant_state_dict + load_state_dict do (scales keep the dtype they were stored with), a PackedBank is attached from the stored codes without
-    re-encoding, and the weights are materialised by the batched decode (release_weights=False: copied into the layers'
-    own float weights instead of replacing them).  fused_linear / keep_images / fused_rows: as in pack_model.  Returns the bank."""
+    re-encoding (a layer's code width is the one its stored size says: numel / 2 bytes are 4-bit codes, numel bytes byte codes;
+    any other size raises AntqError naming the layer), and the weights are materialised by the batched decode
+    (release_weights=False: copied into the layers' own float weights instead of replacing them).  fused_linear / keep_images / fused_rows: as in pack_model.  Returns the bank."""
     if not keep_images and not fused_linear:
         raise _lib.AntqError("load_packed_state_dict: keep_images=False needs fused_linear=True")
     _check_fused_rows("load_packed_state_dict", fused_linear, fused_rows)

@@ -44,7 +44,8 @@ extern "C" {
  * ANTQ_REDUCE_WS_BYTES) and antq_calibrate_install added (nothing else changed).
  * Still 7: antq_decode4_batch_capacity / antq_decode4_batch_build / antq_decode4_batch added (the batched packed decoder; nothing
  * that existed changed, so callers built against 7 keep working).  antq_linear4 (the packed 4-bit linear) added likewise,
- * and antq_linear4_mm (its matrix-core form for up to 64 rows).
+ * and antq_linear4_mm (its matrix-core form for up to 64 rows), and antq_encode8 / antq_decode8 / antq_decode8_batch_capacity /
+ * antq_decode8_batch_build / antq_decode8_batch (the byte-code codec).
  * A caller built against another version must not call in: the blobs / argument lists differ. */
 #define ANTQ_ABI_VERSION 7
 
@@ -468,6 +469,47 @@ size_t antq_decode4_batch_capacity(const antq_decode_job *jobs, int n, int dtype
 int    antq_decode4_batch_build(const antq_decode_job *jobs, int n, int dtype, unsigned flags,
                                 void *batch_host, size_t capacity);
 int    antq_decode4_batch(const void *batch_host, const void *batch_dev, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Byte codes: the same codec with ONE code per byte, for the 5- to 8-bit layers of mixed-precision models (books of up to
+ * 256 values) and for rows the 4-bit codec refuses (row_len % 8 == 4).  Element i of the flat tensor is byte i.
+ *   plain books: 1 <= m <= 256; code = scan-order grid index of the element (what antq_fakequant's idx output holds).
+ * With ANTQ_FLAG_OVP the grid is cat(normal[n_normal], outliers) with 1 <= n_normal <= 255 and 0 <= m - n_normal <= 255:
+ *   normal value  -> its index 0..n_normal-1
+ *   victim        -> 255, the identifier
+ *   outlier       -> index INTO THE OUTLIER LIST (0..254); the partner byte of the pair is 255.
+ * The pair rule and the outlier test (|v| > 32) are antq_encode4's, on the flat pairs (2k, 2k + 1); an element outside the
+ * scan's validity range (ANTQ_IDX_NONE) encodes as the last grid entry (ANTQ_FLAG_OVP: normal entry) holding 0.0.
+ * antq_decode8 writes fl((g[c] + 0.0f) * (alpha / gmax)), the scale formed in the kernel in fp32, bf16 / f16 rounded to nearest
+ * even; a victim decodes to +0, and so does a code beyond the book (a byte >= m; with ANTQ_FLAG_OVP a byte >= n_normal other
+ * than 255, or an outlier index >= m - n_normal).  As for the 4-bit codec, decode8(encode8(x)) is bit-identical to
+ * antq_fakequant(x) whenever the reference's straight-through step ((q - d) + d) is exact: every ANT / OliVe codebook
+ * (adjacent magnitudes within a factor of two: the plan builder's x-domain eligibility) and finite inputs within twice the
+ * outermost grid values; for arbitrary value lists the two may differ by one ulp.
+ * Refusals, all before anything is launched: row_len % 4 != 0 or a book outside the bounds above: ANTQ_ERR_UNSUPPORTED (so is
+ * F64 or any other dtype); a null pointer or an empty tensor: ANTQ_ERR_ARG; a flag other than ANTQ_FLAG_OVP: ANTQ_ERR_ARG;
+ * x_dev / out_dev not aligned to its element: ANTQ_ERR_ALIGN; (batch) capacity too small: ANTQ_ERR_PLAN.
+ * codes_dev: rows*row_len bytes, any alignment.  With row_len % 4 == 0 a code word lies inside one row and a pair never
+ * crosses a row.  Codes that are not 4-byte aligned, outputs that are not 16-byte aligned and 16-bit rows of 4 mod 8 elements
+ * run element-granular (inside the same launch, in a batch).  x: F32 / BF16 / F16, read 16 bytes per lane when x_dev is
+ * 16-byte aligned.  The encoder is the element encoder of antq_encode4 (no row-table, no 16-bit-domain form).
+ * The batch entry points are antq_decode4_batch's with antq_decode_job as it is -- codes_dev holds rows*row_len bytes --
+ * and the same rules for n, flags and n_normal; the builder is pure host code and touches no HIP.  All launches are
+ * stream-ordered and capturable: no allocation, no synchronisation, no workspace.  The packed linears (antq_linear4,
+ * antq_linear4_mm) do not take byte codes.
+ * ------------------------------------------------------------------------- */
+int antq_encode8(const void *x_dev, uint8_t *codes_dev, size_t rows, size_t row_len,
+                 const float *alpha_dev, int alpha_per_row, float gmax,
+                 const void *plan_host, const void *plan_dev, int n_normal,
+                 unsigned flags, int dtype, void *stream);
+int antq_decode8(const uint8_t *codes_dev, void *out_dev, size_t rows, size_t row_len,
+                 const float *alpha_dev, int alpha_per_row, float gmax,
+                 const void *plan_host, const void *plan_dev, int n_normal,
+                 unsigned flags, int dtype, void *stream);
+size_t antq_decode8_batch_capacity(const antq_decode_job *jobs, int n, int dtype);   /* bytes antq_decode8_batch_build needs; 0: bad arguments */
+int    antq_decode8_batch_build(const antq_decode_job *jobs, int n, int dtype, unsigned flags,
+                                void *batch_host, size_t capacity);
+int    antq_decode8_batch(const void *batch_host, const void *batch_dev, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Packed 4-bit linear: y = x . W^T (+ bias) for 1 .. ANTQ_LINEAR4_MAX_M rows of x, computed straight from the codes of W
