@@ -185,6 +185,7 @@ int antq_fakequant_f64(const double *x_dev, double *out_dev, size_t rows, size_t
  *     alpha[r] = fl32(max_c |x[r,c]| * ratio)
  * One quant group (row) per wavefront / workgroup, single read of x.
  * alpha_out_dev (nullable): receives the `rows` alphas.  Per-row only.
+ * A NaN in the row gives a NaN alpha, an Inf an Inf alpha (NaN wins over Inf), like antq_absmax.
  * ------------------------------------------------------------------------- */
 int antq_fakequant_dynamic(const void *x_dev, void *out_dev, int16_t *idx_dev,
                            float *alpha_out_dev, size_t rows, size_t row_len,

@@ -2026,11 +2026,13 @@ def test_quantizer_follows_external_grid_edits(antq_lib, oracle, dev, capsys):
     capsys.readouterr()
 
 
-@pytest.mark.parametrize("dtype_name", ["float32", "bfloat16"])
+@pytest.mark.parametrize("dtype_name", ["float32", "bfloat16", "float16"])
 def test_dynamic_batched_launch_equals_per_tensor_dynamic(antq_lib, dev, dtype_name):
     """ANTQ_FLAG_DYNAMIC: many tensors, alpha = group / row abs-max computed in the kernel, ONE batch -- same alphas and
-    the same bits as antq_fakequant_dynamic per tensor (itself oracle-checked), ANT and OliVe pairs, from 1-vector groups
-    to 8192-vector rows; what cannot live in registers is refused."""
+    the same bits as antq_fakequant_dynamic per tensor, ANT and OliVe pairs, from 1-vector groups to 8192-vector rows; what
+    cannot live in registers is refused.  The per-tensor form is held to the oracle elsewhere: fp32 by
+    test_gpu_fakequant_edges.py::test_fp32_dynamic_scale_forms, bf16 / f16 (k_fq_hrow_dyn, which this test's index-free calls
+    run) by test_gpu_dynamic16_edges.py -- here it is only the other side of an equality."""
     import torch
     dtype = getattr(torch, dtype_name)
     epl = 4 if dtype == torch.float32 else 8
