@@ -757,16 +757,19 @@ def calibrate(x, rows, row_len, per_row, plans, gmaxs, lb, ub, step, xmax="absma
 _install_args = {}        # (plans..., gmaxs...) -> the three small ctypes arrays of antq_calibrate_install (built once per type list)
 
 
-def calibrate_install(x, out, plans, gmaxs, typ, alpha, score, grids_stack, grid_out, alpha_out, mse_out, ovp=False):
+def calibrate_install(x, out, plans, gmaxs, typ, alpha, score, grids_stack, grid_out, alpha_out, mse_out, ovp=False, outl=None, outl_out=None):
     """antq_calibrate_install: from the device-side pick `typ` of calibrate() -- alpha_out / mse_out / grid_out <- the winner's
     alpha, score and row of grids_stack [ntypes, grid_len] float32, and out <- the steady-state forward of x (one scale) with
     the winner's codebook.  Two launches, no read-back.  False: this tensor is not eligible (ragged / unaligned: the caller
-    quantises with every candidate and gathers)."""
+    quantises with every candidate and gathers).  outl [ntypes, outl_len] float32 / outl_out [outl_len] (OliVe's outlier lists,
+    optional): outl_out <- the winner's row of outl.  mse_out may be None."""
     _require_gpu(x, "x")
     dt = _DTYPES.get(x.dtype)
     nt = len(plans)
     if dt is None or dt == F64 or nt > 4 or not x.is_contiguous() or grids_stack.dtype != torch.float32 or grids_stack.shape[0] != nt:
         return False
+    if outl is not None and (outl.dtype != torch.float32 or outl.dim() != 2 or outl.shape[0] != nt or not outl.is_contiguous()):
+        raise AntqError("outl must be a contiguous [ntypes, outl_len] float32 tensor")
     key = (tuple(id(p) for p in plans), tuple(gmaxs), x.device.index)
     a = _install_args.get(key)
     if a is None:
@@ -777,8 +780,10 @@ def calibrate_install(x, out, plans, gmaxs, typ, alpha, score, grids_stack, grid
     with _on_device(x.device):
         rc = lib().antq_calibrate_install(x.data_ptr(), out.data_ptr(), x.numel(), dt, nt, ctypes.addressof(a[0]), ctypes.addressof(a[1]),
                                           ctypes.addressof(a[2]), FLAG_OVP if ovp else 0, typ.data_ptr(), alpha.data_ptr(), score.data_ptr(),
-                                          grids_stack.data_ptr(), grids_stack.shape[1], grid_out.data_ptr(), None, 0, None,
-                                          alpha_out.data_ptr(), mse_out.data_ptr(), _stream_int(x.device))
+                                          grids_stack.data_ptr(), grids_stack.shape[1], grid_out.data_ptr(),
+                                          None if outl is None else outl.data_ptr(), 0 if outl is None else outl.shape[1],
+                                          None if outl_out is None else outl_out.data_ptr(), alpha_out.data_ptr(),
+                                          None if mse_out is None else mse_out.data_ptr(), _stream_int(x.device))
     if rc == -2:                    # ANTQ_ERR_UNSUPPORTED
         return False
     if rc:
@@ -799,7 +804,8 @@ def calibrate_batch(jobs, xmax="absmax", ovp=False):
     """antq_calibrate_batch: the calibrations of many quantisers (one model's weights) in one C call, stream-ordered, no
     device->host sync.  jobs: sequence of (x, rows, row_len, per_row, plans, gmaxs, lb, ub, step); one dtype and one device
     for the batch.  Returns (results, types): results[i] = (alpha [ntypes_i, na_i], score [ntypes_i], xmax [na_i]) -- views
-    of two flat float32 buffers -- and types: ONE int32 tensor with the n type picks (a single read-back for the model)."""
+    of two flat float32 buffers -- and types: ONE int32 tensor with the n type picks (a single read-back for the model).
+    xmax: "absmax", "3sigma", or a sequence of float32 device tensors, one per job (the caller's statistics, ANTQ_XMAX_GIVEN)."""
     jobs = list(jobs)
     if not jobs:
         return [], None
@@ -808,9 +814,13 @@ def calibrate_batch(jobs, xmax="absmax", ovp=False):
     dt = _DTYPES.get(x0.dtype)
     if dt is None or dt == F64:
         raise AntqError("unsupported dtype %s" % x0.dtype)
-    mode = {"absmax": XMAX_ABSMAX, "3sigma": XMAX_3SIGMA}.get(xmax)
-    if mode is None:
-        raise AntqError("xmax must be 'absmax' or '3sigma'")
+    given = None
+    if isinstance(xmax, str):
+        mode = {"absmax": XMAX_ABSMAX, "3sigma": XMAX_3SIGMA}.get(xmax)
+    else:
+        mode, given = XMAX_GIVEN, list(xmax)
+    if mode is None or (given is not None and len(given) != len(jobs)):
+        raise AntqError("xmax must be 'absmax', '3sigma' or one statistic tensor per job")
     dev = x0.device
     n = len(jobs)
     arr = (_CalibJob * n)()
@@ -829,6 +839,11 @@ def calibrate_batch(jobs, xmax="absmax", ovp=False):
     results = []
     for i, ((x, rows, row_len, per_row, plans, gmaxs, lb, ub, step), (na, nt, off)) in enumerate(zip(jobs, sizes)):
         alpha, score, xm = flat[off:off + nt * na].view(nt, na), flat[off + nt * na:off + nt * na + nt], flat[off + nt * na + nt:off + nt * na + nt + na]
+        if given is not None:
+            g = given[i].reshape(-1)
+            if g.dtype != torch.float32 or g.numel() != na or g.device != dev:
+                raise AntqError("calibrate_batch: job %d's statistic must hold %d float32 values on the jobs' device" % (i, na))
+            xm.copy_(g)
         ph = (ctypes.c_void_p * nt)(*[p.host_addr for p in plans])
         pd = (ctypes.c_void_p * nt)(*[p.dev(dev).data_ptr() for p in plans])
         gm = (ctypes.c_float * nt)(*[float(g) for g in gmaxs])

@@ -321,7 +321,10 @@ k_hist_score(const uint32_t *__restrict__ count, const float *__restrict__ xmax,
                 float q;
                 const float term = hist_term<T>(v, sc, pa, L, q);
                 const float xv = H16<T>::val(v);
-                corr += (double)(xv * xv) - (double)term;           // a victim's output is 0: its term is fl32(|0 - x|^2)
+                // a victim's output is 0: its term is fl32(|0 - x|^2).  Equal terms change nothing -- and are not subtracted:
+                // next to FLT_MAX both are Inf, and Inf - Inf made NaN of a sum that is Inf in the reference
+                const float v2 = xv * xv;
+                if (v2 != term) corr += (double)v2 - (double)term;
             }
         };
         // the packed list, eight words in flight per lane; a lane's additions in list order

@@ -106,12 +106,16 @@ __device__ __forceinline__ void sweep_finish(uint32_t lane, uint32_t nthr, uint3
             while (b < nthr && sV[b] < 0.0f) b++;
             const double Ob = (double)(sV[b] * s);
             double Op = (double)(sV[0] * s);
-            double sum = Q + (double)n_tot * Ob * Ob - 2.0 * Ob * ((double)s_tot * unit);
+            // A term that counts no element is left out, not multiplied by zero: at a scale next to FLT_MAX an output value
+            // fl32(v * s) is Inf, and Inf * 0 made NaN of a candidate whose elements were all evaluated literally (a row whose
+            // statistic is FLT_MAX: the oracle's sum is finite).  Where the values are finite such a term is +-0: the same bits.
+            double sum = Q;
+            if (n_tot != 0 || s_tot != 0) sum += (double)n_tot * Ob * Ob - 2.0 * Ob * ((double)s_tot * unit);
             for (uint32_t k = 0; k < nthr; k++) {
                 const double On = (double)(sV[k + 1u] * s);
                 const long long en = (long long)sEn[k * cp + cc], es = sEs[k * cp + cc];
                 const double N = k >= b ? (double)en : -(double)(n_tot - en), S = (double)(k >= b ? es : -(s_tot - es)) * unit;
-                sum += (On - Op) * ((On + Op) * N - 2.0 * S);
+                if (N != 0.0 || S != 0.0) sum += (On - Op) * ((On + Op) * N - 2.0 * S);
                 Op = On;
             }
             sum += h ? exc1 : exc0;

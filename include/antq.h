@@ -333,7 +333,10 @@ int antq_calibrate(const void *x_dev, size_t rows, size_t row_len, int alpha_per
  *   the calibrating call's own output, one pass over the tensor instead of one per candidate and a gather.
  * The host needs the pick only to NAME the mode (it copies *type_dev to pinned memory and reads it when the model's forward
  * has returned).  x: n elements, 16-byte aligned, n a multiple of the vector's element count (4 fp32 / 8 16-bit), otherwise
- * ANTQ_ERR_UNSUPPORTED (the caller quantises with every candidate and gathers, as before).  ntypes <= 4. */
+ * ANTQ_ERR_UNSUPPORTED (the caller quantises with every candidate and gathers, as before; nothing is written).  ntypes <= 4.
+ * A pick outside 0 .. ntypes - 1 is CLAMPED to the nearest end by both launches (a negative *type_dev installs type 0, one of
+ * ntypes or more installs type ntypes - 1): no read or write leaves the ntypes entries whatever the device holds.
+ * mse_out, outl_dev and outl_out may be NULL (outl_out is written only when both outl pointers are given). */
 int antq_calibrate_install(const void *x_dev, void *out_dev, size_t n, int dtype, int ntypes, const float *gmax_host,
                            const void *const *plan_host, const void *const *plan_dev, unsigned flags, const int32_t *type_dev,
                            const float *alpha_dev, const float *score_dev, const float *grids_dev, int grid_len, float *grid_out,
