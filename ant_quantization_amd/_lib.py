@@ -25,6 +25,7 @@ IDX_VICTIM = -2
 MAX_GRID = 1024
 LINEAR4_MAX_M = 8      # include/antq.h ANTQ_LINEAR4_MAX_M: input rows antq_linear4 takes
 LINEAR4_MM_MAX_M = 64  # include/antq.h ANTQ_LINEAR4_MM_MAX_M: input rows antq_linear4_mm takes
+LINEAR8_MAX_M = 8      # include/antq.h ANTQ_LINEAR8_MAX_M: input rows antq_linear8 takes
 PLAN_MAX_BYTES = 128 + 4 * MAX_GRID + 16 * 3072 + 20 * 1024 + 16 * 64
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16, torch.float64: F64}
@@ -62,7 +63,7 @@ def lib():
                              "antq_calibrate", "antq_prefetch_kernels", "antq_plan_eval_host_h", "antq_calibrate_batch", "antq_absmax_into", "antq_fakequant_f64",
                              "antq_absmax_t", "antq_alpha_grad_t", "antq_calibrate_install", "antq_decode4_batch_build", "antq_decode4_batch",
                              "antq_linear4", "antq_linear4_mm", "antq_encode8", "antq_decode8", "antq_decode8_batch_build",
-                             "antq_decode8_batch"):
+                             "antq_decode8_batch", "antq_linear8"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
                 L.antq_decode4_batch_capacity.restype = ctypes.c_size_t
@@ -84,6 +85,7 @@ def lib():
                 L.antq_copy.argtypes = [vp, vp, sz, vp]
                 L.antq_linear4.argtypes = [vp, vp, vp, vp, sz, sz, sz, vp, ci, cf, vp, ci, ci, cu, ci, vp]
                 L.antq_linear4_mm.argtypes = L.antq_linear4.argtypes
+                L.antq_linear8.argtypes = L.antq_linear4.argtypes
                 # development: ANTQ_DEBUG_KNOBS="14=2,0=8" applies antq_debug_set(key, value) pairs to the loading thread
                 # (the knobs are thread-local; tools/fuzz_campaign.sh forces code paths with it)
                 for kv in [k for k in os.environ.get("ANTQ_DEBUG_KNOBS", "").split(",") if "=" in k]:
@@ -980,7 +982,8 @@ def decode8(codes, alpha, plan, gmax, rows, row_len, per_row, dtype, n_normal=0,
     return out.view(rows, row_len)
 
 
-def _linear4_call(entry, max_m, allow_f32, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out):
+def _linear4_call(entry, max_m, allow_f32, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out, per_byte=2):
+    """per_byte: codes a byte holds (2: the 4-bit layout, 1: byte codes)."""
     _require_gpu(x, "x")
     _require_gpu(codes, "codes")
     _require_gpu(alpha, "alpha")
@@ -993,8 +996,8 @@ def _linear4_call(entry, max_m, allow_f32, codes, x, alpha, grid_dev, gmax, N, K
     M = x.numel() // K
     if max_m is not None and M > max_m:
         raise AntqError("%s takes at most %d rows of x (got %d)" % (entry, max_m, M))
-    if codes.dtype != torch.uint8 or codes.numel() * 2 != N * K:
-        raise AntqError("codes must be uint8 of N*K/2 bytes")
+    if codes.dtype != torch.uint8 or codes.numel() * per_byte != N * K:
+        raise AntqError("codes must be uint8 of N*K%s bytes" % ("/2" if per_byte == 2 else ""))
     if alpha.dtype != torch.float32 or alpha.numel() < (N if per_row else 1) or grid_dev.dtype != torch.float32:
         raise AntqError("alpha must be float32, one per row (per_row) or one; grid_dev float32")
     if bias is not None:
@@ -1003,7 +1006,7 @@ def _linear4_call(entry, max_m, allow_f32, codes, x, alpha, grid_dev, gmax, N, K
             raise AntqError("bias must hold N elements of x's dtype")
     for t in (codes, alpha, grid_dev, bias, out):
         if t is not None and t.device != x.device:
-            raise AntqError("every tensor of linear4 must live on one device")
+            raise AntqError("every tensor of %s must live on one device" % ("linear4" if per_byte == 2 else "linear8"))
     shape = tuple(x.shape[:-1]) + (N,)
     if out is None:
         out = torch.empty(shape, dtype=x.dtype, device=x.device)
@@ -1011,8 +1014,8 @@ def _linear4_call(entry, max_m, allow_f32, codes, x, alpha, grid_dev, gmax, N, K
         raise AntqError("out must be a contiguous tensor of x's dtype with M*N elements on x's device")
     with _on_device(x.device):
         rc = getattr(lib(), entry)(codes.data_ptr(), x.data_ptr(), _ptr(bias), out.data_ptr(), M, N, K, alpha.data_ptr(),
-                                   1 if per_row else 0, gmax, grid_dev.data_ptr(), grid_dev.numel(), n_normal,
-                                   FLAG_OVP if ovp else 0, dt, _stream_int(x.device))
+                1 if per_row else 0, gmax, grid_dev.data_ptr(), grid_dev.numel(), n_normal,
+                FLAG_OVP if ovp else 0, dt, _stream_int(x.device))
     if rc:
         _check(rc, entry)
     return out
@@ -1030,6 +1033,13 @@ def linear4_mm(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_norm
     (float32 raises AntqError).  Same W, fp32 accumulation in the MFMA accumulator; the order of the sum is not linear4's,
     so the same row has different low bits from the two.  A row's bits do not depend on the other rows or on their number."""
     return _linear4_call("antq_linear4_mm", LINEAR4_MM_MAX_M, False, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
+
+
+def linear8(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):
+    """linear4 for the BYTE codes of W [N, K] (antq_linear8): x is [..., K] with at most LINEAR8_MAX_M rows, W[n, k] is bit for
+    bit the element decode8 writes in x's dtype, products and sum in fp32; a row's bits do not depend on the other rows or on
+    their number.  codes: uint8 of N*K bytes (encode8's layout), 8-byte aligned.  Returns [..., N]."""
+    return _linear4_call("antq_linear8", None, True, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out, per_byte=1)
 
 
 # ---------------------------------------------------------------------------------

@@ -7,6 +7,7 @@
 #include "antq_k_decbatch8.h"
 #include "antq_k_linear4.h"
 #include "antq_k_linear4_mm.h"
+#include "antq_k_linear8.h"
 
 #include <type_traits>
 
@@ -508,6 +509,44 @@ extern "C" int antq_linear4_mm(const uint8_t *codes, const void *x, const void *
                                  (uint32_t)K, alpha, per_row ? 1 : 0, gmax, grid, (uint32_t)m, ovp ? n_normal : 0);
                         return launch_status();
                     });
+                });
+            });
+        });
+    });
+}
+
+// The byte-code form of antq_linear4 (antq_k_linear8.h): the same launch shape, W the image antq_decode8 writes.  Every check
+// comes before anything touches HIP.
+extern "C" int antq_linear8(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
+                            const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
+                            unsigned flags, int dtype, void *stream)
+{
+    if (!codes || !x || !y || !alpha || !grid || m < 1) return ANTQ_ERR_ARG;
+    if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_ARG;
+    if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
+    if (M == 0 || N == 0) return ANTQ_OK;
+    const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
+    if (M > ANTQ_LINEAR8_MAX_M || K == 0 || K % 8 != 0) return ANTQ_ERR_UNSUPPORTED;
+    if (!dec8_book_ok(m, n_normal, ovp)) return ANTQ_ERR_UNSUPPORTED;
+    if (N > 0x7fffffffull || K > 0x7ffffff8ull) return ANTQ_ERR_UNSUPPORTED;      // (rows and row length in 32 bits)
+    const uintptr_t esz = (dtype == ANTQ_F32) ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(codes) % 8 || reinterpret_cast<uintptr_t>(y) % esz ||
+        reinterpret_cast<uintptr_t>(bias) % esz)
+        return ANTQ_ERR_ALIGN;
+    const bool vec = K % 16 == 0 && reinterpret_cast<uintptr_t>(codes) % 16 == 0;     // 16 B of codes per lane
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int mt = M <= 2 ? (int)M : (M <= 4 ? 4 : 8);           // rows the kernel computes: 3 runs as 4, 5 .. 7 as 8
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return with_bool(ovp, [&](auto o) {
+            return with_value<1, 2, 4, 8>(mt, [&](auto mm) {
+                return with_bool(vec, [&](auto v) {
+                    constexpr int MT = decltype(mm)::value;
+                    const unsigned blocks = (unsigned)((N + lin4_rows(MT) - 1) / lin4_rows(MT));
+                    launch_k(false, k_linear8<T, decltype(o)::value, MT, decltype(v)::value>, dim3(blocks), dim3(64u), 0, st,
+                             codes, x, bias, y, (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha, per_row ? 1 : 0, gmax, grid,
+                             (uint32_t)m, ovp ? n_normal : 0);
+                    return launch_status();
                 });
             });
         });

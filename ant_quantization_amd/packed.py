@@ -63,13 +63,28 @@ length (4 mod 8, such as 20) and that the byte codec accepts -- at most 256 valu
 values, rows of a multiple of 4 elements -- is encoded with `antq_encode8`, one code per byte, 255 the pair identifier: an entry
 with `width == 8`.  Layers the 4-bit codec accepts keep 4-bit codes.  What stays in `.skipped`: rows that are no multiple of 4
 (conv1: K = 147), `base` / `outlier` modes, float64, quantisers that are disabled or not calibrated.  Byte-coded layers are decoded
-by `antq_decode8_batch`, one more launch per (device, dtype, pair rule) group (`.launches` counts it).  The linear-from-codes
-kernels (`antq_linear4`, `antq_linear4_mm`) do not take byte codes: such a layer is never fusable, always keeps its decoded image
-(also under `keep_images=False`) and runs F.linear on it.  `release_weights`, `nbytes()` and the gradient error work on it as on
+by `antq_decode8_batch`, one more launch per (device, dtype, pair rule) group (`.launches` counts it).  `antq_linear4` and
+`antq_linear4_mm` do not take byte codes: without `fused_bytes` (below) such a layer is never fusable, always keeps its decoded
+image (also under `keep_images=False`) and runs F.linear on it.  `release_weights`, `nbytes()` and the gradient error work on it as on
 any image-keeping layer.  `packed_state_dict` writes its codes as numel bytes; `load_packed_state_dict` takes the width from the
 stored size (numel / 2: 4-bit, numel: bytes; anything else raises AntqError naming the layer).  Measured
 (profiles/packed_bytes.md): BERT-base's 74 Linear layers with 8 pairs at 8 bit -- 0 instead of 8 weight launches per forward,
 checkpoint 48.9 instead of 60.1 MB, resident bytes 219.4 instead of 208.2 MB (codes are added, the image replaces the float weight).
+
+`fused_bytes=True` (with fused_linear, else AntqError; off by default -- without it everything above is unchanged): a byte-coded
+entry that is a 2-D Linear weight with in_features = K and K % 8 == 0 is fusable.  Its no-grad calls of at most
+`_lib.LINEAR8_MAX_M` = 8 rows, under the input conditions of the 4-bit path, run `antq_linear8` -- the same product from the byte
+codes, W bit for bit the image `antq_decode8` writes (`.fused_byte_calls` counts them; `.fused_calls` stays antq_linear4's).
+`fused_rows` does not apply to byte entries (there is no matrix-core form): calls of more rows run F.linear on the image or, with
+`keep_images=False`, on the scratch decode (`antq_decode8` into the bank's one scratch buffer, which is sized to the largest
+image-less layer of either width).  `release_weights`, the "float weight is gone" error, the disabled-quantiser path and `.to()`
+/ `.half()` behave as for the 4-bit layers.  Other byte-coded layers (K = 20, conv layers) keep their image as before.
+Measured (profiles/packed_linear8.md; one MI355X, one run, 5 rounds per point, medians; OPT-6.7B's and BERT-base's shapes, M = 1,
+2, 4, 8, bf16 / f16 / fp32, ANT int-8 and OliVe int-8): antq_linear8 beats decode8 + F.linear at all 120 points (1.2-6.5x); against
+F.linear on the kept image it wins everywhere at M = 1 (1.3-3.2x) and M = 2 (1.07-2.0x), at M = 4 everywhere but four 16-bit
+points (0.80-0.99x), and at M = 8 it LOSES on most 16-bit shapes (down to 0.61x) and on the wide fp32 layers (0.86-0.92x).
+BERT-base with 8 pairs at 8 bits, bf16: 216.8 MB resident with byte_codes=True, 50.4 MB with fused_linear, fused_bytes and
+keep_images=False.
 """
 import torch
 import torch.nn.functional as F
@@ -100,11 +115,16 @@ def _settle(q):
 
 class PackedBank:
     def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True, fused_rows=None,
-                 byte_codes=False):
+                 byte_codes=False, fused_bytes=False):
         """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict);
         a layer's code width is then the one its stored size says (numel / 2 bytes: 4-bit, numel bytes: byte codes).
-        byte_codes: layers the 4-bit codec refuses and the byte codec accepts are packed one code per byte (width 8)."""
+        byte_codes: layers the 4-bit codec refuses and the byte codec accepts are packed one code per byte (width 8).
+        fused_bytes (with fused_linear): byte-coded Linear layers of K % 8 == 0 compute from their codes too (antq_linear8)."""
         self.byte_codes = bool(byte_codes)
+        if fused_bytes and not fused_linear:
+            raise _lib.AntqError("PackedBank: fused_bytes needs fused_linear=True")
+        self.fused_bytes = bool(fused_bytes)     # byte-coded Linear layers with few input rows compute from the codes (antq_linear8)
+        self.fused_byte_calls = 0  # forwards antq_linear8 served
         if not keep_images and not fused_linear:
             raise _lib.AntqError("PackedBank: keep_images=False needs fused_linear=True (nothing else computes from the codes)")
         _check_fused_rows("PackedBank", fused_linear, fused_rows)
@@ -150,8 +170,9 @@ class PackedBank:
                         alpha = q.alpha.detach().reshape(-1).to(torch.float32).contiguous()
                         enc = _lib.encode4 if width == 4 else _lib.encode8
                         c = enc(w.detach(), alpha, plan, gmax, rows, row_len, per_row, n_normal=n_normal, ovp=ovp)
-                # (the linear-from-codes kernels take 4-bit codes only: a byte-coded layer always keeps its image)
-                fusable = width == 4 and self.fused_linear and w.dim() == 2 and getattr(mod, "in_features", None) == w.shape[1] and w.shape[1] % 8 == 0
+                # (byte codes: only with fused_bytes -- without it a byte-coded layer always keeps its image)
+                fusable = ((width == 4 or self.fused_bytes) and self.fused_linear and w.dim() == 2
+                           and getattr(mod, "in_features", None) == w.shape[1] and w.shape[1] % 8 == 0)
                 image = self.keep_images or not fusable
                 self.entries[id(q)] = dict(name=name, q=q, mod=mod, rows=rows, row_len=row_len, per_row=per_row, codes=c, width=width,
                                            fusable=fusable, shape=tuple(w.shape), dtype=w.dtype, device=w.device,
@@ -330,8 +351,8 @@ class PackedBank:
         q = e["q"]
         plan, gmax, n_normal, ovp = _codebook(q)
         buf = self._scratch[(e["device"], e["dtype"])][:e["rows"] * e["row_len"]]
-        _lib.decode4(e["codes"], e["alpha"], plan, gmax, e["rows"], e["row_len"], e["per_row"], e["dtype"], n_normal=n_normal,
-                     ovp=ovp, out=buf)
+        dec = _lib.decode4 if e["width"] == 4 else _lib.decode8
+        dec(e["codes"], e["alpha"], plan, gmax, e["rows"], e["row_len"], e["per_row"], e["dtype"], n_normal=n_normal, ovp=ovp, out=buf)
         return buf.view(e["shape"])
 
     def linear(self, mod, input, weight):
@@ -351,15 +372,20 @@ class PackedBank:
             return F.linear(input, weight, mod.bias)
         K = e["shape"][1]
         bias = mod.bias
-        max_rows = _lib.LINEAR4_MAX_M
-        if self.fused_rows is not None and e["dtype"] in (torch.bfloat16, torch.float16):
+        byte = e["width"] == 8                     # (fused_rows is antq_linear4_mm's: byte codes have no matrix-core form)
+        max_rows = _lib.LINEAR8_MAX_M if byte else _lib.LINEAR4_MAX_M
+        if not byte and self.fused_rows is not None and e["dtype"] in (torch.bfloat16, torch.float16):
             max_rows = self.fused_rows
         if (input.is_cuda and input.dtype == e["dtype"] and input.device == e["device"] and input.dim() >= 1 and input.shape[-1] == K
                 and 0 < input.numel() <= max_rows * K and input.is_contiguous() and input.data_ptr() % 16 == 0
+                and not (byte and e["codes"].data_ptr() % 8)
                 and not (torch.is_grad_enabled() and (input.requires_grad or (bias is not None and bias.requires_grad)))
                 and (bias is None or (bias.dtype == input.dtype and bias.is_contiguous() and bias.device == input.device))):
             plan, gmax, n_normal, ovp = _codebook(e["q"])
-            if input.numel() <= _lib.LINEAR4_MAX_M * K:
+            if byte:
+                self.fused_byte_calls += 1
+                fn = _lib.linear8
+            elif input.numel() <= _lib.LINEAR4_MAX_M * K:
                 self.fused_calls += 1
                 fn = _lib.linear4
             else:
@@ -395,12 +421,15 @@ def _bank_of(model):
     return None
 
 
-def pack_model(model, release_weights=False, fused_linear=False, keep_images=True, fused_rows=None, byte_codes=False):
+def pack_model(model, release_weights=False, fused_linear=False, keep_images=True, fused_rows=None, byte_codes=False,
+               fused_bytes=False):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
     (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
     byte_codes: layers the 4-bit codec refuses for their codebook (5- to 8-bit layers, OliVe's unsigned 16 + 15) or their row
     length (4 mod 8) are packed one code per byte (entries of width 8, one more decode launch per group); they always keep
-    their decoded image and run F.linear on it -- the linear-from-codes kernels below take 4-bit codes only.
+    their decoded image and run F.linear on it unless fused_bytes is given.
+    fused_bytes (with fused_linear): byte-coded Linear layers of K % 8 == 0 compute calls of at most _lib.LINEAR8_MAX_M rows from
+    their byte codes (antq_linear8, .fused_byte_calls) and, with keep_images=False, keep no image -- see the module docstring.
     fused_linear: Linear layers called with at most _lib.LINEAR4_MAX_M input rows compute from the codes (antq_linear4);
     keep_images=False (with fused_linear): those layers keep no decoded image -- see the module docstring.
     fused_rows=R (with fused_linear, 8 < R <= 64): bf16 / f16 calls of 9 .. R rows compute from the codes on the matrix cores
@@ -416,7 +445,7 @@ def pack_model(model, release_weights=False, fused_linear=False, keep_images=Tru
     scaling, no hardware counters were collected.  Not measured: other M, the 4-byte code path, per-tensor scales, a whole
     model, more than one run per point.  The 16-bit MFMA keeps subnormal operands (measured): W is the image there too."""
     return PackedBank(model, release_weights=release_weights, fused_linear=fused_linear, keep_images=keep_images, fused_rows=fused_rows,
-                      byte_codes=byte_codes)
+                      byte_codes=byte_codes, fused_bytes=fused_bytes)
 
 
 def packed_state_dict(model):
@@ -437,15 +466,18 @@ def _packed_keys(sd, codes):
     return sd
 
 
-def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, keep_images=True, fused_rows=None):
+def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, keep_images=True, fused_rows=None,
+                           fused_bytes=False):
     """Load a packed checkpoint into a freshly wrapped, uncalibrated model living on the GPU: the quantiser state is
     installed the way load_ant_state_dict + load_state_dict do (scales keep the dtype they were stored with), a PackedBank is attached from the stored codes without
     re-encoding (a layer's code width is the one its stored size says: numel / 2 bytes are 4-bit codes, numel bytes byte codes;
     any other size raises AntqError naming the layer), and the weights are materialised by the batched decode
-    (release_weights=False: copied into the layers' own float weights instead of replacing them).  fused_linear / keep_images / fused_rows: as in pack_model.  Returns the bank."""
+    (release_weights=False: copied into the layers' own float weights instead of replacing them).  fused_linear / keep_images / fused_rows / fused_bytes: as in pack_model (the code width still comes from the stored size).  Returns the bank."""
     if not keep_images and not fused_linear:
         raise _lib.AntqError("load_packed_state_dict: keep_images=False needs fused_linear=True")
     _check_fused_rows("load_packed_state_dict", fused_linear, fused_rows)
+    if fused_bytes and not fused_linear:
+        raise _lib.AntqError("load_packed_state_dict: fused_bytes needs fused_linear=True")
     suffix = "." + CODES_KEY
     codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}
     rest = {k: v for k, v in sd.items() if not k.endswith(suffix)}
@@ -464,7 +496,7 @@ def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, 
     for _, _, q, _ in _weight_layers(model):
         _settle(q)
     bank = PackedBank(model, release_weights=release_weights, codes=codes, fused_linear=fused_linear, keep_images=keep_images,
-                      fused_rows=fused_rows)
+                      fused_rows=fused_rows, fused_bytes=fused_bytes)
     if not release_weights:
         with torch.no_grad():
             for e in bank.entries.values():

@@ -45,7 +45,7 @@ extern "C" {
  * Still 7: antq_decode4_batch_capacity / antq_decode4_batch_build / antq_decode4_batch added (the batched packed decoder; nothing
  * that existed changed, so callers built against 7 keep working).  antq_linear4 (the packed 4-bit linear) added likewise,
  * and antq_linear4_mm (its matrix-core form for up to 64 rows), and antq_encode8 / antq_decode8 / antq_decode8_batch_capacity /
- * antq_decode8_batch_build / antq_decode8_batch (the byte-code codec).
+ * antq_decode8_batch_build / antq_decode8_batch (the byte-code codec), and antq_linear8 (the linear from byte codes).
  * A caller built against another version must not call in: the blobs / argument lists differ. */
 #define ANTQ_ABI_VERSION 7
 
@@ -499,8 +499,8 @@ int    antq_decode4_batch(const void *batch_host, const void *batch_dev, void *s
  * 16-byte aligned.  The encoder is the element encoder of antq_encode4 (no row-table, no 16-bit-domain form).
  * The batch entry points are antq_decode4_batch's with antq_decode_job as it is -- codes_dev holds rows*row_len bytes --
  * and the same rules for n, flags and n_normal; the builder is pure host code and touches no HIP.  All launches are
- * stream-ordered and capturable: no allocation, no synchronisation, no workspace.  The packed linears (antq_linear4,
- * antq_linear4_mm) do not take byte codes.
+ * stream-ordered and capturable: no allocation, no synchronisation, no workspace.  antq_linear4 and antq_linear4_mm take
+ * 4-bit codes only; antq_linear8 (below) is the linear from byte codes, for 1 .. 8 rows of x (no matrix-core form yet).
  * ------------------------------------------------------------------------- */
 int antq_encode8(const void *x_dev, uint8_t *codes_dev, size_t rows, size_t row_len,
                  const float *alpha_dev, int alpha_per_row, float gmax,
@@ -577,6 +577,36 @@ int antq_linear4_mm(const uint8_t *codes_dev, const void *x_dev, const void *bia
                     const float *alpha_dev, int alpha_per_row, float gmax,
                     const float *grid_dev, int m, int n_normal,
                     unsigned flags /* 0 | ANTQ_FLAG_OVP */, int dtype /* BF16 | F16 */, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Packed byte-code linear: antq_linear4 for the byte codes of W -- y = x . W^T (+ bias) for 1 .. ANTQ_LINEAR8_MAX_M rows of x,
+ * computed straight from the codes (half the bytes of the bf16 image, a quarter of the fp32 image).  codes: N rows of K
+ * bytes in antq_encode8's layout; alpha / gmax / grid / m / n_normal as in antq_decode_job, alpha_per_row: one scale per
+ * output row n.
+ *   W[n,k] is, bit for bit, the element antq_decode8 writes for the same codes, alpha, gmax, grid and flags in `dtype`:
+ *          fl((g[c] + 0.0f) * (alpha / gmax)) rounded to `dtype`, the pair rule applied on the flat pairs (2k, 2k + 1), a victim
+ *          and a code beyond the book +0 -- not the unrounded product, and not a scale factored out of the sum.
+ *   y[m,n] = round_dtype( sum_k x[m,k] * W[n,k] + bias[n] ), products and sum accumulated in fp32 (fused multiply-adds).
+ *   The order of the sum is the kernel's own, but fixed: the same input gives the same bits on every run, and y[m,.] does
+ *          not depend on M or on the other rows of x -- a row computed alone has the bits it has inside a call of 8.
+ *   No floating-point atomics, no split-K across workgroups, no inter-workgroup communication, no workspace, no allocation,
+ *          no synchronisation: stream-ordered and capturable into a graph.
+ * Checked before anything touches HIP, in this order:
+ *   ANTQ_ERR_ARG          a null codes / x / y / alpha / grid, m < 1, a bad dtype, a flag bit other than ANTQ_FLAG_OVP
+ *   ANTQ_OK, no launch    M == 0 or N == 0
+ *   ANTQ_ERR_UNSUPPORTED  M > ANTQ_LINEAR8_MAX_M; K == 0 or K % 8 != 0; the byte decoder's refusals: m > 256, with
+ *                         ANTQ_FLAG_OVP n_normal outside 1..255 or m - n_normal outside 0..255; N >= 2^31 or K >= 2^31
+ *   ANTQ_ERR_ALIGN        x_dev not 16-byte aligned, codes_dev not 8-byte aligned, y_dev / bias_dev not aligned to their element
+ * Codes are read 16 bytes per lane when K % 16 == 0 and codes_dev is 16-byte aligned, 8 bytes per lane otherwise (the order
+ * of the sum differs between the two, nothing else).  F32 / BF16 / F16.
+ * ------------------------------------------------------------------------- */
+#define ANTQ_LINEAR8_MAX_M 8
+int antq_linear8(const uint8_t *codes_dev,          /* N*K bytes, antq_encode8's layout */
+                 const void *x_dev, const void *bias_dev, void *y_dev,
+                 size_t M, size_t N, size_t K,
+                 const float *alpha_dev, int alpha_per_row, float gmax,
+                 const float *grid_dev, int m, int n_normal,   /* as in antq_decode_job */
+                 unsigned flags /* 0 | ANTQ_FLAG_OVP */, int dtype /* F32 | BF16 | F16 */, void *stream);
 
 /* -------------------------------------------------------------------------
  * OliVe's clip statistic on ONE read (replaces t.mean() + t.std() of olive_quantization/antquant/quant_modules.py:193-197
