@@ -367,12 +367,14 @@ extern "C" int antq_fakequant_batch(const void *batch_host, const void *batch_de
     });
 }
 
-// The batched packed-4-bit decoder (antq_k_decbatch.h); the blob comes from antq_decode4_batch_build (antq_plan.cpp: pure host).
-extern "C" int antq_decode4_batch(const void *batch_host, const void *batch_dev, void *stream)
+// The batched decoders of both code widths: the blob (antq_decbatch.h) comes from antq_decode4_batch_build /
+// antq_decode8_batch_build (antq_plan.cpp: pure host), `magic` says which; `launch` starts that width's kernel.
+template <typename Launch>
+static int decode_batch(uint32_t magic, const void *batch_host, const void *batch_dev, void *stream, Launch launch)
 {
     if (!batch_host || !batch_dev) return ANTQ_ERR_ARG;
     const DecHeader *h = static_cast<const DecHeader *>(batch_host);
-    if (h->magic != kDecMagic) return ANTQ_ERR_PLAN;
+    if (h->magic != magic) return ANTQ_ERR_PLAN;
     if (h->total_blocks == 0) return ANTQ_OK;
     const char *pd = static_cast<const char *>(batch_dev);
     const DecDesc *descs = reinterpret_cast<const DecDesc *>(pd + sizeof(DecHeader));
@@ -380,9 +382,17 @@ extern "C" int antq_decode4_batch(const void *batch_host, const void *batch_dev,
     hipStream_t st = static_cast<hipStream_t>(stream);
     return with_dtype((int)h->dtype, [&](auto tag) {
         return with_bool((h->flags & ANTQ_FLAG_OVP) != 0, [&](auto ovp) {
-            hipLaunchKernelGGL((k_decode4_batch<decltype(tag), decltype(ovp)::value>), dim3(h->total_blocks * 4u), dim3(64u), 0, st, descs, map);
+            launch(tag, ovp, dim3(h->total_blocks * 4u), st, descs, map);
             return launch_status();
         });
+    });
+}
+
+// The batched packed-4-bit decoder (antq_k_decbatch.h).
+extern "C" int antq_decode4_batch(const void *batch_host, const void *batch_dev, void *stream)
+{
+    return decode_batch(kDecMagic, batch_host, batch_dev, stream, [](auto tag, auto ovp, dim3 grid, hipStream_t st, const DecDesc *descs, const uint32_t *map) {
+        hipLaunchKernelGGL((k_decode4_batch<decltype(tag), decltype(ovp)::value>), grid, dim3(64u), 0, st, descs, map);
     });
 }
 
@@ -417,42 +427,42 @@ extern "C" int antq_decode8(const uint8_t *codes, void *out, size_t rows, size_t
 
 extern "C" int antq_decode8_batch(const void *batch_host, const void *batch_dev, void *stream)
 {
-    if (!batch_host || !batch_dev) return ANTQ_ERR_ARG;
-    const DecHeader *h = static_cast<const DecHeader *>(batch_host);
-    if (h->magic != kDec8Magic) return ANTQ_ERR_PLAN;
-    if (h->total_blocks == 0) return ANTQ_OK;
-    const char *pd = static_cast<const char *>(batch_dev);
-    const DecDesc *descs = reinterpret_cast<const DecDesc *>(pd + sizeof(DecHeader));
-    const uint32_t *map = reinterpret_cast<const uint32_t *>(pd + h->map_offset);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return with_dtype((int)h->dtype, [&](auto tag) {
-        return with_bool((h->flags & ANTQ_FLAG_OVP) != 0, [&](auto ovp) {
-            hipLaunchKernelGGL((k_decode8_batch<decltype(tag), decltype(ovp)::value>), dim3(h->total_blocks * 4u), dim3(64u), 0, st, descs, map);
-            return launch_status();
-        });
+    return decode_batch(kDec8Magic, batch_host, batch_dev, stream, [](auto tag, auto ovp, dim3 grid, hipStream_t st, const DecDesc *descs, const uint32_t *map) {
+        hipLaunchKernelGGL((k_decode8_batch<decltype(tag), decltype(ovp)::value>), grid, dim3(64u), 0, st, descs, map);
     });
 }
 
-// y = x . W^T (+ bias) for 1 .. ANTQ_LINEAR4_MAX_M rows of x from the packed codes of W (antq_k_linear4.h).  Every check
-// comes before anything touches HIP.
-extern "C" int antq_linear4(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
-                            const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
-                            unsigned flags, int dtype, void *stream)
+// The argument ladder of the three packed linears, in the order the C ABI keeps: null pointers and m < 1, the dtype, the
+// flags, the empty call, (f32 where the kernel has none,) M, K and the book, the 32-bit limits, alignment.  Every check comes
+// before anything touches HIP.  Returns the call's status, or kLinearGo: go on and launch.
+//   max_m       the most rows of x            no_f32      f32 is refused as unsupported, after the empty call
+//   book_ok     the code width's book rule    code_align  bytes the codes are aligned to
+//   esz         bytes y and bias are aligned to
+constexpr int kLinearGo = 1;
+static int linear_checks(const uint8_t *codes, const void *x, const void *bias, const void *y, size_t M, size_t N, size_t K,
+                         const float *alpha, const float *grid, int m, int n_normal, unsigned flags, int dtype, size_t max_m,
+                         bool no_f32, bool (*book_ok)(int, int, bool), uintptr_t code_align, uintptr_t esz)
 {
     if (!codes || !x || !y || !alpha || !grid || m < 1) return ANTQ_ERR_ARG;
     if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_ARG;
     if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
     if (M == 0 || N == 0) return ANTQ_OK;
-    const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
-    if (M > ANTQ_LINEAR4_MAX_M || K == 0 || K % 8 != 0) return ANTQ_ERR_UNSUPPORTED;
-    if (ovp) { if (n_normal < 1 || n_normal > 15 || m - n_normal > 15 || m - n_normal < 0) return ANTQ_ERR_UNSUPPORTED; }
-    else if (m > 16) return ANTQ_ERR_UNSUPPORTED;
+    if (no_f32 && dtype == ANTQ_F32) return ANTQ_ERR_UNSUPPORTED;
+    if (M > max_m || K == 0 || K % 8 != 0) return ANTQ_ERR_UNSUPPORTED;
+    if (!book_ok(m, n_normal, (flags & ANTQ_FLAG_OVP) != 0)) return ANTQ_ERR_UNSUPPORTED;
     if (N > 0x7fffffffull || K > 0x7ffffff8ull) return ANTQ_ERR_UNSUPPORTED;      // (rows and row length in 32 bits)
-    const uintptr_t esz = (dtype == ANTQ_F32) ? 4 : 2;
-    if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(codes) % 4 || reinterpret_cast<uintptr_t>(y) % esz ||
+    if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(codes) % code_align || reinterpret_cast<uintptr_t>(y) % esz ||
         reinterpret_cast<uintptr_t>(bias) % esz)
         return ANTQ_ERR_ALIGN;
-    const bool vec = K % 32 == 0 && reinterpret_cast<uintptr_t>(codes) % 16 == 0;     // 16 B of codes per lane
+    return kLinearGo;
+}
+
+// The launch of the row-streaming linear (antq_k_linear.h) for 1 .. 8 rows of x; Codec is Lin4Codec or Lin8Codec.
+template <template <typename, bool> class Codec>
+static int launch_linear(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
+                         const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal, bool ovp, bool vec,
+                         int dtype, void *stream)
+{
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int mt = M <= 2 ? (int)M : (M <= 4 ? 4 : 8);           // rows the kernel computes: 3 runs as 4, 5 .. 7 as 8
     return with_dtype(dtype, [&](auto tag) {
@@ -461,10 +471,10 @@ extern "C" int antq_linear4(const uint8_t *codes, const void *x, const void *bia
             return with_value<1, 2, 4, 8>(mt, [&](auto mm) {
                 return with_bool(vec, [&](auto v) {
                     constexpr int MT = decltype(mm)::value;
-                    const unsigned blocks = (unsigned)((N + lin4_rows(MT) - 1) / lin4_rows(MT));
-                    launch_k(false, k_linear4<T, decltype(o)::value, MT, decltype(v)::value>, dim3(blocks), dim3(64u), 0, st,
-                             reinterpret_cast<const uint32_t *>(codes), x, bias, y, (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha,
-                             per_row ? 1 : 0, gmax, grid, (uint32_t)m, ovp ? n_normal : 0);
+                    const unsigned blocks = (unsigned)((N + lin_rows(MT) - 1) / lin_rows(MT));
+                    launch_k(false, k_linear<Codec<T, decltype(o)::value>, MT, decltype(v)::value>, dim3(blocks), dim3(64u), 0, st,
+                             codes, x, bias, y, (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha, per_row ? 1 : 0, gmax, grid,
+                             (uint32_t)m, ovp ? n_normal : 0);
                     return launch_status();
                 });
             });
@@ -472,25 +482,29 @@ extern "C" int antq_linear4(const uint8_t *codes, const void *x, const void *bia
     });
 }
 
-// The same product for 1 .. ANTQ_LINEAR4_MM_MAX_M rows of x on the matrix cores (antq_k_linear4_mm.h; bf16 / f16).  Checks as
-// in antq_linear4, in its order, before anything touches HIP.
+// y = x . W^T (+ bias) for 1 .. ANTQ_LINEAR4_MAX_M rows of x from the packed codes of W (antq_k_linear4.h).
+extern "C" int antq_linear4(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
+                            const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
+                            unsigned flags, int dtype, void *stream)
+{
+    const int rc = linear_checks(codes, x, bias, y, M, N, K, alpha, grid, m, n_normal, flags, dtype, ANTQ_LINEAR4_MAX_M, false,
+                                 dec4_book_ok, 4, dtype == ANTQ_F32 ? 4 : 2);
+    if (rc != kLinearGo) return rc;
+    const bool vec = K % 32 == 0 && reinterpret_cast<uintptr_t>(codes) % 16 == 0;     // 16 B of codes per lane
+    return launch_linear<Lin4Codec>(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0,
+                                    vec, dtype, stream);
+}
+
+// The same product for 1 .. ANTQ_LINEAR4_MM_MAX_M rows of x on the matrix cores (antq_k_linear4_mm.h; bf16 / f16).
 extern "C" int antq_linear4_mm(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
                                const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
                                unsigned flags, int dtype, void *stream)
 {
-    if (!codes || !x || !y || !alpha || !grid || m < 1) return ANTQ_ERR_ARG;
-    if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_ARG;
-    if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
-    if (M == 0 || N == 0) return ANTQ_OK;
+    // (f32: the f32-input MFMA runs at the VALU rate: antq_linear4's ground; y and bias are 16-bit whatever dtype says)
+    const int rc = linear_checks(codes, x, bias, y, M, N, K, alpha, grid, m, n_normal, flags, dtype, ANTQ_LINEAR4_MM_MAX_M, true,
+                                 dec4_book_ok, 4, 2);
+    if (rc != kLinearGo) return rc;
     const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
-    if (dtype == ANTQ_F32) return ANTQ_ERR_UNSUPPORTED;           // (the f32-input MFMA runs at the VALU rate: antq_linear4's ground)
-    if (M > ANTQ_LINEAR4_MM_MAX_M || K == 0 || K % 8 != 0) return ANTQ_ERR_UNSUPPORTED;
-    if (ovp) { if (n_normal < 1 || n_normal > 15 || m - n_normal > 15 || m - n_normal < 0) return ANTQ_ERR_UNSUPPORTED; }
-    else if (m > 16) return ANTQ_ERR_UNSUPPORTED;
-    if (N > 0x7fffffffull || K > 0x7ffffff8ull) return ANTQ_ERR_UNSUPPORTED;      // (rows and row length in 32 bits)
-    if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(codes) % 4 || reinterpret_cast<uintptr_t>(y) % 2 ||
-        reinterpret_cast<uintptr_t>(bias) % 2)
-        return ANTQ_ERR_ALIGN;
     const bool vec = K % 32 == 0 && reinterpret_cast<uintptr_t>(codes) % 16 == 0;     // 16 B of codes per lane
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int mt = mm_mtiles(M);
@@ -515,42 +529,17 @@ extern "C" int antq_linear4_mm(const uint8_t *codes, const void *x, const void *
     });
 }
 
-// The byte-code form of antq_linear4 (antq_k_linear8.h): the same launch shape, W the image antq_decode8 writes.  Every check
-// comes before anything touches HIP.
+// The byte-code form of antq_linear4 (antq_k_linear8.h): the same launch, W the image antq_decode8 writes.
 extern "C" int antq_linear8(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
                             const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
                             unsigned flags, int dtype, void *stream)
 {
-    if (!codes || !x || !y || !alpha || !grid || m < 1) return ANTQ_ERR_ARG;
-    if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_ARG;
-    if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
-    if (M == 0 || N == 0) return ANTQ_OK;
-    const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
-    if (M > ANTQ_LINEAR8_MAX_M || K == 0 || K % 8 != 0) return ANTQ_ERR_UNSUPPORTED;
-    if (!dec8_book_ok(m, n_normal, ovp)) return ANTQ_ERR_UNSUPPORTED;
-    if (N > 0x7fffffffull || K > 0x7ffffff8ull) return ANTQ_ERR_UNSUPPORTED;      // (rows and row length in 32 bits)
-    const uintptr_t esz = (dtype == ANTQ_F32) ? 4 : 2;
-    if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(codes) % 8 || reinterpret_cast<uintptr_t>(y) % esz ||
-        reinterpret_cast<uintptr_t>(bias) % esz)
-        return ANTQ_ERR_ALIGN;
+    const int rc = linear_checks(codes, x, bias, y, M, N, K, alpha, grid, m, n_normal, flags, dtype, ANTQ_LINEAR8_MAX_M, false,
+                                 dec8_book_ok, 8, dtype == ANTQ_F32 ? 4 : 2);
+    if (rc != kLinearGo) return rc;
     const bool vec = K % 16 == 0 && reinterpret_cast<uintptr_t>(codes) % 16 == 0;     // 16 B of codes per lane
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int mt = M <= 2 ? (int)M : (M <= 4 ? 4 : 8);           // rows the kernel computes: 3 runs as 4, 5 .. 7 as 8
-    return with_dtype(dtype, [&](auto tag) {
-        using T = decltype(tag);
-        return with_bool(ovp, [&](auto o) {
-            return with_value<1, 2, 4, 8>(mt, [&](auto mm) {
-                return with_bool(vec, [&](auto v) {
-                    constexpr int MT = decltype(mm)::value;
-                    const unsigned blocks = (unsigned)((N + lin4_rows(MT) - 1) / lin4_rows(MT));
-                    launch_k(false, k_linear8<T, decltype(o)::value, MT, decltype(v)::value>, dim3(blocks), dim3(64u), 0, st,
-                             codes, x, bias, y, (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha, per_row ? 1 : 0, gmax, grid,
-                             (uint32_t)m, ovp ? n_normal : 0);
-                    return launch_status();
-                });
-            });
-        });
-    });
+    return launch_linear<Lin8Codec>(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0,
+                                    vec, dtype, stream);
 }
 
 namespace antq {

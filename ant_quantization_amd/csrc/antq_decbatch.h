@@ -67,6 +67,13 @@ inline uint32_t dec_row_u(uint32_t vpr)
     return best_u;
 }
 
+// the books a nibble holds: plain 1..16 values; pair rule: 1..15 normal values (15 is the identifier), 0..15 outliers
+inline bool dec4_book_ok(int m, int n_normal, bool ovp)
+{
+    if (ovp) return n_normal >= 1 && n_normal <= 15 && m - n_normal >= 0 && m - n_normal <= 15;
+    return m <= 16;
+}
+
 // One job's descriptor (d may be NULL) -> its number of tasks; ANTQ_ERR_* (< 0) when the job is refused.
 inline long long dec_job_tasks(const antq_decode_job &J, int dtype, unsigned flags, DecDesc *d)
 {
@@ -75,9 +82,7 @@ inline long long dec_job_tasks(const antq_decode_job &J, int dtype, unsigned fla
     if (J.rows == 0 || J.row_len == 0) return ANTQ_ERR_ARG;
     if (J.row_len % 8 != 0) return ANTQ_ERR_UNSUPPORTED;
     if (J.m < 1) return ANTQ_ERR_ARG;
-    if (flags & ANTQ_FLAG_OVP) {
-        if (J.n_normal < 1 || J.n_normal > 15 || J.m - J.n_normal > 15 || J.m - J.n_normal < 0) return ANTQ_ERR_UNSUPPORTED;
-    } else if (J.m > 16) return ANTQ_ERR_UNSUPPORTED;
+    if (!dec4_book_ok(J.m, J.n_normal, (flags & ANTQ_FLAG_OVP) != 0)) return ANTQ_ERR_UNSUPPORTED;
     if (J.rows > (size_t)-1 / J.row_len) return ANTQ_ERR_UNSUPPORTED;
     const size_t esz = dtype == ANTQ_F32 ? 4 : 2, epl = 16 / esz;
     if (reinterpret_cast<uintptr_t>(J.out_dev) % esz) return ANTQ_ERR_ALIGN;
@@ -115,7 +120,11 @@ inline long long dec_job_tasks(const antq_decode_job &J, int dtype, unsigned fla
     return (long long)tasks;
 }
 
-inline size_t dec_batch_capacity(const antq_decode_job *jobs, int n, int dtype)
+// The blob's builder, written once for both code widths: `job_tasks` is dec_job_tasks or dec8_job_tasks (antq_decbatch8.h),
+// `magic` the blob's.
+typedef long long (*dec_job_tasks_fn)(const antq_decode_job &, int, unsigned, DecDesc *);
+
+inline size_t dec_blob_capacity(dec_job_tasks_fn job_tasks, const antq_decode_job *jobs, int n, int dtype)
 {
     if (!jobs || n < 1 || n > 65535) return 0;
     size_t blocks = 0;
@@ -123,24 +132,25 @@ inline size_t dec_batch_capacity(const antq_decode_job *jobs, int n, int dtype)
         // (the codebook changes no task count, and the flags are not known here; a job the builder will refuse counts as empty)
         antq_decode_job J = jobs[i];
         J.m = 1;
-        const long long t = dec_job_tasks(J, dtype, 0u, nullptr);
+        const long long t = job_tasks(J, dtype, 0u, nullptr);
         if (t > 0) blocks += ((size_t)t + 3) / 4;
     }
     return sizeof(DecHeader) + sizeof(DecDesc) * (size_t)n + 4 * blocks;
 }
 
-inline int dec_batch_build(const antq_decode_job *jobs, int n, int dtype, unsigned flags, void *blob, size_t cap)
+inline int dec_blob_build(uint32_t magic, dec_job_tasks_fn job_tasks, const antq_decode_job *jobs, int n, int dtype, unsigned flags,
+                          void *blob, size_t cap)
 {
     if (!jobs || !blob || n < 1 || n > 65535) return ANTQ_ERR_ARG;
     if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
     DecHeader h;
     memset(&h, 0, sizeof(h));
-    h.magic = kDecMagic; h.n = (uint32_t)n; h.dtype = (uint32_t)dtype; h.flags = flags;
+    h.magic = magic; h.n = (uint32_t)n; h.dtype = (uint32_t)dtype; h.flags = flags;
     h.map_offset = (uint32_t)(sizeof(DecHeader) + sizeof(DecDesc) * (size_t)n);
     // every refusal first: nothing is written for a batch that cannot run
     size_t total = 0;
     for (int i = 0; i < n; i++) {
-        const long long t = dec_job_tasks(jobs[i], dtype, flags, nullptr);
+        const long long t = job_tasks(jobs[i], dtype, flags, nullptr);
         if (t < 0) return (int)t;
         total += ((size_t)t + 3) / 4;
     }
@@ -152,7 +162,7 @@ inline int dec_batch_build(const antq_decode_job *jobs, int n, int dtype, unsign
     uint32_t first = 0;
     for (int i = 0; i < n; i++) {
         DecDesc D;
-        const size_t nb = ((size_t)dec_job_tasks(jobs[i], dtype, flags, &D) + 3) / 4;
+        const size_t nb = ((size_t)job_tasks(jobs[i], dtype, flags, &D) + 3) / 4;
         D.first_block = first;
         memcpy(p + sizeof(DecHeader) + sizeof(DecDesc) * (size_t)i, &D, sizeof(D));
         for (size_t b = 0; b < nb; b++) {
@@ -165,6 +175,12 @@ inline int dec_batch_build(const antq_decode_job *jobs, int n, int dtype, unsign
     h.bytes = (uint32_t)bytes;
     memcpy(p, &h, sizeof(h));
     return (int)h.bytes;
+}
+
+inline size_t dec_batch_capacity(const antq_decode_job *jobs, int n, int dtype) { return dec_blob_capacity(dec_job_tasks, jobs, n, dtype); }
+inline int dec_batch_build(const antq_decode_job *jobs, int n, int dtype, unsigned flags, void *blob, size_t cap)
+{
+    return dec_blob_build(kDecMagic, dec_job_tasks, jobs, n, dtype, flags, blob, cap);
 }
 
 }  // namespace antq

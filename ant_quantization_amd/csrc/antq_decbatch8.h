@@ -79,56 +79,10 @@ inline long long dec8_job_tasks(const antq_decode_job &J, int dtype, unsigned fl
     return (long long)tasks;
 }
 
-inline size_t dec8_batch_capacity(const antq_decode_job *jobs, int n, int dtype)
-{
-    if (!jobs || n < 1 || n > 65535) return 0;
-    size_t blocks = 0;
-    for (int i = 0; i < n; i++) {
-        // (the codebook changes no task count, and the flags are not known here; a job the builder will refuse counts as empty)
-        antq_decode_job J = jobs[i];
-        J.m = 1;
-        const long long t = dec8_job_tasks(J, dtype, 0u, nullptr);
-        if (t > 0) blocks += ((size_t)t + 3) / 4;
-    }
-    return sizeof(DecHeader) + sizeof(DecDesc) * (size_t)n + 4 * blocks;
-}
-
+inline size_t dec8_batch_capacity(const antq_decode_job *jobs, int n, int dtype) { return dec_blob_capacity(dec8_job_tasks, jobs, n, dtype); }
 inline int dec8_batch_build(const antq_decode_job *jobs, int n, int dtype, unsigned flags, void *blob, size_t cap)
 {
-    if (!jobs || !blob || n < 1 || n > 65535) return ANTQ_ERR_ARG;
-    if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
-    DecHeader h;
-    memset(&h, 0, sizeof(h));
-    h.magic = kDec8Magic; h.n = (uint32_t)n; h.dtype = (uint32_t)dtype; h.flags = flags;
-    h.map_offset = (uint32_t)(sizeof(DecHeader) + sizeof(DecDesc) * (size_t)n);
-    // every refusal first: nothing is written for a batch that cannot run
-    size_t total = 0;
-    for (int i = 0; i < n; i++) {
-        const long long t = dec8_job_tasks(jobs[i], dtype, flags, nullptr);
-        if (t < 0) return (int)t;
-        total += ((size_t)t + 3) / 4;
-    }
-    if (total > 0x1fffffffull) return ANTQ_ERR_UNSUPPORTED;       // (x 4 one-wavefront workgroups in one grid)
-    const size_t bytes = h.map_offset + 4 * total;
-    if (bytes > 0x7fffffffull) return ANTQ_ERR_UNSUPPORTED;
-    if (cap < bytes) return ANTQ_ERR_PLAN;
-    char *p = static_cast<char *>(blob);
-    uint32_t first = 0;
-    for (int i = 0; i < n; i++) {
-        DecDesc D;
-        const size_t nb = ((size_t)dec8_job_tasks(jobs[i], dtype, flags, &D) + 3) / 4;
-        D.first_block = first;
-        memcpy(p + sizeof(DecHeader) + sizeof(DecDesc) * (size_t)i, &D, sizeof(D));
-        for (size_t b = 0; b < nb; b++) {
-            const uint32_t job = (uint32_t)i;
-            memcpy(p + h.map_offset + 4 * ((size_t)first + b), &job, 4);
-        }
-        first += (uint32_t)nb;
-    }
-    h.total_blocks = (uint32_t)total;
-    h.bytes = (uint32_t)bytes;
-    memcpy(p, &h, sizeof(h));
-    return (int)h.bytes;
+    return dec_blob_build(kDec8Magic, dec8_job_tasks, jobs, n, dtype, flags, blob, cap);
 }
 
 }  // namespace antq

@@ -3,6 +3,7 @@
 #ifndef ANTQ_K_CODEC_H
 #define ANTQ_K_CODEC_H
 
+#include "antq_decbatch.h"
 #include "antq_device.h"
 #include "antq_k_approx.h"
 #include "antq_k_hrow.h"
@@ -604,8 +605,7 @@ static int launch_codec(bool enc, const void *x, void *codes_or_out, const uint8
     const size_t n = rows * row_len;
     if (row_len % 8 != 0) return ANTQ_ERR_UNSUPPORTED;
     const int m = (int)pa.m;
-    if (ovp) { if (n_normal < 1 || n_normal > 15 || m - n_normal > 15 || m - n_normal < 0) return ANTQ_ERR_UNSUPPORTED; }
-    else if (m > 16) return ANTQ_ERR_UNSUPPORTED;
+    if (!dec4_book_ok(m, n_normal, ovp)) return ANTQ_ERR_UNSUPPORTED;
     const size_t n_oct = n / 8;
     const bool vec = reinterpret_cast<uintptr_t>(enc ? x : codes_or_out) % 16 == 0;     // 16-byte vector I/O
     constexpr int kEncU = 2;                           // octets per thread and task when encoding

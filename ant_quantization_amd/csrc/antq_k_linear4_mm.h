@@ -20,7 +20,7 @@
 //              16-byte loads (x is re-read by every workgroup and lives in L2).  A B fragment is reused by the MT tiles of
 //              x, an A fragment by the NT tiles of W.
 //   decode     one 256-entry table per output row (alpha_per_row) or one per tensor, built once per workgroup:
-//              DecOut<T>::make(q0 * s, q1 * s), s = alpha / gmax, the codebook read with + 0.0f -- k_linear4's expressions.
+//              the 4-bit byte table's one definition (antq_k_linear4.h: lin4_book, Lin4Entry), s = alpha / gmax.
 //   sum        fp32 in the MFMA accumulator, a wavefront's chunks chained in rising order; the eight wavefronts' partial
 //              tiles meet in LDS (the tables' memory, after a barrier) and are combined as
 //              ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7)), then the bias in fp32 and ONE rounding to the output type.
@@ -32,7 +32,7 @@
 #ifndef ANTQ_K_LINEAR4_MM_H
 #define ANTQ_K_LINEAR4_MM_H
 
-#include "antq_k_decbatch.h"
+#include "antq_k_linear4.h"
 
 namespace antq {
 
@@ -136,18 +136,13 @@ k_linear4_mm(const uint32_t *__restrict__ codes, const void *__restrict__ x, con
     for (int d = 0; d < D; d++)                          // in flight while the tables are built
         if (wave + kMmWaves * d < nchunks) load_chunk(wave + kMmWaves * d, d);
 
-    // (+ 0.0f: a codebook's -0 decodes to +0, as in the decoders)
-    if (tid < 32u) g[tid] = (tid < m) ? ld_global(grid + tid) + 0.0f : 0.0f;
+    lin4_book(g, tid, grid, m);
     if (tid < (per_row ? (uint32_t)ROWS : 1u)) sc[tid] = ld_global(alpha + (per_row ? min(row0 + tid, N - 1u) : 0u)) / gmax;   // AQ:536 scale = alpha / max(grid)
     __syncthreads();
     {
-        float q0, q1;
         const uint32_t b = tid & 255u;                 // threads b and 256 + b make entry b of the even and the odd tables
-        dec_pair<OVP>(b, g, n_normal, q0, q1);
-        for (uint32_t r = tid >> 8; r < (per_row ? (uint32_t)ROWS : 1u); r += 2u) {
-            const float s = sc[r];
-            smem[r * 256u + b] = DecOut<T>::make(q0 * s, q1 * s);
-        }
+        const Lin4Entry<T, OVP> e(b, g, n_normal);
+        for (uint32_t r = tid >> 8; r < (per_row ? (uint32_t)ROWS : 1u); r += 2u) smem[r * 256u + b] = e.at(sc[r]);
     }
     __syncthreads();
 
