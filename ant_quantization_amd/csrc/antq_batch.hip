@@ -8,6 +8,7 @@
 #include "antq_k_linear4.h"
 #include "antq_k_linear4_mm.h"
 #include "antq_k_linear8.h"
+#include "antq_k_linear8_mm.h"
 
 #include <type_traits>
 
@@ -540,6 +541,40 @@ extern "C" int antq_linear8(const uint8_t *codes, const void *x, const void *bia
     const bool vec = K % 16 == 0 && reinterpret_cast<uintptr_t>(codes) % 16 == 0;     // 16 B of codes per lane
     return launch_linear<Lin8Codec>(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0,
                                     vec, dtype, stream);
+}
+
+// The byte-code form of antq_linear4_mm (antq_k_linear8_mm.h): 1 .. ANTQ_LINEAR8_MM_MAX_M rows of x on the matrix cores, W the
+// image antq_decode8 writes; bf16 / f16.
+extern "C" int antq_linear8_mm(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
+                               const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
+                               unsigned flags, int dtype, void *stream)
+{
+    const int rc = linear_checks(codes, x, bias, y, M, N, K, alpha, grid, m, n_normal, flags, dtype, ANTQ_LINEAR8_MM_MAX_M, true,
+                                 dec8_book_ok, 8, 2);
+    if (rc != kLinearGo) return rc;
+    const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
+    const bool vec = K % 16 == 0 && reinterpret_cast<uintptr_t>(codes) % 16 == 0;     // 16 B of codes per lane
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int mt = mm_mtiles(M);
+    const int nt = one_of<1, 2, 4>(g_knob_mm_tile, mm_ntiles(M, N));
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if constexpr (std::is_same<T, float>::value) return (int)ANTQ_ERR_UNSUPPORTED;
+        else return with_bool(ovp, [&](auto o) {
+            return with_value<1, 2, 4>(mt, [&](auto mm) {
+                return with_value<1, 2, 4>(nt, [&](auto nn) {
+                    return with_bool(vec, [&](auto v) {
+                        constexpr int NT = decltype(nn)::value;
+                        const unsigned blocks = (unsigned)((N + 16 * NT - 1) / (16 * NT));
+                        launch_k(false, k_linear8_mm<T, decltype(o)::value, decltype(mm)::value, NT, decltype(v)::value>, dim3(blocks),
+                                 dim3(64u * kMmWaves), 0, st, reinterpret_cast<const uint32_t *>(codes), x, bias, y, (uint32_t)M, (uint32_t)N,
+                                 (uint32_t)K, alpha, per_row ? 1 : 0, gmax, grid, (uint32_t)m, ovp ? n_normal : 0);
+                        return launch_status();
+                    });
+                });
+            });
+        });
+    });
 }
 
 namespace antq {

@@ -75,9 +75,9 @@ checkpoint 48.9 instead of 60.1 MB, resident bytes 219.4 instead of 208.2 MB (co
 entry that is a 2-D Linear weight with in_features = K and K % 8 == 0 is fusable.  Its no-grad calls of at most
 `_lib.LINEAR8_MAX_M` = 8 rows, under the input conditions of the 4-bit path, run `antq_linear8` -- the same product from the byte
 codes, W bit for bit the image `antq_decode8` writes (`.fused_byte_calls` counts them; `.fused_calls` stays antq_linear4's).
-`fused_rows` does not apply to byte entries (there is no matrix-core form): calls of more rows run F.linear on the image or, with
-`keep_images=False`, on the scratch decode (`antq_decode8` into the bank's one scratch buffer, which is sized to the largest
-image-less layer of either width).  `release_weights`, the "float weight is gone" error, the disabled-quantiser path and `.to()`
+`fused_rows` does not apply to byte entries (their matrix-core form has an option of its own, `fused_byte_rows` below): without
+that one, calls of more rows run F.linear on the image or, with `keep_images=False`, on the scratch decode (`antq_decode8` into
+the bank's one scratch buffer, which is sized to the largest image-less layer of either width).  `release_weights`, the "float weight is gone" error, the disabled-quantiser path and `.to()`
 / `.half()` behave as for the 4-bit layers.  Other byte-coded layers (K = 20, conv layers) keep their image as before.
 Measured (profiles/packed_linear8.md; one MI355X, one run, 5 rounds per point, medians; OPT-6.7B's and BERT-base's shapes, M = 1,
 2, 4, 8, bf16 / f16 / fp32, ANT int-8 and OliVe int-8): antq_linear8 beats decode8 + F.linear at all 120 points (1.2-6.5x); against
@@ -85,6 +85,28 @@ F.linear on the kept image it wins everywhere at M = 1 (1.3-3.2x) and M = 2 (1.0
 points (0.80-0.99x), and at M = 8 it LOSES on most 16-bit shapes (down to 0.61x) and on the wide fp32 layers (0.86-0.92x).
 BERT-base with 8 pairs at 8 bits, bf16: 216.8 MB resident with byte_codes=True, 50.4 MB with fused_linear, fused_bytes and
 keep_images=False.
+
+`fused_byte_rows=R` (with fused_linear and fused_bytes, else AntqError naming the missing one; LINEAR8_MAX_M < R <=
+LINEAR8_MM_MAX_M = 64; off by default -- without it everything above is unchanged): no-grad calls of 9 .. R rows of a fusable
+byte-coded bfloat16 / float16 layer, under the same input conditions, run `antq_linear8_mm` -- the product on the matrix cores
+from the byte codes, W bit for bit the image `antq_decode8` writes (`.fused_byte_mm_calls` counts them) -- and with
+`keep_images=False` decode nothing and leave the scratch buffer alone.  Calls of at most 8 rows still run `antq_linear8`; float32
+layers, calls of more than R rows and banks without the option keep the paths above.  `fused_rows` keeps meaning 4-bit entries
+only.  The two byte kernels sum in different orders: the same row of x has different low bits from a 3-row and from a 9-row call
+(each within the bound of an fp32 sum, each independent of the other rows).
+Measured (profiles/packed_linear8_mm.md; one MI355X, one run, 5 rounds per point with the arms alternated, medians, spread below
+6 %; M = 8 / 16 / 32 / 64, bf16 and f16, ANT int-8 and OliVe int-8, per-row scales; A = F.linear on the kept image, C =
+antq_decode8 into scratch + F.linear, B = antq_linear8_mm).  Largest M up to which B beats A / beats C in all four runs, counted
+from M = 8, per layer [N, K]: [4096, 4096] A 0, C 64; [16384, 4096] A 0, C 64; [4096, 16384] A 0, C 64; [3072, 768] A 64, C 64;
+[768, 3072] A 0, C 32.  The zeros are M = 8 (which the option does not route: B loses to A there in at least one of the four runs); the M at
+which B beats A in all four runs are [4096, 4096] 16; [16384, 4096] 16, 32; [4096, 16384] 16; [3072, 768] 8 ... 64; [768, 3072]
+none (M = 16: 0.995 ... 1.29x).  So: against the scratch decode (keep_images=False) the option is worth turning on for every
+layer measured up to R = 64 except [768, 3072], where R = 32 is the limit (M = 64: 0.78 ... 1.01x); against kept images it pays at
+M = 16 (1.0 ... 1.3x) and, beyond that, only on [16384, 4096] at 32 (1.05x) and [3072, 768] up to 64 (1.16 ... 1.53x) -- at M = 64
+B takes up to twice A's time on the other layers (0.51 ... 0.83x), and what the option buys there is the memory and the free
+scratch.  At M = 8 B beats antq_linear8 in 12 of 20 rows only (0.81 ... 1.41x): the routing up to 8 rows stays.  The tile rule of
+the 4-bit kernel (mm_ntiles) was within 7.5 % of the best forced shape in every row and is kept.  Not measured: other M, per-tensor
+scales, the 8-byte code path, a whole model's forward time, more than one run; no hardware counters were collected.
 """
 import torch
 import torch.nn.functional as F
@@ -115,16 +137,20 @@ def _settle(q):
 
 class PackedBank:
     def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True, fused_rows=None,
-                 byte_codes=False, fused_bytes=False):
+                 byte_codes=False, fused_bytes=False, fused_byte_rows=None):
         """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict);
         a layer's code width is then the one its stored size says (numel / 2 bytes: 4-bit, numel bytes: byte codes).
         byte_codes: layers the 4-bit codec refuses and the byte codec accepts are packed one code per byte (width 8).
-        fused_bytes (with fused_linear): byte-coded Linear layers of K % 8 == 0 compute from their codes too (antq_linear8)."""
+        fused_bytes (with fused_linear): byte-coded Linear layers of K % 8 == 0 compute from their codes too (antq_linear8).
+        fused_byte_rows=R (with fused_linear and fused_bytes): their bf16 / f16 calls of 9 .. R rows too (antq_linear8_mm)."""
         self.byte_codes = bool(byte_codes)
         if fused_bytes and not fused_linear:
             raise _lib.AntqError("PackedBank: fused_bytes needs fused_linear=True")
+        _check_fused_byte_rows("PackedBank", fused_linear, fused_bytes, fused_byte_rows)
         self.fused_bytes = bool(fused_bytes)     # byte-coded Linear layers with few input rows compute from the codes (antq_linear8)
         self.fused_byte_calls = 0  # forwards antq_linear8 served
+        self.fused_byte_rows = None if fused_byte_rows is None else int(fused_byte_rows)   # bf16 / f16 calls of 9 .. R rows: antq_linear8_mm
+        self.fused_byte_mm_calls = 0   # forwards antq_linear8_mm served
         if not keep_images and not fused_linear:
             raise _lib.AntqError("PackedBank: keep_images=False needs fused_linear=True (nothing else computes from the codes)")
         _check_fused_rows("PackedBank", fused_linear, fused_rows)
@@ -372,19 +398,23 @@ class PackedBank:
             return F.linear(input, weight, mod.bias)
         K = e["shape"][1]
         bias = mod.bias
-        byte = e["width"] == 8                     # (fused_rows is antq_linear4_mm's: byte codes have no matrix-core form)
+        byte = e["width"] == 8                     # (fused_rows is antq_linear4_mm's, fused_byte_rows antq_linear8_mm's)
         max_rows = _lib.LINEAR8_MAX_M if byte else _lib.LINEAR4_MAX_M
-        if not byte and self.fused_rows is not None and e["dtype"] in (torch.bfloat16, torch.float16):
-            max_rows = self.fused_rows
+        more_rows = self.fused_byte_rows if byte else self.fused_rows
+        if more_rows is not None and e["dtype"] in (torch.bfloat16, torch.float16):
+            max_rows = more_rows
         if (input.is_cuda and input.dtype == e["dtype"] and input.device == e["device"] and input.dim() >= 1 and input.shape[-1] == K
                 and 0 < input.numel() <= max_rows * K and input.is_contiguous() and input.data_ptr() % 16 == 0
                 and not (byte and e["codes"].data_ptr() % 8)
                 and not (torch.is_grad_enabled() and (input.requires_grad or (bias is not None and bias.requires_grad)))
                 and (bias is None or (bias.dtype == input.dtype and bias.is_contiguous() and bias.device == input.device))):
             plan, gmax, n_normal, ovp = _codebook(e["q"])
-            if byte:
+            if byte and input.numel() <= _lib.LINEAR8_MAX_M * K:
                 self.fused_byte_calls += 1
                 fn = _lib.linear8
+            elif byte:
+                self.fused_byte_mm_calls += 1
+                fn = _lib.linear8_mm
             elif input.numel() <= _lib.LINEAR4_MAX_M * K:
                 self.fused_calls += 1
                 fn = _lib.linear4
@@ -405,6 +435,19 @@ def _check_fused_rows(who, fused_linear, fused_rows):
         raise _lib.AntqError("%s: fused_rows must be an integer in (%d, %d] (got %r)" % (who, _lib.LINEAR4_MAX_M, _lib.LINEAR4_MM_MAX_M, fused_rows))
 
 
+def _check_fused_byte_rows(who, fused_linear, fused_bytes, fused_byte_rows):
+    if fused_byte_rows is None:
+        return
+    if not fused_linear:
+        raise _lib.AntqError("%s: fused_byte_rows needs fused_linear=True" % who)
+    if not fused_bytes:
+        raise _lib.AntqError("%s: fused_byte_rows needs fused_bytes=True" % who)
+    if not (isinstance(fused_byte_rows, int) and not isinstance(fused_byte_rows, bool)
+            and _lib.LINEAR8_MAX_M < fused_byte_rows <= _lib.LINEAR8_MM_MAX_M):
+        raise _lib.AntqError("%s: fused_byte_rows must be an integer in (%d, %d] (got %r)"
+                             % (who, _lib.LINEAR8_MAX_M, _lib.LINEAR8_MM_MAX_M, fused_byte_rows))
+
+
 def _no_auto_bank(model):
     """The automatic weight bank steps aside (as for set_weights_at_rest(resident=False)), and the choice stays with the
     module: a deep copy carries the mark, so its forward hook does not arm a fresh AutoBank for it."""
@@ -422,7 +465,7 @@ def _bank_of(model):
 
 
 def pack_model(model, release_weights=False, fused_linear=False, keep_images=True, fused_rows=None, byte_codes=False,
-               fused_bytes=False):
+               fused_bytes=False, fused_byte_rows=None):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
     (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
     byte_codes: layers the 4-bit codec refuses for their codebook (5- to 8-bit layers, OliVe's unsigned 16 + 15) or their row
@@ -430,6 +473,14 @@ def pack_model(model, release_weights=False, fused_linear=False, keep_images=Tru
     their decoded image and run F.linear on it unless fused_bytes is given.
     fused_bytes (with fused_linear): byte-coded Linear layers of K % 8 == 0 compute calls of at most _lib.LINEAR8_MAX_M rows from
     their byte codes (antq_linear8, .fused_byte_calls) and, with keep_images=False, keep no image -- see the module docstring.
+    fused_byte_rows=R (with fused_linear and fused_bytes, 8 < R <= 64): their bf16 / f16 calls of 9 .. R rows compute from the byte
+    codes on the matrix cores (antq_linear8_mm, .fused_byte_mm_calls) and, with keep_images=False, leave the scratch alone.
+    Measured (profiles/packed_linear8_mm.md, one MI355X, one run; A = F.linear on the image, C = antq_decode8 into scratch +
+    F.linear, B = antq_linear8_mm): M at which B beats A / beats C in all four runs (bf16, f16, ANT and OliVe int-8), per
+    layer [N, K]: [4096, 4096] A 16, C 8 ... 64; [16384, 4096] A 16, 32, C 8 ... 64; [4096, 16384] A 16, C 8 ... 64; [3072, 768] A
+    8 ... 64, C 8 ... 64; [768, 3072] A none, C 8 ... 32.  Worth turning on with keep_images=False (R = 64; 32 for layers like
+    [768, 3072]); with kept images only around M = 16 and for [3072, 768]-like layers.  Not measured: other M, per-tensor
+    scales, a whole model's forward time, more than one run.
     fused_linear: Linear layers called with at most _lib.LINEAR4_MAX_M input rows compute from the codes (antq_linear4);
     keep_images=False (with fused_linear): those layers keep no decoded image -- see the module docstring.
     fused_rows=R (with fused_linear, 8 < R <= 64): bf16 / f16 calls of 9 .. R rows compute from the codes on the matrix cores
@@ -445,7 +496,7 @@ def pack_model(model, release_weights=False, fused_linear=False, keep_images=Tru
     scaling, no hardware counters were collected.  Not measured: other M, the 4-byte code path, per-tensor scales, a whole
     model, more than one run per point.  The 16-bit MFMA keeps subnormal operands (measured): W is the image there too."""
     return PackedBank(model, release_weights=release_weights, fused_linear=fused_linear, keep_images=keep_images, fused_rows=fused_rows,
-                      byte_codes=byte_codes, fused_bytes=fused_bytes)
+                      byte_codes=byte_codes, fused_bytes=fused_bytes, fused_byte_rows=fused_byte_rows)
 
 
 def packed_state_dict(model):
@@ -467,17 +518,18 @@ def _packed_keys(sd, codes):
 
 
 def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, keep_images=True, fused_rows=None,
-                           fused_bytes=False):
+                           fused_bytes=False, fused_byte_rows=None):
     """Load a packed checkpoint into a freshly wrapped, uncalibrated model living on the GPU: the quantiser state is
     installed the way load_ant_state_dict + load_state_dict do (scales keep the dtype they were stored with), a PackedBank is attached from the stored codes without
     re-encoding (a layer's code width is the one its stored size says: numel / 2 bytes are 4-bit codes, numel bytes byte codes;
     any other size raises AntqError naming the layer), and the weights are materialised by the batched decode
-    (release_weights=False: copied into the layers' own float weights instead of replacing them).  fused_linear / keep_images / fused_rows / fused_bytes: as in pack_model (the code width still comes from the stored size).  Returns the bank."""
+    (release_weights=False: copied into the layers' own float weights instead of replacing them).  fused_linear / keep_images / fused_rows / fused_bytes / fused_byte_rows: as in pack_model (the code width still comes from the stored size).  Returns the bank."""
     if not keep_images and not fused_linear:
         raise _lib.AntqError("load_packed_state_dict: keep_images=False needs fused_linear=True")
     _check_fused_rows("load_packed_state_dict", fused_linear, fused_rows)
     if fused_bytes and not fused_linear:
         raise _lib.AntqError("load_packed_state_dict: fused_bytes needs fused_linear=True")
+    _check_fused_byte_rows("load_packed_state_dict", fused_linear, fused_bytes, fused_byte_rows)
     suffix = "." + CODES_KEY
     codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}
     rest = {k: v for k, v in sd.items() if not k.endswith(suffix)}
@@ -496,7 +548,7 @@ def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, 
     for _, _, q, _ in _weight_layers(model):
         _settle(q)
     bank = PackedBank(model, release_weights=release_weights, codes=codes, fused_linear=fused_linear, keep_images=keep_images,
-                      fused_rows=fused_rows, fused_bytes=fused_bytes)
+                      fused_rows=fused_rows, fused_bytes=fused_bytes, fused_byte_rows=fused_byte_rows)
     if not release_weights:
         with torch.no_grad():
             for e in bank.entries.values():

@@ -45,7 +45,8 @@ extern "C" {
  * Still 7: antq_decode4_batch_capacity / antq_decode4_batch_build / antq_decode4_batch added (the batched packed decoder; nothing
  * that existed changed, so callers built against 7 keep working).  antq_linear4 (the packed 4-bit linear) added likewise,
  * and antq_linear4_mm (its matrix-core form for up to 64 rows), and antq_encode8 / antq_decode8 / antq_decode8_batch_capacity /
- * antq_decode8_batch_build / antq_decode8_batch (the byte-code codec), and antq_linear8 (the linear from byte codes).
+ * antq_decode8_batch_build / antq_decode8_batch (the byte-code codec), and antq_linear8 (the linear from byte codes), and
+ * antq_linear8_mm (its matrix-core form for up to 64 rows).
  * A caller built against another version must not call in: the blobs / argument lists differ. */
 #define ANTQ_ABI_VERSION 7
 
@@ -500,7 +501,7 @@ int    antq_decode4_batch(const void *batch_host, const void *batch_dev, void *s
  * The batch entry points are antq_decode4_batch's with antq_decode_job as it is -- codes_dev holds rows*row_len bytes --
  * and the same rules for n, flags and n_normal; the builder is pure host code and touches no HIP.  All launches are
  * stream-ordered and capturable: no allocation, no synchronisation, no workspace.  antq_linear4 and antq_linear4_mm take
- * 4-bit codes only; antq_linear8 (below) is the linear from byte codes, for 1 .. 8 rows of x (no matrix-core form yet).
+ * 4-bit codes only; antq_linear8 (below) is the linear from byte codes for 1 .. 8 rows of x, antq_linear8_mm its matrix-core form.
  * ------------------------------------------------------------------------- */
 int antq_encode8(const void *x_dev, uint8_t *codes_dev, size_t rows, size_t row_len,
                  const float *alpha_dev, int alpha_per_row, float gmax,
@@ -608,6 +609,37 @@ int antq_linear8(const uint8_t *codes_dev,          /* N*K bytes, antq_encode8's
                  const float *grid_dev, int m, int n_normal,   /* as in antq_decode_job */
                  unsigned flags /* 0 | ANTQ_FLAG_OVP */, int dtype /* F32 | BF16 | F16 */, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * The same product for 1 .. ANTQ_LINEAR8_MM_MAX_M rows of x on the matrix cores (v_mfma_f32_16x16x32_bf16 / _f16), BF16 and
+ * F16 only: antq_linear4_mm for byte codes.  Parameters as antq_linear8.
+ *   W[n,k] is, bit for bit, the element antq_decode8 writes in `dtype` (per output row a table of the decoder's finished
+ *          16-bit outputs keyed by the code byte, with the pair rule a second one for the outlier list; two look-ups are one
+ *          MFMA operand register; the scale is never factored out of the sum).
+ *   y[m,n] = round_dtype( sum_k x[m,k] * W[n,k] + bias[n] ): products exact, the sum in fp32 in the MFMA accumulator, the bias
+ *          added in fp32, one rounding to `dtype`.
+ *   The bits of y[m,n] depend only on row m of x, row n of W, bias[n], K and the code path (below): not on M, not on N, not on
+ *          the other rows of x, not on the run.  K is split between the eight wavefronts of a workgroup by a rule of K alone and
+ *          their partial sums are combined through LDS in one fixed order.  The order of the sum is NOT antq_linear8's: the
+ *          same row has different low bits from the two entry points (both within the bound of an fp32 sum).
+ *   No floating-point atomics, no split of K across workgroups, no workspace, no allocation, no synchronisation: stream-ordered
+ *          and capturable into a graph.  Reads stay inside the buffers; padded rows contribute exactly +0 and are not stored.
+ *   At most 64 KB of LDS per workgroup (64 output rows with the pair rule), the size every launch may have.
+ * Checked before anything touches HIP, in this order:
+ *   ANTQ_ERR_ARG          as antq_linear8
+ *   ANTQ_OK, no launch    M == 0 or N == 0
+ *   ANTQ_ERR_UNSUPPORTED  dtype == ANTQ_F32 (such layers stay with antq_linear8); M > ANTQ_LINEAR8_MM_MAX_M; K == 0 or
+ *                         K % 8 != 0; the byte decoder's refusals; N >= 2^31 or K >= 2^31
+ *   ANTQ_ERR_ALIGN        x_dev not 16-byte aligned, codes_dev not 8-byte aligned, y_dev / bias_dev not 2-byte aligned
+ * Codes are read 16 bytes per lane when K % 16 == 0 and codes_dev is 16-byte aligned, 8 bytes per lane otherwise (the order
+ * of the sum differs between the two, nothing else).  Measurements: profiles/packed_linear8_mm.md.
+ * ------------------------------------------------------------------------- */
+#define ANTQ_LINEAR8_MM_MAX_M 64
+int antq_linear8_mm(const uint8_t *codes_dev, const void *x_dev, const void *bias_dev, void *y_dev,
+                    size_t M, size_t N, size_t K,
+                    const float *alpha_dev, int alpha_per_row, float gmax,
+                    const float *grid_dev, int m, int n_normal,
+                    unsigned flags /* 0 | ANTQ_FLAG_OVP */, int dtype /* BF16 | F16 */, void *stream);
+
 /* -------------------------------------------------------------------------
  * OliVe's clip statistic on ONE read (replaces t.mean() + t.std() of olive_quantization/antquant/quant_modules.py:193-197
  * and :213-218, which read the tensor at least three times before the clip search reads it again).
@@ -663,7 +695,7 @@ int antq_copy(const void *src_dev, void *dst_dev, size_t bytes, void *stream);
  *           tensors with one scale from 1 M elements): 0 off, 1 (default), 2 every eligible launch (rows from 128 elements
  *           with or without the pair rule, one-scale fp32 tensors from 4096)
  *   key 21: 0 sends rows of <= 1024 elements through the 4096-key kernel instead of one row per wavefront (A/B)
- *   key 22: antq_linear4_mm: tiles of 16 output rows per workgroup, 1 / 2 / 4 (A/B; 0 = the launcher's rule; no result changes) */
+ *   key 22: antq_linear4_mm / antq_linear8_mm: tiles of 16 output rows per workgroup, 1 / 2 / 4 (A/B; 0 = the launcher's rule; no result changes) */
 int antq_debug_set(int key, int value);
 
 /* Load the library's GPU code objects for the current device now (HIP would load each of them at the first launch of one
