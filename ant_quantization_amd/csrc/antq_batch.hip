@@ -6,9 +6,8 @@
 #include "antq_k_decbatch.h"
 #include "antq_k_decbatch8.h"
 #include "antq_k_linear4.h"
-#include "antq_k_linear4_mm.h"
 #include "antq_k_linear8.h"
-#include "antq_k_linear8_mm.h"
+#include "antq_k_linear_mm.h"
 
 #include <type_traits>
 
@@ -458,11 +457,18 @@ static int linear_checks(const uint8_t *codes, const void *x, const void *bias, 
     return kLinearGo;
 }
 
+// 16 B of codes per lane: K a multiple of the elements 16 bytes hold (4-bit: 32, bytes: 16) and the codes 16-byte aligned
+template <template <typename, bool> class Codec>
+static bool linear_vec(const uint8_t *codes, size_t K)
+{
+    return K % (32 / Codec<float, false>::WORDS) == 0 && reinterpret_cast<uintptr_t>(codes) % 16 == 0;
+}
+
 // The launch of the row-streaming linear (antq_k_linear.h) for 1 .. 8 rows of x; Codec is Lin4Codec or Lin8Codec.
 template <template <typename, bool> class Codec>
 static int launch_linear(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
-                         const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal, bool ovp, bool vec,
-                         int dtype, void *stream)
+                         const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal, bool ovp, int dtype,
+                         void *stream)
 {
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int mt = M <= 2 ? (int)M : (M <= 4 ? 4 : 8);           // rows the kernel computes: 3 runs as 4, 5 .. 7 as 8
@@ -470,13 +476,42 @@ static int launch_linear(const uint8_t *codes, const void *x, const void *bias, 
         using T = decltype(tag);
         return with_bool(ovp, [&](auto o) {
             return with_value<1, 2, 4, 8>(mt, [&](auto mm) {
-                return with_bool(vec, [&](auto v) {
+                return with_bool(linear_vec<Codec>(codes, K), [&](auto v) {
                     constexpr int MT = decltype(mm)::value;
                     const unsigned blocks = (unsigned)((N + lin_rows(MT) - 1) / lin_rows(MT));
                     launch_k(false, k_linear<Codec<T, decltype(o)::value>, MT, decltype(v)::value>, dim3(blocks), dim3(64u), 0, st,
                              codes, x, bias, y, (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha, per_row ? 1 : 0, gmax, grid,
                              (uint32_t)m, ovp ? n_normal : 0);
                     return launch_status();
+                });
+            });
+        });
+    });
+}
+
+// The launch of the matrix-core linear (antq_k_linear_mm.h) for 1 .. 64 rows of x, bf16 / f16; Codec as above.
+template <template <typename, bool> class Codec>
+static int launch_linear_mm(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
+                            const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal, bool ovp, int dtype,
+                            void *stream)
+{
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int mt = mm_mtiles(M);
+    const int nt = one_of<1, 2, 4>(g_knob_mm_tile, mm_ntiles(M, N));
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if constexpr (std::is_same<T, float>::value) return (int)ANTQ_ERR_UNSUPPORTED;
+        else return with_bool(ovp, [&](auto o) {
+            return with_value<1, 2, 4>(mt, [&](auto mm) {
+                return with_value<1, 2, 4>(nt, [&](auto nn) {
+                    return with_bool(linear_vec<Codec>(codes, K), [&](auto v) {
+                        constexpr int NT = decltype(nn)::value;
+                        const unsigned blocks = (unsigned)((N + 16 * NT - 1) / (16 * NT));
+                        launch_k(false, k_linear_mm<Codec<T, decltype(o)::value>, decltype(mm)::value, NT, decltype(v)::value>, dim3(blocks),
+                                 dim3(64u * kMmWaves), 0, st, reinterpret_cast<const uint32_t *>(codes), x, bias, y, (uint32_t)M, (uint32_t)N,
+                                 (uint32_t)K, alpha, per_row ? 1 : 0, gmax, grid, (uint32_t)m, ovp ? n_normal : 0);
+                        return launch_status();
+                    });
                 });
             });
         });
@@ -491,12 +526,11 @@ extern "C" int antq_linear4(const uint8_t *codes, const void *x, const void *bia
     const int rc = linear_checks(codes, x, bias, y, M, N, K, alpha, grid, m, n_normal, flags, dtype, ANTQ_LINEAR4_MAX_M, false,
                                  dec4_book_ok, 4, dtype == ANTQ_F32 ? 4 : 2);
     if (rc != kLinearGo) return rc;
-    const bool vec = K % 32 == 0 && reinterpret_cast<uintptr_t>(codes) % 16 == 0;     // 16 B of codes per lane
     return launch_linear<Lin4Codec>(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0,
-                                    vec, dtype, stream);
+                                    dtype, stream);
 }
 
-// The same product for 1 .. ANTQ_LINEAR4_MM_MAX_M rows of x on the matrix cores (antq_k_linear4_mm.h; bf16 / f16).
+// The same product for 1 .. ANTQ_LINEAR4_MM_MAX_M rows of x on the matrix cores (antq_k_linear_mm.h; bf16 / f16).
 extern "C" int antq_linear4_mm(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
                                const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
                                unsigned flags, int dtype, void *stream)
@@ -505,29 +539,8 @@ extern "C" int antq_linear4_mm(const uint8_t *codes, const void *x, const void *
     const int rc = linear_checks(codes, x, bias, y, M, N, K, alpha, grid, m, n_normal, flags, dtype, ANTQ_LINEAR4_MM_MAX_M, true,
                                  dec4_book_ok, 4, 2);
     if (rc != kLinearGo) return rc;
-    const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
-    const bool vec = K % 32 == 0 && reinterpret_cast<uintptr_t>(codes) % 16 == 0;     // 16 B of codes per lane
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int mt = mm_mtiles(M);
-    const int nt = one_of<1, 2, 4>(g_knob_mm_tile, mm_ntiles(M, N));
-    return with_dtype(dtype, [&](auto tag) {
-        using T = decltype(tag);
-        if constexpr (std::is_same<T, float>::value) return (int)ANTQ_ERR_UNSUPPORTED;
-        else return with_bool(ovp, [&](auto o) {
-            return with_value<1, 2, 4>(mt, [&](auto mm) {
-                return with_value<1, 2, 4>(nt, [&](auto nn) {
-                    return with_bool(vec, [&](auto v) {
-                        constexpr int NT = decltype(nn)::value;
-                        const unsigned blocks = (unsigned)((N + 16 * NT - 1) / (16 * NT));
-                        launch_k(false, k_linear4_mm<T, decltype(o)::value, decltype(mm)::value, NT, decltype(v)::value>, dim3(blocks),
-                                 dim3(64u * kMmWaves), 0, st, reinterpret_cast<const uint32_t *>(codes), x, bias, y, (uint32_t)M, (uint32_t)N,
-                                 (uint32_t)K, alpha, per_row ? 1 : 0, gmax, grid, (uint32_t)m, ovp ? n_normal : 0);
-                        return launch_status();
-                    });
-                });
-            });
-        });
-    });
+    return launch_linear_mm<Lin4Codec>(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0,
+                                       dtype, stream);
 }
 
 // The byte-code form of antq_linear4 (antq_k_linear8.h): the same launch, W the image antq_decode8 writes.
@@ -538,13 +551,12 @@ extern "C" int antq_linear8(const uint8_t *codes, const void *x, const void *bia
     const int rc = linear_checks(codes, x, bias, y, M, N, K, alpha, grid, m, n_normal, flags, dtype, ANTQ_LINEAR8_MAX_M, false,
                                  dec8_book_ok, 8, dtype == ANTQ_F32 ? 4 : 2);
     if (rc != kLinearGo) return rc;
-    const bool vec = K % 16 == 0 && reinterpret_cast<uintptr_t>(codes) % 16 == 0;     // 16 B of codes per lane
     return launch_linear<Lin8Codec>(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0,
-                                    vec, dtype, stream);
+                                    dtype, stream);
 }
 
-// The byte-code form of antq_linear4_mm (antq_k_linear8_mm.h): 1 .. ANTQ_LINEAR8_MM_MAX_M rows of x on the matrix cores, W the
-// image antq_decode8 writes; bf16 / f16.
+// The byte-code form of antq_linear4_mm: 1 .. ANTQ_LINEAR8_MM_MAX_M rows of x on the matrix cores, W the image antq_decode8
+// writes; bf16 / f16.
 extern "C" int antq_linear8_mm(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
                                const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
                                unsigned flags, int dtype, void *stream)
@@ -552,29 +564,8 @@ extern "C" int antq_linear8_mm(const uint8_t *codes, const void *x, const void *
     const int rc = linear_checks(codes, x, bias, y, M, N, K, alpha, grid, m, n_normal, flags, dtype, ANTQ_LINEAR8_MM_MAX_M, true,
                                  dec8_book_ok, 8, 2);
     if (rc != kLinearGo) return rc;
-    const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
-    const bool vec = K % 16 == 0 && reinterpret_cast<uintptr_t>(codes) % 16 == 0;     // 16 B of codes per lane
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int mt = mm_mtiles(M);
-    const int nt = one_of<1, 2, 4>(g_knob_mm_tile, mm_ntiles(M, N));
-    return with_dtype(dtype, [&](auto tag) {
-        using T = decltype(tag);
-        if constexpr (std::is_same<T, float>::value) return (int)ANTQ_ERR_UNSUPPORTED;
-        else return with_bool(ovp, [&](auto o) {
-            return with_value<1, 2, 4>(mt, [&](auto mm) {
-                return with_value<1, 2, 4>(nt, [&](auto nn) {
-                    return with_bool(vec, [&](auto v) {
-                        constexpr int NT = decltype(nn)::value;
-                        const unsigned blocks = (unsigned)((N + 16 * NT - 1) / (16 * NT));
-                        launch_k(false, k_linear8_mm<T, decltype(o)::value, decltype(mm)::value, NT, decltype(v)::value>, dim3(blocks),
-                                 dim3(64u * kMmWaves), 0, st, reinterpret_cast<const uint32_t *>(codes), x, bias, y, (uint32_t)M, (uint32_t)N,
-                                 (uint32_t)K, alpha, per_row ? 1 : 0, gmax, grid, (uint32_t)m, ovp ? n_normal : 0);
-                        return launch_status();
-                    });
-                });
-            });
-        });
-    });
+    return launch_linear_mm<Lin8Codec>(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0,
+                                       dtype, stream);
 }
 
 namespace antq {

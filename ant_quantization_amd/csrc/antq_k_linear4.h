@@ -1,5 +1,6 @@
 // antq_k_linear4.h -- the packed 4-bit codec of the row-streaming linear (antq_k_linear.h: k_linear; antq_linear4), and the
-// 4-bit byte table's one definition, which the matrix-core kernel (antq_k_linear4_mm.h) builds its tables from too.
+// 4-bit byte table's one definition; the codec's last members are its part of the matrix-core kernel (antq_k_linear_mm.h:
+// k_linear_mm; antq_linear4_mm).
 // Part of libantq's batched translation unit (antq_batch.hip includes it); gfx950 only.
 //
 //   loads      16 B (VEC: 32 elements) or 4 B (8 elements) of codes per lane and row
@@ -12,6 +13,7 @@
 
 #include "antq_k_decbatch.h"
 #include "antq_k_linear.h"
+#include "antq_k_linear_mm.h"
 
 namespace antq {
 
@@ -94,6 +96,36 @@ template <typename T, bool OVP> struct Lin4Codec {
                 acc[i][r] = __builtin_fmaf(xf[i][2 * p + 1], w1, acc[i][r]);
             }
         }
+    }
+
+    // The matrix-core kernel's part (antq_k_linear_mm.h: k_linear_mm): the same table for 16 NT rows, built by 512 threads
+    // with the codebook and the rows' scales staged in LDS.
+    typedef Ent MmEnt;
+    template <int ROWS> struct MmLds {
+        __attribute__((aligned(16))) Ent tab[ROWS * 256];
+        float g[32];
+        float sc[ROWS];
+    };
+    // (the 64 x 64 tile with 16 B of codes per lane has no registers for x in the ring)
+    static constexpr bool mm_x_in_ring(int MT, int NT, bool VEC) { return !(MT == 4 && NT == 4 && VEC); }
+
+    template <int ROWS>
+    __device__ __forceinline__ static void mm_build(MmLds<ROWS> &L, uint32_t tid, uint32_t row0, uint32_t N, const float *alpha, int per_row,
+                                                    float gmax, const float *grid, uint32_t m, int n_normal)
+    {
+        lin4_book(L.g, tid, grid, m);
+        if (tid < (per_row ? (uint32_t)ROWS : 1u)) L.sc[tid] = ld_global(alpha + (per_row ? min(row0 + tid, N - 1u) : 0u)) / gmax;   // AQ:536 scale = alpha / max(grid)
+        __syncthreads();
+        const uint32_t b = tid & 255u;                 // threads b and 256 + b make entry b of the even and the odd tables
+        const Lin4Entry<T, OVP> e(b, L.g, n_normal);
+        for (uint32_t r = tid >> 8; r < (per_row ? (uint32_t)ROWS : 1u); r += 2u) L.tab[r * 256u + b] = e.at(L.sc[r]);
+        __syncthreads();
+    }
+
+    // one code word is the step's 8 elements: four look-ups ARE the four operand registers
+    __device__ __forceinline__ static u32x4_t mm_b(const Ent *t, const uint32_t *w)
+    {
+        return u32x4_t{t[w[0] & 0xffu], t[(w[0] >> 8) & 0xffu], t[(w[0] >> 16) & 0xffu], t[w[0] >> 24]};
     }
 };
 

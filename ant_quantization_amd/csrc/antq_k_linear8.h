@@ -1,5 +1,6 @@
 // antq_k_linear8.h -- the BYTE-code codec of the row-streaming linear (antq_k_linear.h: k_linear; antq_linear8): the byte
-// decoder's rule (antq_k_decbatch8.h: dec8_book, dec8_slot, Dec8Out), so that W[n, k] IS the element antq_decode8 writes.
+// decoder's rule (antq_k_decbatch8.h: dec8_book, dec8_slot, Dec8Out), so that W[n, k] IS the element antq_decode8 writes.  The
+// codec's last members are its part of the matrix-core kernel (antq_k_linear_mm.h: k_linear_mm; antq_linear8_mm).
 // Part of libantq's batched translation unit (antq_batch.hip includes it); gfx950 only.
 //
 //   loads      16 B (VEC: 16 elements) or 8 B (8 elements) of codes per lane and row
@@ -12,6 +13,7 @@
 
 #include "antq_k_decbatch8.h"
 #include "antq_k_linear.h"
+#include "antq_k_linear_mm.h"
 
 namespace antq {
 
@@ -73,6 +75,55 @@ template <typename T, bool OVP> struct Lin8Codec {
         for (int e = 0; e < 8; e++)
 #pragma unroll
             for (int i = 0; i < M; i++) acc[i][r] = __builtin_fmaf(xf[i][e], wv[e], acc[i][r]);
+    }
+
+    // The matrix-core kernel's part (antq_k_linear_mm.h: k_linear_mm; bf16 / f16): the same tables for 16 NT rows, of the
+    // decoder's finished 16-bit outputs as they are -- Dec8Out<T>::make(g * s), the multiplication done for every entry as the
+    // decoder does it.  16 NT rows x 256 or 512 entries x 2 B: 64 KB at the most (NT = 4, pair rule), and nothing else lives
+    // in LDS, so no variant needs more than the 64 KB every launch may have.
+    typedef typename Dec8Out<T>::Ent MmEnt;
+    template <int ROWS> struct MmLds {
+        __attribute__((aligned(16))) MmEnt tab[ROWS * TS];
+        static_assert(sizeof(MmEnt) == 2 && sizeof(tab) <= 65536, "two entries are one operand register; the tables fit every launch");
+    };
+    static constexpr bool mm_x_in_ring(int, int, bool) { return true; }
+
+    // Every wavefront holds the book in registers (dec8_book's four entries per lane) and builds whole rows r = w, w + 8, ...:
+    // no staging array and no second barrier.
+    template <int ROWS>
+    __device__ __forceinline__ static void mm_build(MmLds<ROWS> &L, uint32_t tid, uint32_t row0, uint32_t N, const float *alpha, int per_row,
+                                                    float gmax, const float *grid, uint32_t m, int n_normal)
+    {
+        const uint32_t lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        DecDesc D;
+        D.grid = grid; D.m = m; D.n_normal = n_normal;
+        float nv[4], ov[4];
+        dec8_book<OVP>(D, lane, nv, ov);
+        for (uint32_t r = wave; r < (per_row ? (uint32_t)ROWS : 1u); r += kMmWaves) {
+            const float s = ld_global(alpha + (per_row ? min(row0 + r, N - 1u) : 0u)) / gmax;   // AQ:536 scale = alpha / max(grid)
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint32_t b = lane + 64u * k;
+                L.tab[r * TS + b] = Dec8Out<T>::make(nv[k] * s);
+                if (OVP) L.tab[r * TS + 256u + b] = Dec8Out<T>::make(ov[k] * s);
+            }
+        }
+        __syncthreads();
+    }
+
+    // two code words are the step's 8 elements; two 16-bit look-ups are one operand register
+    __device__ __forceinline__ static u32x4_t mm_b(const MmEnt *t, const uint32_t *w)
+    {
+        uint32_t c[8];
+#pragma unroll
+        for (int e = 0; e < 4; e++) { c[e] = (w[0] >> (8 * e)) & 0xffu; c[4 + e] = (w[1] >> (8 * e)) & 0xffu; }
+        uint32_t o[4];
+#pragma unroll
+        for (int p = 0; p < 4; p++) {                   // (flat pairs (2k, 2k + 1): the partner is the byte next door)
+            const uint32_t lo = t[dec8_slot<OVP>(c[2 * p], c[2 * p + 1])], hi = t[dec8_slot<OVP>(c[2 * p + 1], c[2 * p])];
+            o[p] = lo | (hi << 16);
+        }
+        return u32x4_t{o[0], o[1], o[2], o[3]};
     }
 };
 

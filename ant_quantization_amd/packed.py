@@ -426,26 +426,24 @@ class PackedBank:
         return F.linear(input, weight if e["out"] is not None else self._image(e), bias)
 
 
-def _check_fused_rows(who, fused_linear, fused_rows):
-    if fused_rows is None:
+def _check_rows_option(who, name, rows, needs, lo, hi):
+    """rows is None, or an integer (not a bool) in (lo, hi] with every option of `needs` (name, value) switched on"""
+    if rows is None:
         return
-    if not fused_linear:
-        raise _lib.AntqError("%s: fused_rows needs fused_linear=True" % who)
-    if not (isinstance(fused_rows, int) and not isinstance(fused_rows, bool) and _lib.LINEAR4_MAX_M < fused_rows <= _lib.LINEAR4_MM_MAX_M):
-        raise _lib.AntqError("%s: fused_rows must be an integer in (%d, %d] (got %r)" % (who, _lib.LINEAR4_MAX_M, _lib.LINEAR4_MM_MAX_M, fused_rows))
+    for need, on in needs:
+        if not on:
+            raise _lib.AntqError("%s: %s needs %s=True" % (who, name, need))
+    if not (isinstance(rows, int) and not isinstance(rows, bool) and lo < rows <= hi):
+        raise _lib.AntqError("%s: %s must be an integer in (%d, %d] (got %r)" % (who, name, lo, hi, rows))
+
+
+def _check_fused_rows(who, fused_linear, fused_rows):
+    _check_rows_option(who, "fused_rows", fused_rows, (("fused_linear", fused_linear),), _lib.LINEAR4_MAX_M, _lib.LINEAR4_MM_MAX_M)
 
 
 def _check_fused_byte_rows(who, fused_linear, fused_bytes, fused_byte_rows):
-    if fused_byte_rows is None:
-        return
-    if not fused_linear:
-        raise _lib.AntqError("%s: fused_byte_rows needs fused_linear=True" % who)
-    if not fused_bytes:
-        raise _lib.AntqError("%s: fused_byte_rows needs fused_bytes=True" % who)
-    if not (isinstance(fused_byte_rows, int) and not isinstance(fused_byte_rows, bool)
-            and _lib.LINEAR8_MAX_M < fused_byte_rows <= _lib.LINEAR8_MM_MAX_M):
-        raise _lib.AntqError("%s: fused_byte_rows must be an integer in (%d, %d] (got %r)"
-                             % (who, _lib.LINEAR8_MAX_M, _lib.LINEAR8_MM_MAX_M, fused_byte_rows))
+    _check_rows_option(who, "fused_byte_rows", fused_byte_rows, (("fused_linear", fused_linear), ("fused_bytes", fused_bytes)),
+                       _lib.LINEAR8_MAX_M, _lib.LINEAR8_MM_MAX_M)
 
 
 def _no_auto_bank(model):

@@ -2,7 +2,7 @@
 test_linear8_mm_cases_host.py holds the very same arrays to their premises with numpy and the CPU oracle alone.  Nothing here
 touches the HIP library.  Books, codes and the decoder's rule restated in numpy are linear8_cases' and byte_codes_cases'.
 
-The kernel's own constants (csrc/antq_k_linear8_mm.h): K is cut into chunks of 64 elements (codes read 16 bytes per lane:
+The kernel's own constants (csrc/antq_k_linear_mm.h with Lin8Codec): K is cut into chunks of 64 elements (codes read 16 bytes per lane:
 K % 16 == 0 and 16-byte-aligned codes) or of 32 (8 bytes per lane), dealt to eight wavefronts in turn, so w = 1 .. 8 wavefronts
 have work up to K = 64 w and 32 w; a wavefront keeps a ring of D = 4 / 3 / 2 chunks (1 / 2 / 4 tiles of 16 rows of x) and
 refills it for the first time when K holds more than 8 D chunks."""

@@ -1,4 +1,4 @@
-"""The packed 4-bit linear on the matrix cores: antq_linear4_mm (csrc/antq_k_linear4_mm.h) computes y = x . W^T (+ bias) for
+"""The packed 4-bit linear on the matrix cores: antq_linear4_mm (csrc/antq_k_linear_mm.h with Lin4Codec) computes y = x . W^T (+ bias) for
 1 .. 64 rows of bf16 / f16 x from the code bytes with v_mfma_f32_16x16x32, W being the image antq_decode4 writes.  The
 yardsticks are those of test_gpu_linear4.py: include/antq.h's decode rule restated in numpy on the code bytes, and float64.
 Exact tests compare bits; the general test holds the result to the derived bound of an fp32 sum.

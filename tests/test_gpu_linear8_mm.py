@@ -1,4 +1,4 @@
-"""The byte-code linear on the matrix cores: antq_linear8_mm (csrc/antq_k_linear8_mm.h) computes y = x . W^T (+ bias) for
+"""The byte-code linear on the matrix cores: antq_linear8_mm (csrc/antq_k_linear_mm.h with Lin8Codec) computes y = x . W^T (+ bias) for
 1 .. 64 rows of bf16 / f16 x from the code bytes with v_mfma_f32_16x16x32, W being the image antq_decode8 writes.  The
 yardstick is byte_codes_cases.decode_ref (include/antq.h restated in numpy) and float64.  Exact tests compare bits; the general
 test holds the result to the derived bound of an fp32 sum (test_gpu_linear4_mm._within_bound).  The inputs come from
