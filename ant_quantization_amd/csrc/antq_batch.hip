@@ -8,6 +8,7 @@
 #include "antq_k_linear4.h"
 #include "antq_k_linear8.h"
 #include "antq_k_linear_mm.h"
+#include "antq_k_linear_gemm.h"
 
 #include <type_traits>
 
@@ -518,6 +519,33 @@ static int launch_linear_mm(const uint8_t *codes, const void *x, const void *bia
     });
 }
 
+// The launch of the tiled matrix-core linear (antq_k_linear_gemm.h) for 1 .. 4096 rows of x, bf16 / f16, 4-bit codes: one
+// workgroup per (64 WAVES rows of x, 64 output rows) tile.
+static int launch_linear_gemm(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
+                              const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal, bool ovp, int dtype,
+                              void *stream)
+{
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int waves = one_of<2, 4>(g_knob_gemm_tile, gemm_waves(M, N));
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if constexpr (std::is_same<T, float>::value) return (int)ANTQ_ERR_UNSUPPORTED;
+        else return with_bool(ovp, [&](auto o) {
+            return with_value<2, 4>(waves, [&](auto wv) {
+                return with_bool(linear_vec<Lin4Codec>(codes, K), [&](auto v) {
+                    constexpr int WAVES = decltype(wv)::value;
+                    constexpr size_t BM = (size_t)kGemmWaveRows * WAVES;
+                    const dim3 blocks((unsigned)((N + kGemmBN - 1) / kGemmBN), (unsigned)((M + BM - 1) / BM));
+                    launch_k(false, k_linear4_gemm<T, decltype(o)::value, WAVES, decltype(v)::value>, blocks, dim3(64u * WAVES), 0, st,
+                             reinterpret_cast<const uint32_t *>(codes), x, bias, y, (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha,
+                             per_row ? 1 : 0, gmax, grid, (uint32_t)m, ovp ? n_normal : 0);
+                    return launch_status();
+                });
+            });
+        });
+    });
+}
+
 // y = x . W^T (+ bias) for 1 .. ANTQ_LINEAR4_MAX_M rows of x from the packed codes of W (antq_k_linear4.h).
 extern "C" int antq_linear4(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
                             const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
@@ -541,6 +569,18 @@ extern "C" int antq_linear4_mm(const uint8_t *codes, const void *x, const void *
     if (rc != kLinearGo) return rc;
     return launch_linear_mm<Lin4Codec>(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0,
                                        dtype, stream);
+}
+
+// The same product for 1 .. ANTQ_LINEAR4_GEMM_MAX_M rows of x as a tiled matrix-core product (antq_k_linear_gemm.h; bf16 / f16).
+extern "C" int antq_linear4_gemm(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
+                                 const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
+                                 unsigned flags, int dtype, void *stream)
+{
+    const int rc = linear_checks(codes, x, bias, y, M, N, K, alpha, grid, m, n_normal, flags, dtype, ANTQ_LINEAR4_GEMM_MAX_M, true,
+                                 dec4_book_ok, 4, 2);
+    if (rc != kLinearGo) return rc;
+    return launch_linear_gemm(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0, dtype,
+                              stream);
 }
 
 // The byte-code form of antq_linear4 (antq_k_linear8.h): the same launch, W the image antq_decode8 writes.

@@ -57,6 +57,25 @@ and the table look-ups below -- inferred from the scaling, no hardware counters 
 4-byte code path, per-tensor scales, a whole model, more than one run per point.  The 16-bit MFMA keeps subnormal operands
 (measured): W is the image there too.
 
+`fused_gemm_rows=R` (with fused_linear; LINEAR4_MM_MAX_M = 64 < R <= LINEAR4_GEMM_MAX_M = 4096; off by default -- without it
+everything above is unchanged) extends the same to calls with more rows than the other kernels take -- more than 8, or more than
+`fused_rows` when that is given -- and at most R rows of bfloat16 / float16 4-bit layers: they run `antq_linear4_gemm`, a tiled
+matrix-core product straight from the codes (`.fused_gemm_calls` counts them; one fp32 accumulator chain per output, its own
+order of the sum), and with `keep_images=False` decode nothing and leave the scratch buffer alone, so the scratch's lifetime rule
+does not apply to them.  Calls of more than R rows, float32 layers and byte-coded entries keep the paths above.
+Measured (profiles/packed_linear4_gemm.md; one MI355X, one run, 5 repetitions of 200 graph-replayed calls per point with the
+arms alternated, medians, spread below 8 %; M = 64 / 128 / 256 / 512 / 1024 / 4096, the five layer shapes above, bf16 and f16,
+ANT flint-4 and OliVe, per-row scales; A = F.linear on the kept image, C = antq_decode4 into scratch + F.linear, B =
+antq_linear4_gemm): B LOSES to C and to A at all 120 points, so there is no M up to which the option is worth choosing for
+speed on any layer measured.  Closest to C: [16384, 4096] at M = 128 / 256 (C / B 0.83 ... 0.92) and [3072, 768] at M = 512 /
+1024 (0.65 ... 0.84); elsewhere B takes 1.3 ... 5 times C's time (3.6 ... 3.9 times at M = 4096 on the wide layers), and at M =
+64 it takes 2.9 ... 4.7 times antq_linear4_mm's, so give fused_rows=64 beside it.  The kernel tops out at 356 ... 404 TFLOP/s,
+a quarter of F.linear's rate: one workgroup per CU, and by the count of LDS instructions per step the table look-ups (every
+wavefront decodes all 64 output rows of the tile itself) and the two barriers per step bound it -- inferred from arithmetic
+and scaling, no hardware counters.  What the option buys is the memory (no decoded image, a quarter of the weight bytes) and
+the free scratch buffer, at those prices.  Not measured: other M, the 4-byte code path, per-tensor scales, a whole model's
+forward, more than one run.
+
 `byte_codes=True` (pack_model, PackedBank; off by default -- without it everything above is unchanged): a layer the 4-bit codec
 refuses for its codebook (the 5- to 8-bit layers of `set_8_bit_layer_n/_l`, OliVe's unsigned 16 + 15 values) or for its row
 length (4 mod 8, such as 20) and that the byte codec accepts -- at most 256 values, with OliVe at most 255 normal and 255 outlier
@@ -137,12 +156,14 @@ def _settle(q):
 
 class PackedBank:
     def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True, fused_rows=None,
-                 byte_codes=False, fused_bytes=False, fused_byte_rows=None):
+                 byte_codes=False, fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None):
         """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict);
         a layer's code width is then the one its stored size says (numel / 2 bytes: 4-bit, numel bytes: byte codes).
         byte_codes: layers the 4-bit codec refuses and the byte codec accepts are packed one code per byte (width 8).
         fused_bytes (with fused_linear): byte-coded Linear layers of K % 8 == 0 compute from their codes too (antq_linear8).
-        fused_byte_rows=R (with fused_linear and fused_bytes): their bf16 / f16 calls of 9 .. R rows too (antq_linear8_mm)."""
+        fused_byte_rows=R (with fused_linear and fused_bytes): their bf16 / f16 calls of 9 .. R rows too (antq_linear8_mm).
+        fused_gemm_rows=R (with fused_linear): bf16 / f16 calls of the 4-bit layers with more rows than the other kernels take
+        and at most R rows run antq_linear4_gemm."""
         self.byte_codes = bool(byte_codes)
         if fused_bytes and not fused_linear:
             raise _lib.AntqError("PackedBank: fused_bytes needs fused_linear=True")
@@ -156,6 +177,9 @@ class PackedBank:
         _check_fused_rows("PackedBank", fused_linear, fused_rows)
         self.fused_rows = None if fused_rows is None else int(fused_rows)   # bf16 / f16 calls of 9 .. fused_rows rows: antq_linear4_mm
         self.fused_mm_calls = 0    # forwards antq_linear4_mm served
+        _check_fused_gemm_rows("PackedBank", fused_linear, fused_gemm_rows)
+        self.fused_gemm_rows = None if fused_gemm_rows is None else int(fused_gemm_rows)   # bf16 / f16 calls of more rows, up to this many: antq_linear4_gemm
+        self.fused_gemm_calls = 0  # forwards antq_linear4_gemm served
         self.model = model
         self.release_weights = bool(release_weights)
         self.fused_linear = bool(fused_linear)   # Linear layers with few input rows compute from the codes (antq_linear4)
@@ -401,8 +425,12 @@ class PackedBank:
         byte = e["width"] == 8                     # (fused_rows is antq_linear4_mm's, fused_byte_rows antq_linear8_mm's)
         max_rows = _lib.LINEAR8_MAX_M if byte else _lib.LINEAR4_MAX_M
         more_rows = self.fused_byte_rows if byte else self.fused_rows
-        if more_rows is not None and e["dtype"] in (torch.bfloat16, torch.float16):
-            max_rows = more_rows
+        gemm_rows = None if byte else self.fused_gemm_rows     # (the tiled kernel takes 4-bit codes only)
+        if e["dtype"] in (torch.bfloat16, torch.float16):
+            if more_rows is not None:
+                max_rows = more_rows
+            if gemm_rows is not None:
+                max_rows = gemm_rows               # (> LINEAR4_MM_MAX_M >= fused_rows)
         if (input.is_cuda and input.dtype == e["dtype"] and input.device == e["device"] and input.dim() >= 1 and input.shape[-1] == K
                 and 0 < input.numel() <= max_rows * K and input.is_contiguous() and input.data_ptr() % 16 == 0
                 and not (byte and e["codes"].data_ptr() % 8)
@@ -418,9 +446,12 @@ class PackedBank:
             elif input.numel() <= _lib.LINEAR4_MAX_M * K:
                 self.fused_calls += 1
                 fn = _lib.linear4
-            else:
+            elif self.fused_rows is not None and input.numel() <= self.fused_rows * K:
                 self.fused_mm_calls += 1
                 fn = _lib.linear4_mm
+            else:                                  # more rows than the other kernels take, at most fused_gemm_rows
+                self.fused_gemm_calls += 1
+                fn = _lib.linear4_gemm
             return fn(e["codes"], input, e["alpha"], plan.grid_dev(e["device"]), gmax, e["shape"][0], K, e["per_row"],
                       bias=None if bias is None else bias.detach(), n_normal=n_normal, ovp=ovp)
         return F.linear(input, weight if e["out"] is not None else self._image(e), bias)
@@ -446,6 +477,11 @@ def _check_fused_byte_rows(who, fused_linear, fused_bytes, fused_byte_rows):
                        _lib.LINEAR8_MAX_M, _lib.LINEAR8_MM_MAX_M)
 
 
+def _check_fused_gemm_rows(who, fused_linear, fused_gemm_rows):
+    _check_rows_option(who, "fused_gemm_rows", fused_gemm_rows, (("fused_linear", fused_linear),), _lib.LINEAR4_MM_MAX_M,
+                       _lib.LINEAR4_GEMM_MAX_M)
+
+
 def _no_auto_bank(model):
     """The automatic weight bank steps aside (as for set_weights_at_rest(resident=False)), and the choice stays with the
     module: a deep copy carries the mark, so its forward hook does not arm a fresh AutoBank for it."""
@@ -463,7 +499,7 @@ def _bank_of(model):
 
 
 def pack_model(model, release_weights=False, fused_linear=False, keep_images=True, fused_rows=None, byte_codes=False,
-               fused_bytes=False, fused_byte_rows=None):
+               fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
     (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
     byte_codes: layers the 4-bit codec refuses for their codebook (5- to 8-bit layers, OliVe's unsigned 16 + 15) or their row
@@ -492,9 +528,17 @@ def pack_model(model, release_weights=False, fused_linear=False, keep_images=Tru
     re-read from L2 by every workgroup) and with fewer, larger workgroups, and did not change with a deeper load ring: it
     appears bound by the x stream from L2 at M >= 32 and by parallelism and the table look-ups below -- inferred from the
     scaling, no hardware counters were collected.  Not measured: other M, the 4-byte code path, per-tensor scales, a whole
-    model, more than one run per point.  The 16-bit MFMA keeps subnormal operands (measured): W is the image there too."""
+    model, more than one run per point.  The 16-bit MFMA keeps subnormal operands (measured): W is the image there too.
+    fused_gemm_rows=R (with fused_linear, 64 < R <= 4096): bf16 / f16 calls of the 4-bit layers with more rows than the other
+    kernels take (more than 8, or more than fused_rows) and at most R rows compute from the codes as a tiled matrix-core product
+    (antq_linear4_gemm, .fused_gemm_calls) and, with keep_images=False, decode nothing and leave the scratch alone.
+    Measured (profiles/packed_linear4_gemm.md, one MI355X, one run; A = F.linear on the image, C = antq_decode4 into
+    scratch + F.linear, B = antq_linear4_gemm; M = 64 ... 4096, five layer shapes, bf16 / f16, ANT and OliVe): B loses to
+    C and to A at all 120 points (C / B 0.20 ... 0.92, best on [16384, 4096] at M = 128 / 256), so no R is worth choosing
+    for speed; the option buys the memory and the free scratch.  Give fused_rows=64 beside it (at M = 64 B takes 2.9 ...
+    4.7 times antq_linear4_mm's time).  Not measured: other M, the 4-byte code path, per-tensor scales, a whole model."""
     return PackedBank(model, release_weights=release_weights, fused_linear=fused_linear, keep_images=keep_images, fused_rows=fused_rows,
-                      byte_codes=byte_codes, fused_bytes=fused_bytes, fused_byte_rows=fused_byte_rows)
+                      byte_codes=byte_codes, fused_bytes=fused_bytes, fused_byte_rows=fused_byte_rows, fused_gemm_rows=fused_gemm_rows)
 
 
 def packed_state_dict(model):
@@ -516,18 +560,19 @@ def _packed_keys(sd, codes):
 
 
 def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, keep_images=True, fused_rows=None,
-                           fused_bytes=False, fused_byte_rows=None):
+                           fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None):
     """Load a packed checkpoint into a freshly wrapped, uncalibrated model living on the GPU: the quantiser state is
     installed the way load_ant_state_dict + load_state_dict do (scales keep the dtype they were stored with), a PackedBank is attached from the stored codes without
     re-encoding (a layer's code width is the one its stored size says: numel / 2 bytes are 4-bit codes, numel bytes byte codes;
     any other size raises AntqError naming the layer), and the weights are materialised by the batched decode
-    (release_weights=False: copied into the layers' own float weights instead of replacing them).  fused_linear / keep_images / fused_rows / fused_bytes / fused_byte_rows: as in pack_model (the code width still comes from the stored size).  Returns the bank."""
+    (release_weights=False: copied into the layers' own float weights instead of replacing them).  fused_linear / keep_images / fused_rows / fused_bytes / fused_byte_rows / fused_gemm_rows: as in pack_model (the code width still comes from the stored size).  Returns the bank."""
     if not keep_images and not fused_linear:
         raise _lib.AntqError("load_packed_state_dict: keep_images=False needs fused_linear=True")
     _check_fused_rows("load_packed_state_dict", fused_linear, fused_rows)
     if fused_bytes and not fused_linear:
         raise _lib.AntqError("load_packed_state_dict: fused_bytes needs fused_linear=True")
     _check_fused_byte_rows("load_packed_state_dict", fused_linear, fused_bytes, fused_byte_rows)
+    _check_fused_gemm_rows("load_packed_state_dict", fused_linear, fused_gemm_rows)
     suffix = "." + CODES_KEY
     codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}
     rest = {k: v for k, v in sd.items() if not k.endswith(suffix)}
@@ -546,7 +591,7 @@ def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, 
     for _, _, q, _ in _weight_layers(model):
         _settle(q)
     bank = PackedBank(model, release_weights=release_weights, codes=codes, fused_linear=fused_linear, keep_images=keep_images,
-                      fused_rows=fused_rows, fused_bytes=fused_bytes, fused_byte_rows=fused_byte_rows)
+                      fused_rows=fused_rows, fused_bytes=fused_bytes, fused_byte_rows=fused_byte_rows, fused_gemm_rows=fused_gemm_rows)
     if not release_weights:
         with torch.no_grad():
             for e in bank.entries.values():

@@ -46,7 +46,7 @@ extern "C" {
  * that existed changed, so callers built against 7 keep working).  antq_linear4 (the packed 4-bit linear) added likewise,
  * and antq_linear4_mm (its matrix-core form for up to 64 rows), and antq_encode8 / antq_decode8 / antq_decode8_batch_capacity /
  * antq_decode8_batch_build / antq_decode8_batch (the byte-code codec), and antq_linear8 (the linear from byte codes), and
- * antq_linear8_mm (its matrix-core form for up to 64 rows).
+ * antq_linear8_mm (its matrix-core form for up to 64 rows), and antq_linear4_gemm (the tiled 4-bit form for up to 4096 rows).
  * A caller built against another version must not call in: the blobs / argument lists differ. */
 #define ANTQ_ABI_VERSION 7
 
@@ -580,6 +580,37 @@ int antq_linear4_mm(const uint8_t *codes_dev, const void *x_dev, const void *bia
                     unsigned flags /* 0 | ANTQ_FLAG_OVP */, int dtype /* BF16 | F16 */, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * The same product for 1 .. ANTQ_LINEAR4_GEMM_MAX_M rows of x as a tiled matrix-core product, BF16 and F16 only: every workgroup
+ * takes one (128 or 256 rows of x, 64 output rows) tile, x is staged through LDS, K is not split.  Parameters as antq_linear4.
+ *   W[n,k] is, bit for bit, the element antq_decode4 writes in `dtype` (the decoder's byte table is the MFMA operand; no
+ *          widening, the scale is never factored out of the sum).
+ *   y[m,n] = round_dtype( sum_k x[m,k] * W[n,k] + bias[n] ): ONE fp32 MFMA accumulator chain over K in steps of 128 elements in
+ *          rising order, the bias added in fp32, one rounding to `dtype`.  K is split neither across wavefronts nor across
+ *          workgroups.
+ *   The bits of y[m,n] depend only on row m of x, row n of W, bias[n], K and the code path (below): not on M, not on N, not on
+ *          the other rows of x, not on the tile shape, not on the run.  The order of the sum is this kernel's own -- NOT
+ *          antq_linear4's and NOT antq_linear4_mm's: the same row has different low bits from the three entry points (each
+ *          within the bound of an fp32 sum).
+ *   No floating-point atomics, no workspace, no allocation, no synchronisation: stream-ordered and capturable into a graph.
+ *          Rows m >= M, n >= N and k >= K of the last step clamp their addresses into the buffers, contribute exactly +0 and
+ *          are not stored: no read or write falls outside codes, x, bias, alpha / grid and y.
+ * Checked before anything touches HIP, in this order:
+ *   ANTQ_ERR_ARG          as antq_linear4
+ *   ANTQ_OK, no launch    M == 0 or N == 0
+ *   ANTQ_ERR_UNSUPPORTED  dtype == ANTQ_F32; M > ANTQ_LINEAR4_GEMM_MAX_M; K == 0 or K % 8 != 0; the decoder's refusals;
+ *                         N >= 2^31 or K >= 2^31
+ *   ANTQ_ERR_ALIGN        as antq_linear4
+ * Codes are read 16 bytes per lane when K % 32 == 0 and codes_dev is 16-byte aligned, 4 bytes per lane otherwise (the order
+ * of the sum differs between the two, nothing else).  Measurements: profiles/packed_linear4_gemm.md.
+ * ------------------------------------------------------------------------- */
+#define ANTQ_LINEAR4_GEMM_MAX_M 4096
+int antq_linear4_gemm(const uint8_t *codes_dev, const void *x_dev, const void *bias_dev, void *y_dev,
+                      size_t M, size_t N, size_t K,
+                      const float *alpha_dev, int alpha_per_row, float gmax,
+                      const float *grid_dev, int m, int n_normal,
+                      unsigned flags /* 0 | ANTQ_FLAG_OVP */, int dtype /* BF16 | F16 */, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Packed byte-code linear: antq_linear4 for the byte codes of W -- y = x . W^T (+ bias) for 1 .. ANTQ_LINEAR8_MAX_M rows of x,
  * computed straight from the codes (half the bytes of the bf16 image, a quarter of the fp32 image).  codes: N rows of K
  * bytes in antq_encode8's layout; alpha / gmax / grid / m / n_normal as in antq_decode_job, alpha_per_row: one scale per
@@ -695,7 +726,9 @@ int antq_copy(const void *src_dev, void *dst_dev, size_t bytes, void *stream);
  *           tensors with one scale from 1 M elements): 0 off, 1 (default), 2 every eligible launch (rows from 128 elements
  *           with or without the pair rule, one-scale fp32 tensors from 4096)
  *   key 21: 0 sends rows of <= 1024 elements through the 4096-key kernel instead of one row per wavefront (A/B)
- *   key 22: antq_linear4_mm / antq_linear8_mm: tiles of 16 output rows per workgroup, 1 / 2 / 4 (A/B; 0 = the launcher's rule; no result changes) */
+ *   key 22: antq_linear4_mm / antq_linear8_mm: tiles of 16 output rows per workgroup, 1 / 2 / 4 (A/B; 0 = the launcher's rule; no result changes)
+ *   key 23: antq_linear4_gemm: wavefronts per workgroup, 2 / 4, i.e. tiles of 128 / 256 rows of x (A/B; 0 = the launcher's rule:
+ *           2 while the tiles of 128 rows number at most 256; no result changes) */
 int antq_debug_set(int key, int value);
 
 /* Load the library's GPU code objects for the current device now (HIP would load each of them at the first launch of one
