@@ -445,6 +445,30 @@ __device__ __forceinline__ void store_idx(int16_t *idx, size_t vec, const int (&
     }
 }
 
+// ------------------------------------------------------------------------------------
+// Packed 4-bit codes, read: what every decoder of them shares (antq_decode4, the batched decoder, the packed linears).
+// ------------------------------------------------------------------------------------
+// The codebook goes to LDS first, read with + 0.0f (a codebook's -0 decodes to +0, which is what the reference's
+// (q - d) + d makes of it for every finite d); thread t writes entry t, and the caller orders the writes before the first read.
+__device__ __forceinline__ void dec4_book(float (&g)[32], uint32_t t, const float *grid, uint32_t m)
+{
+    if (t < 32u) g[t] = (t < m) ? ld_global(grid + t) + 0.0f : 0.0f;
+}
+// the decoded pair of one code byte, before scaling
+template <bool OVP>
+__device__ __forceinline__ void dec_pair(uint32_t byte, const float *g, int n_normal, float &q0, float &q1)
+{
+    const uint32_t c0 = byte & 15u, c1 = (byte >> 4) & 15u;
+    if (OVP) {
+        // identifier 15 in one nibble: that element is the victim (0), its partner an outlier
+        q0 = (c0 == 15u) ? 0.0f : ((c1 == 15u) ? g[n_normal + c0] : g[c0]);
+        q1 = (c1 == 15u) ? 0.0f : ((c0 == 15u) ? g[n_normal + c1] : g[c1]);
+    } else {
+        q0 = g[c0];
+        q1 = g[c1];
+    }
+}
+
 }  // namespace antq
 
 #endif  // ANTQ_DEVICE_H

@@ -1,39 +1,49 @@
-// antq_k_codec.h -- packed 4-bit codec kernels and their launcher
+// antq_k_codec.h -- packed codec kernels: the element encoder of both code widths (k_encode over a code-width trait:
+// Code4 here, Code8 in antq_k_codec8.h), the 4-bit row encoders, the 4-bit decoder and the 4-bit launchers
 // Part of libantq's single device translation unit (antq_kernels.hip includes it); gfx950 only.
 #ifndef ANTQ_K_CODEC_H
 #define ANTQ_K_CODEC_H
 
 #include "antq_decbatch.h"
 #include "antq_device.h"
+#include "antq_dispatch.h"
 #include "antq_k_approx.h"
 #include "antq_k_hrow.h"
 
 namespace antq {
 
 // The encoder only needs codes: its LDS table is the plan's a-table with the two values of every entry replaced, once per
-// workgroup, by their nibbles (bit 8 = the pair rule's outlier test |v| > 32): {M' (double), code_lo, code_hi}.  One
+// workgroup, by their codes (bit 8 = the pair rule's outlier test |v| > 32): {M' (double), code_lo, code_hi}.  One
 // ds_read_b128, the exact decision (antq_k_approx.h) and one select per element; no second table read, no dequantised value.
 constexpr uint32_t kOutlierBit = 0x100u;
-template <bool OVP>
+template <bool OVP, uint32_t MASK = 15u>
 __device__ __forceinline__ uint32_t code_of(uint32_t j, float v, int n_normal)
 {
     uint32_t c = (OVP && (int)j >= n_normal) ? j - (uint32_t)n_normal : j;
-    c &= 15u;
+    c &= MASK;
     if (OVP && fabsf(v) > 32.0f) c |= kOutlierBit;                // OQ:314
     return c;
 }
-template <bool OVP>
+template <bool OVP, uint32_t MASK>
 __device__ __forceinline__ void atab_to_codes(const PlanArgs &pa, uint4 *smem, const ATab &A, int n_normal)
 {
     for (uint32_t i = threadIdx.x; i < pa.atab_slots; i += blockDim.x) {
         uint4 e = smem[i];
         const uint32_t w = A.idx[i];
-        e.z = code_of<OVP>(w & kIdxMask, u2f(e.z), n_normal);
-        e.w = code_of<OVP>((w >> 16) & kIdxMask, u2f(e.w), n_normal);
+        e.z = code_of<OVP, MASK>(w & kIdxMask, u2f(e.z), n_normal);
+        e.w = code_of<OVP, MASK>((w >> 16) & kIdxMask, u2f(e.w), n_normal);
         smem[i] = e;
     }
 }
-// 8 codes (4 pairs) -> one word of nibbles; OVP: the pair rule on the outlier bits first (OQ:313-320)
+// the pair rule on the outlier bits of one pair (OQ:313-320): the identifier marks the victim
+__device__ __forceinline__ void pair_rule(uint32_t &c0, uint32_t &c1, uint32_t ident)
+{
+    const bool me = c0 >= kOutlierBit, mo = c1 >= kOutlierBit;
+    const bool ve = mo && !me;
+    c0 = ve ? ident : c0;
+    c1 = me ? ident : c1;
+}
+// 8 codes (4 pairs) -> one word of nibbles; OVP: the pair rule first
 template <bool OVP>
 __device__ __forceinline__ uint32_t pack_codes(uint32_t (&c)[8])
 {
@@ -41,12 +51,7 @@ __device__ __forceinline__ uint32_t pack_codes(uint32_t (&c)[8])
 #pragma unroll
     for (int p = 0; p < 4; p++) {
         uint32_t c0 = c[2 * p], c1 = c[2 * p + 1];
-        if (OVP) {
-            const bool me = c0 >= kOutlierBit, mo = c1 >= kOutlierBit;
-            const bool ve = mo && !me;
-            c0 = ve ? 15u : c0;                                  // the identifier 1111 marks the victim
-            c1 = me ? 15u : c1;
-        }
+        if (OVP) pair_rule(c0, c1, 15u);
         pr[p] = (c1 << 4) | c0;                                  // byte 0 = the pair; the outlier bits land in byte 1
     }
     if (OVP) {
@@ -56,69 +61,92 @@ __device__ __forceinline__ uint32_t pack_codes(uint32_t (&c)[8])
     }
     return pr[0] | (pr[1] << 8) | (pr[2] << 16) | (pr[3] << 24);
 }
-// 8 consecutive elements of one row (the first at an index that is a multiple of 8) -> 8 nibbles
-template <bool OVP>
-__device__ __forceinline__ uint32_t encode_oct_a(const PlanArgs &pa, const uint4 *etab, const float *grid, const ScaleA &sc,
-                                                 const float (&x)[8], int n_normal, int zero_code)
+
+// What differs between the code widths of the element encoder (k_encode): bits per code, the pair rule's identifier, the
+// units a row may be cut into, the book a code holds, how the E codes of a unit become E * BITS / 32 words (OVP: the pair
+// rule on the outlier bits first) and how those words are stored.
+struct Code4 {
+    static constexpr int BITS = 4;
+    static constexpr uint32_t IDENT = 15u;
+    typedef uint32_t Store;                            // the codes are 4-byte aligned (antq_encode4): an octet is one word
+    static constexpr bool unit_ok(int E) { return E == 8; }
+    static bool book_ok(int m, int n_normal, bool ovp) { return dec4_book_ok(m, n_normal, ovp); }
+    template <bool OVP>
+    __device__ __forceinline__ static void pack(uint32_t (&c)[8], uint32_t (&w)[1]) { w[0] = pack_codes<OVP>(c); }
+    __device__ __forceinline__ static void store(uint32_t *codes, size_t o, const uint32_t (&w)[1], int) { codes[o] = w[0]; }
+};
+
+// E consecutive elements of one row (the first at an index that is a multiple of E) -> their codes, packed
+template <typename W, bool OVP, int E>
+__device__ __forceinline__ void encode_unit_a(const PlanArgs &pa, const uint4 *etab, const float *grid, const ScaleA &sc,
+                                              const float (&x)[E], int n_normal, int zero_code, uint32_t (&w)[E * W::BITS / 32])
 {
-    float dt[8];
-    uint32_t c[8];
+    constexpr uint32_t MASK = (1u << W::BITS) - 1u;
+    float dt[E];
+    uint32_t c[E];
     const float flim = pa.fastlim * 0.99999f;
 #pragma unroll
-    for (int e = 0; e < 8; e++) dt[e] = x[e] * sc.rs;
+    for (int e = 0; e < E; e++) dt[e] = x[e] * sc.rs;
     bool nan;
-    const float dmax = absmax_nan<8>(dt, nan);
+    const float dmax = absmax_nan<E>(dt, nan);
     if (sc.ok && !nan && dmax < flim) {                 // false for NaN / Inf / beyond the table's domain
-        uint32_t slot[8];
-        a_slots<8>(pa, dt, slot);
+        uint32_t slot[E];
+        a_slots<E>(pa, dt, slot);
         const AEnt *tab0 = reinterpret_cast<const AEnt *>(pa.linear ? etab : etab - 2u * pa.kmin);
-        AEnt ents[8];
+        AEnt ents[E];
 #pragma unroll
-        for (int e = 0; e < 8; e++) ents[e] = tab0[slot[e]];      // all reads in flight before the first use
+        for (int e = 0; e < E; e++) ents[e] = tab0[slot[e]];      // all reads in flight before the first use
 #pragma unroll
-        for (int e = 0; e < 8; e++) {
+        for (int e = 0; e < E; e++) {
             AEnt ent = ents[e];
             ent.pin();
             c[e] = (__builtin_fma(-ent.Mp(), sc.sd, (double)x[e]) >= 0.0) ? ent.hi() : ent.lo();
         }
     } else {
-        // the literal sequence (true division, scan) for this lane's octet
+        // the literal sequence (true division, scan) for this lane's unit
 #pragma unroll
-        for (int e = 0; e < 8; e++) {
+        for (int e = 0; e < E; e++) {
             int jj;
             const float q = scan_lds(x[e] / sc.s, grid, (int)pa.m, jj);
-            c[e] = jj == ANTQ_IDX_NONE ? (uint32_t)zero_code : code_of<OVP>((uint32_t)jj, q, n_normal);
+            c[e] = jj == ANTQ_IDX_NONE ? (uint32_t)zero_code : code_of<OVP, MASK>((uint32_t)jj, q, n_normal);
         }
     }
-    return pack_codes<OVP>(c);
+    W::template pack<OVP>(c, w);
 }
 
-// One lane: 8 consecutive elements (4 pairs) of one row -> 4 bytes of codes; VEC: the octet is one (bf16 / f16) or two
-// (fp32) 16-byte loads, U octets in flight per thread.
-template <typename T> struct Oct {                     // 8 elements <- 16-byte vectors
-    __device__ __forceinline__ static void load(const void *p, size_t o, float (&f)[8])
-    {
-        IO<T>::unpack(ld_stream(static_cast<const uint4 *>(p) + o), f);
-    }
-};
-template <> struct Oct<float> {
-    __device__ __forceinline__ static void load(const void *p, size_t o, float (&f)[8])
-    {
-        const uint4 *v = static_cast<const uint4 *>(p) + 2 * o;
+// The E elements of unit o <- two (fp32, E = 8), one (16-bit, E = 8; fp32, E = 4) or half a (16-bit, E = 4) 16-byte vector
+template <typename T, int E>
+__device__ __forceinline__ void unit_load(const void *x, size_t o, float (&f)[E])
+{
+    if constexpr (E == 2 * IO<T>::EPL) {
+        const uint4 *v = static_cast<const uint4 *>(x) + 2 * o;
         const uint4 a = ld_stream(v), b = ld_stream(v + 1);
         f[0] = u2f(a.x); f[1] = u2f(a.y); f[2] = u2f(a.z); f[3] = u2f(a.w);
         f[4] = u2f(b.x); f[5] = u2f(b.y); f[6] = u2f(b.z); f[7] = u2f(b.w);
+    } else if constexpr (E == IO<T>::EPL) IO<T>::unpack(ld_stream(static_cast<const uint4 *>(x) + o), f);
+    else {
+        typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+        const u32x2_t h = __builtin_nontemporal_load(((const ANTQ_GLOBAL u32x2_t *)(x)) + o);
+        float f8[8];
+        IO<T>::unpack(make_uint4(h.x, h.y, 0u, 0u), f8);
+#pragma unroll
+        for (int e = 0; e < 4; e++) f[e] = f8[e];
     }
-};
+}
 
-// Persistent workgroups (the plan's table is staged once), each looping over tasks of 256 * U octets.
-template <typename T, bool OVP, bool VEC, int UE>
+// The element encoder of both code widths.  Persistent workgroups (the plan's table is staged once), each looping over
+// tasks of 256 * U units of E elements; VEC: a unit is loaded as 16-byte vectors (unit_load), kEncU units in flight per
+// thread.  `words` is W::store's: the byte codes' choice between word and byte stores.
+constexpr int kEncU = 2;
+template <typename W, typename T, bool OVP, bool VEC, int E>
 __global__ void __launch_bounds__(256)
-k_encode4(const void *__restrict__ x, uint32_t *__restrict__ codes, size_t n_oct, size_t row_len, size_t n_tasks,
-          const float *__restrict__ alpha, int per_row, float gmax, int n_normal, int zero_code,
-          PlanArgs pa, const uint4 *__restrict__ plan_tab)
+k_encode(const void *__restrict__ x, typename W::Store *__restrict__ codes, size_t n_units, size_t row_len, size_t n_tasks,
+         const float *__restrict__ alpha, int per_row, float gmax, int n_normal, int zero_code,
+         PlanArgs pa, const uint4 *__restrict__ plan_tab, int words)
 {
-    constexpr int U = VEC ? UE : 1;
+    static_assert(W::unit_ok(E), "no such unit for this code width");
+    constexpr int U = VEC ? kEncU : 1;
+    constexpr uint32_t MASK = (1u << W::BITS) - 1u;
     extern __shared__ __attribute__((aligned(16))) uint4 smem[];
     uint4 tab0 = make_uint4(0, 0, 0, 0);
     if (pa.adom) tab0 = atab_prefetch<true>(pa, plan_tab);         // exact decision on x (antq_k_approx.h), with indices
@@ -128,58 +156,59 @@ k_encode4(const void *__restrict__ x, uint32_t *__restrict__ codes, size_t n_oct
     if (pa.adom) {
         A = stage_atab<true>(pa, plan_tab, smem, tab0);
         __syncthreads();
-        atab_to_codes<OVP>(pa, smem, A, n_normal);
+        atab_to_codes<OVP, MASK>(pa, smem, A, n_normal);
     } else L = stage_plan(pa, plan_tab, smem, tab0);
     __syncthreads();
-    const size_t opr = row_len / 8;                    // row_len % 8 == 0: an octet (4 pairs) lies inside one row -> one scale
-    const bool small = n_oct <= 0xffffffffull && opr <= 0xffffffffull;
-    const bool pow2 = (opr & (opr - 1)) == 0;          // the usual case: the row index is a shift
-    const int rsh = pow2 ? __builtin_ctzll(opr | (1ull << 63)) : 0;
-    const double inv = 1.0 / (double)opr;
+    const size_t upr = row_len / E;                    // row_len % E == 0: a unit (E / 2 pairs) lies inside one row -> one scale
+    const bool small = n_units <= 0xffffffffull && upr <= 0xffffffffull;
+    const bool pow2 = (upr & (upr - 1)) == 0;          // the usual case: the row index is a shift
+    const int rsh = pow2 ? __builtin_ctzll(upr | (1ull << 63)) : 0;
+    const double inv = 1.0 / (double)upr;
     const float a0 = per_row ? 1.0f : alpha[0];
     const double inv_gmax = 1.0 / (double)gmax;
     for (size_t task = blockIdx.x; task < n_tasks; task += gridDim.x) {
-        const size_t first = (task * U) * 256u + threadIdx.x;   // octet index: elements [8o, 8o+8)
-        float xf[U][8], a[U];
+        const size_t first = (task * U) * 256u + threadIdx.x;   // unit index: elements [E o, E o + E)
+        float xf[U][E], a[U];
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const size_t o = first + (size_t)u * 256u;
             a[u] = a0;
 #pragma unroll
-            for (int e = 0; e < 8; e++) xf[u][e] = 0.0f;
-            if (o < n_oct) {
-                if (per_row) a[u] = alpha[pow2 ? (o >> rsh) : small ? (size_t)oct_row((uint32_t)o, (uint32_t)opr, inv) : o / opr];
-                if constexpr (VEC) Oct<T>::load(x, o, xf[u]);
+            for (int e = 0; e < E; e++) xf[u][e] = 0.0f;
+            if (o < n_units) {
+                if (per_row) a[u] = alpha[pow2 ? (o >> rsh) : small ? (size_t)oct_row((uint32_t)o, (uint32_t)upr, inv) : o / upr];
+                if constexpr (VEC) unit_load<T, E>(x, o, xf[u]);
                 else {
 #pragma unroll
-                    for (int e = 0; e < 8; e++) xf[u][e] = IO<T>::load1(x, o * 8 + e);
+                    for (int e = 0; e < E; e++) xf[u][e] = IO<T>::load1(x, o * E + e);
                 }
             }
         }
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const size_t o = first + (size_t)u * 256u;
-            if (o >= n_oct) continue;
-            if (pa.adom) {
-                codes[o] = encode_oct_a<OVP>(pa, A.tab, A.grid, make_scale_a(a[u], gmax, inv_gmax), xf[u], n_normal, zero_code);
-                continue;
-            }
-            float of[8];
-            int j[8];
-            const Scale sc = make_scale(a[u], gmax);
-            quant_vec<8, OVP, true>(pa, L, sc, xf[u], of, j);
-            uint32_t word = 0;
+            if (o >= n_units) continue;
+            uint32_t w[E * W::BITS / 32];
+            if (pa.adom) encode_unit_a<W, OVP, E>(pa, A.tab, A.grid, make_scale_a(a[u], gmax, inv_gmax), xf[u], n_normal, zero_code, w);
+            else {
+                float of[E];
+                int j[E];
+                const Scale sc = make_scale(a[u], gmax);
+                quant_vec<E, OVP, true>(pa, L, sc, xf[u], of, j);
 #pragma unroll
-            for (int e = 0; e < 8; e++) {
-                const int jj = j[e];
-                uint32_t c;
-                if (jj == ANTQ_IDX_VICTIM) c = 15u;
-                else if (jj == ANTQ_IDX_NONE) c = (uint32_t)zero_code;
-                else if (OVP && jj >= n_normal) c = (uint32_t)(jj - n_normal);
-                else c = (uint32_t)jj;
-                word |= (c & 15u) << (4 * e);
+                for (int q = 0; q < E * W::BITS / 32; q++) w[q] = 0u;
+#pragma unroll
+                for (int e = 0; e < E; e++) {
+                    const int jj = j[e];
+                    uint32_t c;
+                    if (jj == ANTQ_IDX_VICTIM) c = W::IDENT;
+                    else if (jj == ANTQ_IDX_NONE) c = (uint32_t)zero_code;
+                    else if (OVP && jj >= n_normal) c = (uint32_t)(jj - n_normal);
+                    else c = (uint32_t)jj;
+                    w[e * W::BITS / 32] |= (c & MASK) << (e * W::BITS % 32);
+                }
             }
-            codes[o] = word;
+            W::store(codes, o, w, words);
         }
     }
 }
@@ -211,12 +240,7 @@ __device__ __forceinline__ uint32_t pack_codes4(uint32_t (&c)[4])          // 4 
 #pragma unroll
     for (int p = 0; p < 2; p++) {
         uint32_t c0 = c[2 * p], c1 = c[2 * p + 1];
-        if (OVP) {
-            const bool me = c0 >= kOutlierBit, mo = c1 >= kOutlierBit;
-            const bool ve = mo && !me;
-            c0 = ve ? 15u : c0;
-            c1 = me ? 15u : c1;
-        }
+        if (OVP) pair_rule(c0, c1, 15u);
         pr[p] = ((c1 & 15u) << 4) | (c0 & 15u);
     }
     return pr[0] | (pr[1] << 8);
@@ -551,7 +575,7 @@ k_decode4(const uint32_t *__restrict__ codes, void *__restrict__ out, size_t n_o
     constexpr int EPL = VEC ? IO<T>::EPL : 8;          // elements per thread and access
     constexpr int U = VEC ? 4 : 1;
     __shared__ float g[32];
-    // (+ 0.0f: a codebook's -0 decodes to +0, which is what the reference's (q - d) + d makes of it for every finite d)
+    // (dec4_book's load, spelled with this kernel's signed m: sharing it changes the plain-book variants' code)
     if (threadIdx.x < 32) g[threadIdx.x] = ((int)threadIdx.x < m) ? grid[threadIdx.x] + 0.0f : 0.0f;
     const size_t n_units = n_oct * (8 / EPL);
     const size_t first = ((size_t)blockIdx.x * U) * 256u + threadIdx.x;
@@ -576,16 +600,8 @@ k_decode4(const uint32_t *__restrict__ codes, void *__restrict__ out, size_t n_o
         float of[EPL];
 #pragma unroll
         for (int p = 0; p < EPL / 2; p++) {
-            const uint32_t c0 = (word[u] >> (8 * p)) & 15u, c1 = (word[u] >> (8 * p + 4)) & 15u;
             float q0, q1;
-            if (OVP) {
-                // identifier 15 in one nibble: that element is the victim (0), its partner an outlier
-                q0 = (c0 == 15u) ? 0.0f : ((c1 == 15u) ? g[n_normal + c0] : g[c0]);
-                q1 = (c1 == 15u) ? 0.0f : ((c0 == 15u) ? g[n_normal + c1] : g[c1]);
-            } else {
-                q0 = g[c0];
-                q1 = g[c1];
-            }
+            dec_pair<OVP>(word[u] >> (8 * p), g, n_normal, q0, q1);
             of[2 * p] = q0 * s;
             of[2 * p + 1] = q1 * s;
         }
@@ -597,33 +613,72 @@ k_decode4(const uint32_t *__restrict__ codes, void *__restrict__ out, size_t n_o
     }
 }
 
-template <typename T>
-static int launch_codec(bool enc, const void *x, void *codes_or_out, const uint8_t *codes_in, size_t rows, size_t row_len,
-                        const float *alpha, int per_row, float gmax, const PlanArgs &pa, const void *plan_host,
-                        const void *plan_dev, int n_normal, bool ovp, hipStream_t st)
+// ------------------------------------------------------------------------------------
+// Launchers.  What the three of them (launch_encode4, launch_decode4; antq_k_codec8.h: launch_encode8) share comes first.
+// ------------------------------------------------------------------------------------
+// the first refusals of a launcher of code width W: a row that is not whole units, a book the code cannot hold
+template <typename W>
+static inline bool codec_refuses(size_t row_len, size_t min_unit, const PlanArgs &pa, int n_normal, bool ovp)
 {
-    const size_t n = rows * row_len;
-    if (row_len % 8 != 0) return ANTQ_ERR_UNSUPPORTED;
-    const int m = (int)pa.m;
-    if (!dec4_book_ok(m, n_normal, ovp)) return ANTQ_ERR_UNSUPPORTED;
-    const size_t n_oct = n / 8;
-    const bool vec = reinterpret_cast<uintptr_t>(enc ? x : codes_or_out) % 16 == 0;     // 16-byte vector I/O
-    constexpr int kEncU = 2;                           // octets per thread and task when encoding
-    const size_t per_block = vec ? (enc ? 256 * kEncU : 1024 * IO<T>::EPL / 8) : 256;     // octets per workgroup (task)
-    const size_t n_tasks = (n_oct + per_block - 1) / per_block;
-    size_t blocks = n_tasks;
-    if (enc && blocks > (size_t)g_knob_encwg) blocks = (size_t)g_knob_encwg;   // persistent workgroups
-    if (blocks > 0x7fffffffull) return ANTQ_ERR_UNSUPPORTED;
+    return row_len % min_unit != 0 || !W::book_ok((int)pa.m, n_normal, ovp);
+}
+// the code of an element with no grid value within reach: that of the grid's (last) zero
+static inline int codec_zero_code(const void *plan_host, const PlanArgs &pa, int n_normal, bool ovp)
+{
     const float *grid_host = plan_grid(plan_host);
     int zero_code = 0;
-    for (int i = 0; i < (ovp ? n_normal : m); i++) if (grid_host[i] == 0.0f) zero_code = i;
-    const dim3 gd((unsigned)blocks), bd(256);
+    for (int i = 0; i < (ovp ? n_normal : (int)pa.m); i++) if (grid_host[i] == 0.0f) zero_code = i;
+    return zero_code;
+}
+// n_units in tasks of per_block, and the workgroups that run them: one per task, or (the encoders: persistent workgroups,
+// the plan's table is staged once) at most knob 1.  False: more workgroups than a grid holds.
+static inline bool codec_tasks(size_t n_units, size_t per_block, bool persistent, size_t &n_tasks, dim3 &grid)
+{
+    n_tasks = (n_units + per_block - 1) / per_block;
+    size_t blocks = n_tasks;
+    if (persistent && blocks > (size_t)g_knob_encwg) blocks = (size_t)g_knob_encwg;
+    grid = dim3((unsigned)blocks);
+    return blocks <= 0x7fffffffull;
+}
+// the element encoder's launch (E is one of W's units)
+template <typename W, typename T>
+static int launch_encode_units(int E, const void *x, typename W::Store *codes, size_t n_units, size_t row_len, size_t n_tasks, dim3 grid,
+                               bool vec, const float *alpha, int per_row, float gmax, int n_normal, int zero_code, const PlanArgs &pa,
+                               const void *plan_dev, bool ovp, int words, hipStream_t st)
+{
+    const size_t lds = lds_table(pa, true);
+    return with_bool(ovp, [&](auto o) {
+        return with_bool(vec, [&](auto v) {
+            return with_value<8, 4>(E, [&](auto e) {
+                constexpr int E_ = decltype(e)::value;
+                if constexpr (!W::unit_ok(E_)) return (int)ANTQ_ERR_UNSUPPORTED;
+                else {
+                    launch_k(false, k_encode<W, T, decltype(o)::value, decltype(v)::value, E_>, grid, dim3(256), lds, st, x, codes, n_units,
+                             row_len, n_tasks, alpha, per_row, gmax, n_normal, zero_code, pa, plan_tab_ptr(plan_dev), words);
+                    return launch_status();
+                }
+            });
+        });
+    });
+}
+
+template <typename T>
+static int launch_encode4(const void *x, uint32_t *codes, size_t rows, size_t row_len, const float *alpha, int per_row, float gmax,
+                          const PlanArgs &pa, const void *plan_host, const void *plan_dev, int n_normal, bool ovp, hipStream_t st)
+{
+    if (codec_refuses<Code4>(row_len, 8, pa, n_normal, ovp)) return ANTQ_ERR_UNSUPPORTED;
+    const size_t n = rows * row_len, n_oct = n / 8;
+    const bool vec = reinterpret_cast<uintptr_t>(x) % 16 == 0;     // 16-byte vector I/O
+    size_t n_tasks;
+    dim3 gd;
+    if (!codec_tasks(n_oct, vec ? 256 * kEncU : 256, true, n_tasks, gd)) return ANTQ_ERR_UNSUPPORTED;
+    const int zero_code = codec_zero_code(plan_host, pa, n_normal, ovp);
     if constexpr (!std::is_same<T, float>::value) {
         // bf16 / f16 rows of >= 128 vectors with a 16-bit-domain plan: the K1h encoder (knob 9 = 0: the fp32-domain row encoder)
         HArgs ha;
         const size_t rl = per_row ? row_len : n;
         const size_t vpr = rl / 8;
-        if (enc && vec && g_knob_h != 0 && vpr >= kRowKernelMinVpr && vpr <= 0xffffffffull &&
+        if (vec && g_knob_h != 0 && vpr >= kRowKernelMinVpr && vpr <= 0xffffffffull &&
             hargs_from_plan(plan_host, IO<T>::DTYPE, gmax, ha)) {
             // vectors per lane and task: the largest of 8 / 4 / 3 / 2 that keeps the lanes of a row's tasks busy (the table is
             // built once per task); knob 0 forces a size (A/B)
@@ -640,28 +695,27 @@ static int launch_codec(bool enc, const void *x, void *codes_or_out, const uint8
                 const uint4 *tl = plan_tlist_dev(plan_host, plan_dev);
                 const float *grid = reinterpret_cast<const float *>(plan_tab_ptr(plan_dev));
                 const unsigned pad = g_knob_hlds >= 0 ? (unsigned)g_knob_hlds : 0u;
-#define ANTQ_ENCH(O, U_) hipLaunchKernelGGL((k_encode4_hrow<T, O, U_>), dim3((unsigned)total), dim3(64), pad, st, static_cast<const uint4 *>(x), \
-                                        static_cast<uint32_t *>(codes_or_out), (uint32_t)total, (uint32_t)vpr, (uint32_t)tpr, alpha, per_row, \
-                                        gmax, ha, tl, grid, n_normal, zero_code)
-#define ANTQ_ENCHM(O, U_, M_) hipLaunchKernelGGL((k_encode4_hrow<T, O, U_, M_>), dim3((unsigned)total), dim3(64), pad, st, static_cast<const uint4 *>(x), \
-                                        static_cast<uint32_t *>(codes_or_out), (uint32_t)total, (uint32_t)vpr, (uint32_t)tpr, alpha, per_row, \
-                                        gmax, ha, tl, grid, n_normal, zero_code)
-                // whole 8 KiB tasks store their 256-byte code words through the cache (plain stores: 71.1 -> 76.5 % ANT, 70.4 ->
-                // 75.4 % OliVe on 16384 x 8192 bf16; nontemporal loads stay -- plain loads cost 4 points); knob 13 = 1: nontemporal
-                // stores (A/B).  profiles/r05_codec_h.log
-                if (U == 8 && g_knob_exp != 1) { if (ovp) ANTQ_ENCHM(true, 8, 2); else ANTQ_ENCHM(false, 8, 2); }
-                else
-                if (U == 8) { if (ovp) ANTQ_ENCH(true, 8); else ANTQ_ENCH(false, 8); }
-                else if (U == 4) { if (ovp) ANTQ_ENCH(true, 4); else ANTQ_ENCH(false, 4); }
-                else if (U == 3) { if (ovp) ANTQ_ENCH(true, 3); else ANTQ_ENCH(false, 3); }
-                else { if (ovp) ANTQ_ENCH(true, 2); else ANTQ_ENCH(false, 2); }
-#undef ANTQ_ENCH
-#undef ANTQ_ENCHM
-                return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+                // whole 8 KiB tasks store their 256-byte code words through the cache (plain stores, MEM = 2: 71.1 -> 76.5 % ANT,
+                // 70.4 -> 75.4 % OliVe on 16384 x 8192 bf16; nontemporal loads stay -- plain loads cost 4 points); knob 13 = 1:
+                // nontemporal stores (A/B).  profiles/r05_codec_h.log
+                const int mem = (U == 8 && g_knob_exp != 1) ? 2 : 0;
+                return with_bool(ovp, [&](auto o) {
+                    return with_value<8, 4, 3, 2>(one_of<8, 4, 3>((int)U, 2), [&](auto u) {
+                        return with_value<0, 2>(mem, [&](auto mm) {
+                            constexpr int U_ = decltype(u)::value, MEM = decltype(mm)::value;
+                            if constexpr (MEM == 2 && U_ != 8) return (int)ANTQ_ERR_UNSUPPORTED;
+                            else {
+                                launch_k(false, k_encode4_hrow<T, decltype(o)::value, U_, MEM>, dim3((unsigned)total), dim3(64), pad, st, x,
+                                         codes, total, vpr, tpr, alpha, per_row, gmax, ha, tl, grid, n_normal, zero_code);
+                                return launch_status();
+                            }
+                        });
+                    });
+                });
             }
         }
     }
-    if (enc && vec && g_knob_x != 0 && g_knob_lane_rows != 2) {
+    if (vec && g_knob_x != 0 && g_knob_lane_rows != 2) {
         // rows of >= 128 vectors with an x-domain plan: the row-table encoder (knob 2 = 0 or knob 5 = 2: the element encoder, A/B)
         const PlanHeader *ph = static_cast<const PlanHeader *>(plan_host);
         const size_t rl = per_row ? row_len : n;
@@ -669,42 +723,45 @@ static int launch_codec(bool enc, const void *x, void *codes_or_out, const uint8
         if (pa.kind == kPlanLut && ph->xdom && vpr >= kRowKernelMinVpr && vpr <= 0xffffffffull && rl % 8 == 0) {
             // 4 vectors per lane for rows of >= 256 vectors (the encoder is VALU-bound: the per-task table build is then shared
             // by twice the elements: +3 ... +5 points, tools/probe_codec_u.py; knob 0 = 2 / 4 / 8 forces a size for A/B)
-            const uint32_t U = (g_knob_u == 2 || g_knob_u == 4 || g_knob_u == 8) ? (uint32_t)g_knob_u : (vpr >= 256 ? 4u : 2u);
+            const int U = one_of<2, 4, 8>(g_knob_u, vpr >= 256 ? 4 : 2);
             const size_t tpr = (vpr + 64 * U - 1) / (64 * U), total = (per_row ? rows : 1) * tpr;
             if (total <= 0x7fffffffull) {
                 XArgs xa = xargs_from_plan(plan_host, pa);
                 xa.inv_gmax = 1.0 / (double)gmax;
                 const uint4 *tab = plan_tab_ptr(plan_dev);
-#define ANTQ_ENCX(O, U_) hipLaunchKernelGGL((k_encode4_xrow<T, O, U_>), dim3((unsigned)total), dim3(64), 0, st, static_cast<const uint4 *>(x), \
-                                        static_cast<uint32_t *>(codes_or_out), (uint32_t)total, (uint32_t)vpr, (uint32_t)tpr, alpha, per_row, \
-                                        gmax, xa, tab + (pa.m_pad >> 2), reinterpret_cast<const float *>(tab), n_normal, zero_code,    \
-                                        pa.fastlim * 0.99999f)
-                if (U == 8) { if (ovp) ANTQ_ENCX(true, 8); else ANTQ_ENCX(false, 8); }
-                else if (U == 4) { if (ovp) ANTQ_ENCX(true, 4); else ANTQ_ENCX(false, 4); }
-                else        { if (ovp) ANTQ_ENCX(true, 2); else ANTQ_ENCX(false, 2); }
-#undef ANTQ_ENCX
-                return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+                return with_bool(ovp, [&](auto o) {
+                    return with_value<8, 4, 2>(U, [&](auto u) {
+                        launch_k(false, k_encode4_xrow<T, decltype(o)::value, decltype(u)::value>, dim3((unsigned)total), dim3(64), 0, st, x,
+                                 codes, total, vpr, tpr, alpha, per_row, gmax, xa, tab + (pa.m_pad >> 2), reinterpret_cast<const float *>(tab),
+                                 n_normal, zero_code, pa.fastlim * 0.99999f);
+                        return launch_status();
+                    });
+                });
             }
         }
     }
-    if (enc) {
-        const size_t lds = lds_table(pa, true);
-        uint32_t *codes = static_cast<uint32_t *>(codes_or_out);
-#define ANTQ_ENC(O, V) hipLaunchKernelGGL((k_encode4<T, O, V, kEncU>), gd, bd, lds, st, x, codes, n_oct, row_len, n_tasks, alpha, per_row, gmax, \
-                                          n_normal, zero_code, pa, plan_tab_ptr(plan_dev))
-        if (ovp) { if (vec) ANTQ_ENC(true, true); else ANTQ_ENC(true, false); }
-        else     { if (vec) ANTQ_ENC(false, true); else ANTQ_ENC(false, false); }
-#undef ANTQ_ENC
-    } else {
-        const float *grid_dev = reinterpret_cast<const float *>(plan_tab_ptr(plan_dev));
-        const uint32_t *codes = reinterpret_cast<const uint32_t *>(codes_in);
-#define ANTQ_DEC(O, V) hipLaunchKernelGGL((k_decode4<T, O, V>), gd, bd, 0, st, codes, codes_or_out, n_oct, row_len, alpha, per_row, \
-                                          gmax, n_normal, grid_dev, m)
-        if (ovp) { if (vec) ANTQ_DEC(true, true); else ANTQ_DEC(true, false); }
-        else     { if (vec) ANTQ_DEC(false, true); else ANTQ_DEC(false, false); }
-#undef ANTQ_DEC
-    }
-    return hipGetLastError() == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;
+    return launch_encode_units<Code4, T>(8, x, codes, n_oct, row_len, n_tasks, gd, vec, alpha, per_row, gmax, n_normal, zero_code, pa,
+                                         plan_dev, ovp, 0, st);
+}
+
+template <typename T>
+static int launch_decode4(const uint8_t *codes, void *out, size_t rows, size_t row_len, const float *alpha, int per_row, float gmax,
+                          const PlanArgs &pa, const void *plan_dev, int n_normal, bool ovp, hipStream_t st)
+{
+    if (codec_refuses<Code4>(row_len, 8, pa, n_normal, ovp)) return ANTQ_ERR_UNSUPPORTED;
+    const size_t n_oct = rows * row_len / 8;
+    const bool vec = reinterpret_cast<uintptr_t>(out) % 16 == 0;   // 16-byte vector I/O
+    size_t n_tasks;
+    dim3 gd;
+    if (!codec_tasks(n_oct, vec ? 1024 * IO<T>::EPL / 8 : 256, false, n_tasks, gd)) return ANTQ_ERR_UNSUPPORTED;
+    const float *grid_dev = reinterpret_cast<const float *>(plan_tab_ptr(plan_dev));
+    return with_bool(ovp, [&](auto o) {
+        return with_bool(vec, [&](auto v) {
+            launch_k(false, k_decode4<T, decltype(o)::value, decltype(v)::value>, gd, dim3(256), 0, st,
+                     reinterpret_cast<const uint32_t *>(codes), out, n_oct, row_len, alpha, per_row, gmax, n_normal, grid_dev, (int)pa.m);
+            return launch_status();
+        });
+    });
 }
 
 }  // namespace antq

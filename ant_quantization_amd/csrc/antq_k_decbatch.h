@@ -17,22 +17,8 @@
 
 namespace antq {
 
-// the decoded pair of one code byte, before scaling (k_decode4's selection)
-template <bool OVP>
-__device__ __forceinline__ void dec_pair(uint32_t byte, const float *g, int n_normal, float &q0, float &q1)
-{
-    const uint32_t c0 = byte & 15u, c1 = (byte >> 4) & 15u;
-    if (OVP) {
-        // identifier 15 in one nibble: that element is the victim (0), its partner an outlier
-        q0 = (c0 == 15u) ? 0.0f : ((c1 == 15u) ? g[n_normal + c0] : g[c0]);
-        q1 = (c1 == 15u) ? 0.0f : ((c0 == 15u) ? g[n_normal + c1] : g[c1]);
-    } else {
-        q0 = g[c0];
-        q1 = g[c1];
-    }
-}
-
-template <typename T> struct DecOut;           // two finished outputs -> the words the table / the store holds
+// (the decoded pair of one code byte, dec_pair, and the codebook's load, dec4_book: antq_device.h)
+template <typename T> struct DecOut;          // two finished outputs -> the words the table / the store holds
 template <> struct DecOut<float> {
     typedef uint2 Ent;                          // fp32: an entry is the pair's two words
     __device__ __forceinline__ static Ent make(float a, float b) { return make_uint2(f2u(a), f2u(b)); }
@@ -156,8 +142,7 @@ k_decode4_batch(const DecDesc *__restrict__ descs, const uint32_t *__restrict__ 
     const uint32_t task = __builtin_amdgcn_readfirstlane((b4 - D.first_block) * 4u + sub);
     if (task >= D.total_tasks) return;
     const uint32_t lane = threadIdx.x;
-    // (+ 0.0f: a codebook's -0 decodes to +0, which is what the reference's (q - d) + d makes of it for every finite d)
-    if (lane < 32u) g[lane] = (lane < D.m) ? ld_global(D.grid + lane) + 0.0f : 0.0f;
+    dec4_book(g, lane, D.grid, D.m);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     if (D.kind == kDecRow) {

@@ -5,7 +5,7 @@
 //
 //   loads      16 B (VEC: 32 elements) or 4 B (8 elements) of codes per lane and row
 //   decode     a wave-private table of 256 entries per row (per tensor: one), keyed by the code BYTE, entry = the pair's two
-//              finished outputs in the output type -- the decoder's own byte table (antq_k_decbatch.h: dec_pair / DecOut),
+//              finished outputs in the output type -- the decoder's own byte table (dec_pair, antq_k_decbatch.h: DecOut),
 //              so that W[n, k] IS the element antq_decode4 writes; per pair one ds_read_b32 (bf16 / f16) or ds_read_b64
 //              (fp32) and the exact widening to fp32
 #ifndef ANTQ_K_LINEAR4_H
@@ -17,12 +17,8 @@
 
 namespace antq {
 
-// The 4-bit byte table.  The codebook goes to LDS first, read with + 0.0f (a codebook's -0 decodes to +0, as in the
-// decoders); thread t writes entry t, and the caller orders the writes before the first Lin4Entry.
-__device__ __forceinline__ void lin4_book(float (&g)[32], uint32_t t, const float *grid, uint32_t m)
-{
-    if (t < 32u) g[t] = (t < m) ? ld_global(grid + t) + 0.0f : 0.0f;
-}
+// The 4-bit byte table.  The codebook goes to LDS first (antq_device.h: dec4_book), and the caller orders its writes before
+// the first Lin4Entry.
 // entry b of the table of scale s = alpha / gmax (AQ:536 scale = alpha / max(grid)): the decoded pair of code byte b, then
 // both finished outputs in the output type
 template <typename T, bool OVP> struct Lin4Entry {
@@ -64,7 +60,7 @@ template <typename T, bool OVP> struct Lin4Codec {
     __device__ __forceinline__ static void build(Lds<R> &L, uint32_t lane, uint32_t row0, uint32_t N, const float *alpha, int per_row,
                                                  float gmax, const float *grid, uint32_t m, int n_normal)
     {
-        lin4_book(L.g, lane, grid, m);
+        dec4_book(L.g, lane, grid, m);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         // this lane's four decoded pairs once, before any table is written: the R tables differ in the scale only
@@ -113,7 +109,7 @@ template <typename T, bool OVP> struct Lin4Codec {
     __device__ __forceinline__ static void mm_build(MmLds<ROWS> &L, uint32_t tid, uint32_t row0, uint32_t N, const float *alpha, int per_row,
                                                     float gmax, const float *grid, uint32_t m, int n_normal)
     {
-        lin4_book(L.g, tid, grid, m);
+        dec4_book(L.g, tid, grid, m);
         if (tid < (per_row ? (uint32_t)ROWS : 1u)) L.sc[tid] = ld_global(alpha + (per_row ? min(row0 + tid, N - 1u) : 0u)) / gmax;   // AQ:536 scale = alpha / max(grid)
         __syncthreads();
         const uint32_t b = tid & 255u;                 // threads b and 256 + b make entry b of the even and the odd tables

@@ -9,7 +9,7 @@
 //              (grid: x = tiles of n, y = tiles of m).  Wavefront w owns rows 64 w .. 64 w + 63 of the tile for all 64 n:
 //              4 x 4 accumulator tiles of v_mfma_f32_16x16x32_{bf16,f16}.  A wavefront whose 64 rows lie past M only helps
 //              to stage.  WAVES is the launcher's choice from M and N (gemm_waves; antq_debug_set key 23 forces it); no sum depends on it.
-//   W          the decoder's own byte tables (antq_k_linear4.h: lin4_book / Lin4Entry, i.e. dec_pair / DecOut), one per
+//   W          the decoder's own byte tables (antq_k_linear4.h: Lin4Entry over dec4_book, i.e. dec_pair / DecOut), one per
 //              output row (alpha_per_row; 64 KB) or one per tensor, laid out as Lin4Codec::MmLds and read by Lin4Codec::mm_b:
 //              one 32-bit code word is the 8 consecutive k of one weight row that a lane of the MFMA holds, four ds_read_b32
 //              ARE the four operand registers.  W[n, k] is the element antq_decode4 writes: no widening, no scale factored out.
@@ -120,7 +120,7 @@ k_linear4_gemm(const uint32_t *__restrict__ codes, const void *__restrict__ x, c
     load_step(0u);                                     // in flight while the tables are built
 
     // the tables: entry b of row r is Lin4Entry(b).at(alpha[r] / gmax), as Lin4Codec::mm_build makes them
-    lin4_book(lds.w.g, tid, grid, m);
+    dec4_book(lds.w.g, tid, grid, m);
     if (tid < (per_row ? (uint32_t)kGemmBN : 1u)) lds.w.sc[tid] = ld_global(alpha + (per_row ? min(n0 + tid, N - 1u) : 0u)) / gmax;   // AQ:536 scale = alpha / max(grid)
     __syncthreads();
     for (uint32_t b = tid; b < 256u; b += (uint32_t)NTH) {

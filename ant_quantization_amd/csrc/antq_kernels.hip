@@ -466,7 +466,7 @@ extern "C" int antq_encode4(const void *x, uint8_t *codes, size_t rows, size_t r
     const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     return with_dtype(dtype, [&](auto tag) {
-        return launch_codec<decltype(tag)>(true, x, codes, nullptr, rows, row_len, alpha, per_row ? 1 : 0, gmax, pa, plan_host, plan_dev, n_normal, ovp, st);
+        return launch_encode4<decltype(tag)>(x, reinterpret_cast<uint32_t *>(codes), rows, row_len, alpha, per_row ? 1 : 0, gmax, pa, plan_host, plan_dev, n_normal, ovp, st);
     });
 }
 
@@ -482,7 +482,7 @@ extern "C" int antq_decode4(const uint8_t *codes, void *out, size_t rows, size_t
     const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     return with_dtype(dtype, [&](auto tag) {
-        return launch_codec<decltype(tag)>(false, nullptr, out, codes, rows, row_len, alpha, per_row ? 1 : 0, gmax, pa, plan_host, plan_dev, n_normal, ovp, st);
+        return launch_decode4<decltype(tag)>(codes, out, rows, row_len, alpha, per_row ? 1 : 0, gmax, pa, plan_dev, n_normal, ovp, st);
     });
 }
 

@@ -70,7 +70,7 @@ def row_task_u(vpr):
 
 
 def encoder_u(vpr):
-    """csrc/antq_k_codec.h launch_codec: the largest of 8 / 4 / 3 / 2 that keeps the lanes of a row's tasks busy"""
+    """csrc/antq_k_codec.h launch_encode4: the largest of 8 / 4 / 3 / 2 that keeps the lanes of a row's tasks busy"""
     return _best_u(vpr, (8, 4, 3, 2), 0.02)[0]
 
 

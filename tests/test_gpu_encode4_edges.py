@@ -8,7 +8,7 @@ victim: 15, no entry within the scan's horizon: the code of the grid's zero).  N
 comes from the HIP library.  The inputs are built by encode4_cases.py, which test_encode4_cases_host.py holds to their
 conditions without a GPU.
 
-Not covered: tensors of more than 2^32 octets (the 64-bit row-index branch of k_encode4) -- too large for a test of seconds."""
+Not covered: tensors of more than 2^32 octets (the 64-bit row-index branch of k_encode) -- too large for a test of seconds."""
 import contextlib
 
 import numpy as np
@@ -272,7 +272,7 @@ def test_out_is_validated_and_odd_offsets_are_refused(antq_lib, dev):
 # ---------------------------------------------------------------------------------------------------------------------------
 def _plan_kind(antq_lib, g):
     """What the plan builder chose (antq_plan_kind and the plan header's eligibility words): a table whose thresholds move into
-    the x domain per row (k_encode4_xrow on long rows, the approximate-quotient branch of k_encode4 on short ones), a table
+    the x domain per row (k_encode4_xrow on long rows, the approximate-quotient branch of k_encode on short ones), a table
     decided in the d domain with the approximate quotient (that branch on every row) or with the exact division only (the
     quant_vec branch), or no table at all (quant_vec's literal scan)."""
     plan = antq_lib.plan_for(g)

@@ -85,7 +85,7 @@ def main():
     for x in (xf[0], xs[0]):
         a = _lib.absmax(x, 4096, 4096) * 0.25
         codes = _lib.encode4(x, a, ol, 32.0, 4096, 4096, True, n_normal=gn, ovp=True)
-        codec.append(lambda x=x, a=a: _lib.encode4(x, a, ol, 32.0, 4096, 4096, True, n_normal=gn, ovp=True))      # k_encode4
+        codec.append(lambda x=x, a=a: _lib.encode4(x, a, ol, 32.0, 4096, 4096, True, n_normal=gn, ovp=True))      # k_encode4_xrow
         codec.append(lambda x=x, a=a, c=codes: _lib.decode4(c, a, ol, 32.0, 4096, 4096, True, x.dtype, n_normal=gn, ovp=True))
     a_ant = _lib.absmax(xs[0], 4096, 4096)
     codec.append(lambda: _lib.encode4(xs[0], a_ant, flint, 10.0, 4096, 4096, True))                     # k_encode4_hrow, ANT
