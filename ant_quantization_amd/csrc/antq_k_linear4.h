@@ -104,6 +104,7 @@ template <typename T, bool OVP> struct Lin4Codec {
     };
     // (the 64 x 64 tile with 16 B of codes per lane has no registers for x in the ring)
     static constexpr bool mm_x_in_ring(int MT, int NT, bool VEC) { return !(MT == 4 && NT == 4 && VEC); }
+    static constexpr bool mm_tail_in_ring(int, int, bool) { return false; }
 
     template <int ROWS>
     __device__ __forceinline__ static void mm_build(MmLds<ROWS> &L, uint32_t tid, uint32_t row0, uint32_t N, const float *alpha, int per_row,

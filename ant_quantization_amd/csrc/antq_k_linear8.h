@@ -87,6 +87,9 @@ template <typename T, bool OVP> struct Lin8Codec {
         static_assert(sizeof(MmEnt) == 2 && sizeof(tab) <= 65536, "two entries are one operand register; the tables fit every launch");
     };
     static constexpr bool mm_x_in_ring(int, int, bool) { return true; }
+    // (with the pair rule these tiles sit on a register step: the partial chunk's own step after the ring cost them 3 - 4 VGPRs
+    // and a wave per SIMD, the select inside the ring costs none -- profiles/packed_linear_specials.md)
+    static constexpr bool mm_tail_in_ring(int MT, int NT, bool VEC) { return OVP && ((MT == 1 && NT == 2) || (MT == 2 && NT == 1 && !VEC)); }
 
     // Every wavefront holds the book in registers (dec8_book's four entries per lane) and builds whole rows r = w, w + 8, ...:
     // no staging array and no second barrier.

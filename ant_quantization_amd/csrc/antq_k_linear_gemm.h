@@ -30,7 +30,9 @@
 //              antq_linear4's (fp32 FMAs, e = 0 .. 7 per word) nor antq_linear4_mm's (eight partial chains and a fixed
 //              tree), so the same row of x has different low bits from the three.
 //   edges      rows m >= M, rows n >= N and pieces with k >= K clamp their addresses into the buffers; the x of such a row or
-//              piece is written to LDS as exactly zero (it adds +0), padded outputs are not stored.
+//              piece is written to LDS as exactly zero, and the W fragment of a lane with k >= K is zero too (the last step,
+//              one copy of the step after the loop): padding adds exactly +0 whatever the weights, Inf and NaN included.
+//              Padded outputs are not stored.
 // No atomics, no workspace: one launch, stream-ordered, capturable.
 // Measured (profiles/packed_linear4_gemm.md): 356 ... 404 TFLOP/s at best, slower than antq_decode4 + F.linear at every point
 // (0.20 ... 0.92 of its speed).  Per step a wavefront issues 64 scattered ds_read_b32 look-ups beside 16 ds_read_b128 and 16
@@ -106,7 +108,7 @@ k_linear4_gemm(const uint32_t *__restrict__ codes, const void *__restrict__ x, c
         }
         if (active) {
             if constexpr (VEC) {
-                const uint32_t u = min(c * 4u + kg, (K >> 5) - 1u);        // (units past the row's end repeat its last; their x is 0)
+                const uint32_t u = min(c * 4u + kg, (K >> 5) - 1u);        // (units past the row's end repeat its last; their x and their B are 0)
 #pragma unroll
                 for (int nt = 0; nt < NT; nt++) lin_words(*((const ANTQ_GLOBAL u32x4_t *)(crow[nt]) + u), cwn[nt]);
             } else {
@@ -138,7 +140,11 @@ k_linear4_gemm(const uint32_t *__restrict__ codes, const void *__restrict__ x, c
         for (int nt = 0; nt < NT; nt++) acc[mt][nt] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
 
     uint32_t cw[NT][4];
-    for (uint32_t c = 0; c < nsteps; c++) {
+    // One step.  Only the last step can hold pieces with k >= K: the loop leaves it to ONE copy of the step after it (TAIL),
+    // in which the B fragment of a lane with k >= K is zero like its x -- 0 * W is +0 only for a finite W, and the lane repeats
+    // the row's last unit, whatever that holds.
+    const uint32_t nmain = (K % (uint32_t)kGemmBK) ? nsteps - 1u : nsteps;
+    auto step = [&](uint32_t c, auto TAIL) {
 #pragma unroll
         for (int i = 0; i < XL; i++) {
             const uint32_t r = xr0 + (uint32_t)(RSTEP * i);
@@ -149,13 +155,20 @@ k_linear4_gemm(const uint32_t *__restrict__ codes, const void *__restrict__ x, c
 #pragma unroll
             for (int j = 0; j < 4; j++) cw[nt][j] = cwn[nt][j];
         __syncthreads();                               // the image (and, the first time, the tables) written
-        if (c + 1u < nsteps) load_step(c + 1u);
+        if constexpr (!decltype(TAIL)::value)
+            if (c + 1u < nsteps) load_step(c + 1u);
         if (active) {
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 u32x4_t b[NT];
 #pragma unroll
                 for (int nt = 0; nt < NT; nt++) b[nt] = C::mm_b(tab[nt], &cw[nt][j]);
+                if constexpr (decltype(TAIL)::value) {
+                    const bool kok = VEC ? c * 4u + kg < (K >> 5) : c * 16u + 4u * j + kg < wpr;
+#pragma unroll
+                    for (int nt = 0; nt < NT; nt++)
+                        if (!kok) b[nt] = u32x4_t{0u, 0u, 0u, 0u};
+                }
                 const uint32_t p = VEC ? 4u * kg + j : 4u * j + kg;
 #pragma unroll
                 for (int mt = 0; mt < MT; mt++) {
@@ -165,8 +178,12 @@ k_linear4_gemm(const uint32_t *__restrict__ codes, const void *__restrict__ x, c
                 }
             }
         }
+    };
+    for (uint32_t c = 0; c < nmain; c++) {
+        step(c, std::false_type{});
         __syncthreads();                               // the image free again
     }
+    if (nmain < nsteps) step(nmain, std::true_type{});
 
     // C / D map: column (n) = lane & 15, row (m) = 4 (lane >> 4) + reg
     if (!active) return;

@@ -35,7 +35,9 @@
 //                  or the other rows of x.
 //              (2) The fixed tree over the eight wavefronts.
 //   edges      rows m >= M, rows n >= N and lanes past the end of K clamp their addresses into the buffers; the x fragment
-//              of such a row or lane is all zeros (it adds exactly +0), padded outputs are not stored.
+//              of such a row or lane is all zeros, and so is the W fragment of a lane past the end of K (the row's last
+//              chunk, which runs after the ring in a step of its own): padding adds exactly +0 whatever the weights, Inf and
+//              NaN included.  Padded outputs are not stored.
 // No atomics, no split of K across workgroups, no workspace: one launch, stream-ordered, capturable.
 #ifndef ANTQ_K_LINEAR_MM_H
 #define ANTQ_K_LINEAR_MM_H
@@ -84,6 +86,8 @@ template <> struct MmOp<f16_tag> {
 //                                  aligned; the reduction reuses this memory), and what the build stages
 //     mm_build<ROWS>(lds, ...)     builds the tables, all 512 threads; ends with the barrier that orders them before the reads
 //     mm_x_in_ring(MT, NT, VEC)    whether x rides in the ring with the codes
+//     mm_tail_in_ring(MT, NT, VEC) whether a row's partial last chunk stays in the ring (every chunk then pays a select on
+//                                  its B fragments) or gets a step of its own after it (below)
 //     mm_b(t, w)                   the B fragment of one MFMA step from the WORDS code words w (t = the row's table)
 // MT: tiles of 16 rows of x; NT: tiles of 16 rows of W per workgroup; VEC: 16 B of codes per lane (K a multiple of the 16 bytes'
 // elements, codes aligned)
@@ -126,7 +130,7 @@ k_linear_mm(const uint32_t *__restrict__ codes, const void *__restrict__ x, cons
     constexpr bool XR = C::mm_x_in_ring(MT, NT, VEC);
     uint32_t cw[D][NT][CW];
     u32x4_t xa[XR ? D : 1][MT][S];
-    // load unit u = 4 c + kg of chunk c, clamped into the row (lanes past the row's end repeat its last unit; their x is 0)
+    // load unit u = 4 c + kg of chunk c, clamped into the row (lanes past the row's end repeat its last unit; their x and their B are 0)
     auto unit = [&](uint32_t c, bool &kok) {
         const uint32_t u0 = c * 4u + kg;
         kok = u0 < upr;
@@ -150,9 +154,17 @@ k_linear_mm(const uint32_t *__restrict__ codes, const void *__restrict__ x, cons
         for (int nt = 0; nt < NT; nt++) lin_words(__builtin_nontemporal_load((const ANTQ_GLOBAL Load *)(crow[nt]) + u), cw[d][nt]);
         if constexpr (XR) load_x(u, kok, xa[d]);
     };
+    // The ring serves the row's full chunks.  A partial last chunk is the last chunk of wavefront `towner` and runs after the
+    // ring, from slot 0 -- loaded here already when that wavefront has no full chunk before it: rows of at most 8 chunks, whose
+    // chunks all go to slot 0 of a wavefront each.
+    constexpr bool TIR = C::mm_tail_in_ring(MT, NT, VEC);
+    const uint32_t nfull = TIR ? nchunks : upr >> 2;     // (TIR: the ring serves every chunk, and no wavefront owns a tail)
+    const uint32_t towner = nfull < nchunks ? (nfull & (kMmWaves - 1u)) : ~0u;
+    const bool tearly = nfull < kMmWaves;
+    const uint32_t nfirst = tearly ? nchunks : nfull;
 #pragma unroll
     for (int d = 0; d < D; d++)                          // in flight while the tables are built
-        if (wave + kMmWaves * d < nchunks) load_chunk(wave + kMmWaves * d, d);
+        if (wave + kMmWaves * d < nfirst) load_chunk(wave + kMmWaves * d, d);
 
     C::template mm_build<ROWS>(lds, tid, row0, N, alpha, per_row, gmax, grid, m, n_normal);
 
@@ -165,11 +177,11 @@ k_linear_mm(const uint32_t *__restrict__ codes, const void *__restrict__ x, cons
 #pragma unroll
         for (int nt = 0; nt < NT; nt++) acc[mt][nt] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
 
-    for (uint32_t c0 = wave; c0 < nchunks; c0 += kMmWaves * D) {
+    for (uint32_t c0 = wave; c0 < nfull; c0 += kMmWaves * D) {
 #pragma unroll
         for (int d = 0; d < D; d++) {
             const uint32_t c = c0 + kMmWaves * d;
-            if (c >= nchunks) break;
+            if (c >= nfull) break;
             if constexpr (!XR) {
                 bool kok;
                 const uint32_t u = unit(c, kok);
@@ -180,12 +192,35 @@ k_linear_mm(const uint32_t *__restrict__ codes, const void *__restrict__ x, cons
             for (int nt = 0; nt < NT; nt++)
 #pragma unroll
                 for (int j = 0; j < S; j++) {
-                    const u32x4_t b = C::mm_b(tab[nt], &cw[d][nt][C::WORDS * j]);
+                    u32x4_t b = C::mm_b(tab[nt], &cw[d][nt][C::WORDS * j]);
+                    if constexpr (TIR)
+                        if (c * 4u + kg >= upr) b = u32x4_t{0u, 0u, 0u, 0u};
 #pragma unroll
                     for (int mt = 0; mt < MT; mt++) acc[mt][nt] = MmOp<T>::mfma(xc[mt][j], b, acc[mt][nt]);
                 }
-            if (c + kMmWaves * D < nchunks) load_chunk(c + kMmWaves * D, d);
+            if (c + kMmWaves * D < nfull) load_chunk(c + kMmWaves * D, d);
         }
+    }
+    // The row's partial last chunk, the last of the wavefront it falls to, in ring slot 0.  The B fragment of a lane past the
+    // row's end is zero like its x: 0 * W is +0 only for a finite W, and the lane holds the row's repeated last unit.
+    if (!TIR && wave == towner) {
+        uint32_t ct = nfull;
+        // (an empty statement the compiler cannot see through: the chunk's addresses are made here and not kept through
+        // the loop, 2 VGPRs less in the byte-code pair-rule variants -- profiles/packed_linear_specials.md)
+        asm volatile("" : "+s"(ct));
+        if (!tearly) load_chunk(ct, 0);
+        bool kok;
+        const uint32_t u = unit(ct, kok);
+        if constexpr (!XR) load_x(u, kok, xa[0]);
+#pragma unroll
+        for (int nt = 0; nt < NT; nt++)
+#pragma unroll
+            for (int j = 0; j < S; j++) {
+                u32x4_t b = C::mm_b(tab[nt], &cw[0][nt][C::WORDS * j]);
+                if (!kok) b = u32x4_t{0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int mt = 0; mt < MT; mt++) acc[mt][nt] = MmOp<T>::mfma(xa[0][mt][j], b, acc[mt][nt]);
+            }
     }
 
     // The eight partial tiles meet in LDS (the tables' memory, once every wavefront is done with them), G tiles per round:

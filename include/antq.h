@@ -529,6 +529,15 @@ int    antq_decode8_batch(const void *batch_host, const void *batch_dev, void *s
  *          not depend on M or on the other rows of x -- a row computed alone has the bits it has inside a call of 8.
  *   No floating-point atomics, no split-K across workgroups, no inter-workgroup communication, no workspace, no allocation,
  *          no synchronisation: stream-ordered and capturable into a graph.
+ *   Non-finite values (this entry point and antq_linear4_mm, antq_linear4_gemm, antq_linear8, antq_linear8_mm alike): NaN and
+ *          Inf in x, in W -- a NaN or Inf alpha, a weight that overflows `dtype`; 0 * Inf is a NaN weight, as in the decoder's
+ *          image -- and in bias follow IEEE 754 per product and per sum: a NaN product or bias, 0 * Inf either way, or Inf - Inf
+ *          give NaN, Inf of one sign gives that Inf.  A non-finite x[m,k] reaches row m of y only, a non-finite weight or
+ *          scale of row n and bias[n] reach column n only.  Padding never reaches a stored y[m,n], whatever the weights:
+ *          along K a lane past the end of the row has BOTH operands zero (not a zero x against a repeated weight, whose
+ *          0 * Inf would be NaN) and adds exactly +0; padded rows m >= M and n >= N repeat the last real row and may well
+ *          compute NaN, but only into accumulator rows and columns of their own, which are not stored.  The accumulators
+ *          start at +0: a sum of -0 products, with or without a bias of -0.0, is +0.  (tests/test_gpu_linear_specials.py)
  * Checked before anything touches HIP, in this order:
  *   ANTQ_ERR_ARG          a null codes / x / y / alpha / grid, m < 1, a bad dtype, a flag bit other than ANTQ_FLAG_OVP
  *   ANTQ_OK, no launch    M == 0 or N == 0
@@ -560,7 +569,8 @@ int antq_linear4(const uint8_t *codes_dev,          /* N*K/2 bytes, antq_encode4
  *          their partial sums are combined through LDS in one fixed order.  The order of the sum is NOT antq_linear4's: the
  *          same row has different low bits from the two entry points (both within the bound of an fp32 sum).
  *   No floating-point atomics, no split of K across workgroups, no workspace, no allocation, no synchronisation: stream-ordered
- *          and capturable into a graph.  Reads stay inside the buffers; padded rows contribute exactly +0 and are not stored.
+ *          and capturable into a graph.  Reads stay inside the buffers; lanes past the end of K add exactly +0, whatever
+ *          the weights, and padded rows are not stored (non-finite values: as antq_linear4).
  *   Subnormal bf16 / f16 weights and inputs are kept by the 16-bit MFMA on gfx950 (measured on an MI355X: a one-hot x returns the
  *          image's subnormal elements bit for bit), so W is the image there too: there is no departure to state.
  * Checked before anything touches HIP, in this order:
@@ -592,8 +602,9 @@ int antq_linear4_mm(const uint8_t *codes_dev, const void *x_dev, const void *bia
  *          antq_linear4's and NOT antq_linear4_mm's: the same row has different low bits from the three entry points (each
  *          within the bound of an fp32 sum).
  *   No floating-point atomics, no workspace, no allocation, no synchronisation: stream-ordered and capturable into a graph.
- *          Rows m >= M, n >= N and k >= K of the last step clamp their addresses into the buffers, contribute exactly +0 and
- *          are not stored: no read or write falls outside codes, x, bias, alpha / grid and y.
+ *          Rows m >= M, n >= N and k >= K of the last step clamp their addresses into the buffers; k >= K adds exactly +0
+ *          whatever the weights, padded rows are not stored (non-finite values: as antq_linear4): no read or write falls
+ *          outside codes, x, bias, alpha / grid and y.
  * Checked before anything touches HIP, in this order:
  *   ANTQ_ERR_ARG          as antq_linear4
  *   ANTQ_OK, no launch    M == 0 or N == 0
@@ -622,7 +633,7 @@ int antq_linear4_gemm(const uint8_t *codes_dev, const void *x_dev, const void *b
  *   The order of the sum is the kernel's own, but fixed: the same input gives the same bits on every run, and y[m,.] does
  *          not depend on M or on the other rows of x -- a row computed alone has the bits it has inside a call of 8.
  *   No floating-point atomics, no split-K across workgroups, no inter-workgroup communication, no workspace, no allocation,
- *          no synchronisation: stream-ordered and capturable into a graph.
+ *          no synchronisation: stream-ordered and capturable into a graph.  Non-finite values: as antq_linear4.
  * Checked before anything touches HIP, in this order:
  *   ANTQ_ERR_ARG          a null codes / x / y / alpha / grid, m < 1, a bad dtype, a flag bit other than ANTQ_FLAG_OVP
  *   ANTQ_OK, no launch    M == 0 or N == 0
@@ -653,7 +664,8 @@ int antq_linear8(const uint8_t *codes_dev,          /* N*K bytes, antq_encode8's
  *          their partial sums are combined through LDS in one fixed order.  The order of the sum is NOT antq_linear8's: the
  *          same row has different low bits from the two entry points (both within the bound of an fp32 sum).
  *   No floating-point atomics, no split of K across workgroups, no workspace, no allocation, no synchronisation: stream-ordered
- *          and capturable into a graph.  Reads stay inside the buffers; padded rows contribute exactly +0 and are not stored.
+ *          and capturable into a graph.  Reads stay inside the buffers; lanes past the end of K add exactly +0, whatever
+ *          the weights, and padded rows are not stored (non-finite values: as antq_linear4).
  *   At most 64 KB of LDS per workgroup (64 output rows with the pair rule), the size every launch may have.
  * Checked before anything touches HIP, in this order:
  *   ANTQ_ERR_ARG          as antq_linear8
