@@ -28,6 +28,7 @@ LINEAR4_MM_MAX_M = 64  # include/antq.h ANTQ_LINEAR4_MM_MAX_M: input rows antq_l
 LINEAR4_GEMM_MAX_M = 4096  # include/antq.h ANTQ_LINEAR4_GEMM_MAX_M: input rows antq_linear4_gemm takes
 LINEAR8_MAX_M = 8      # include/antq.h ANTQ_LINEAR8_MAX_M: input rows antq_linear8 takes
 LINEAR8_MM_MAX_M = 64  # include/antq.h ANTQ_LINEAR8_MM_MAX_M: input rows antq_linear8_mm takes
+LINEAR8_GEMM_MAX_M = 4096  # include/antq.h ANTQ_LINEAR8_GEMM_MAX_M: input rows antq_linear8_gemm takes
 PLAN_MAX_BYTES = 128 + 4 * MAX_GRID + 16 * 3072 + 20 * 1024 + 16 * 64
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16, torch.float64: F64}
@@ -65,7 +66,8 @@ def lib():
                              "antq_calibrate", "antq_prefetch_kernels", "antq_plan_eval_host_h", "antq_calibrate_batch", "antq_absmax_into", "antq_fakequant_f64",
                              "antq_absmax_t", "antq_alpha_grad_t", "antq_calibrate_install", "antq_decode4_batch_build", "antq_decode4_batch",
                              "antq_linear4", "antq_linear4_mm", "antq_encode8", "antq_decode8", "antq_decode8_batch_build",
-                             "antq_decode8_batch", "antq_linear8", "antq_linear8_mm", "antq_linear4_gemm"):
+                             "antq_decode8_batch", "antq_linear8", "antq_linear8_mm", "antq_linear4_gemm",
+                             "antq_linear8_gemm"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
                 L.antq_decode4_batch_capacity.restype = ctypes.c_size_t
@@ -90,6 +92,7 @@ def lib():
                 L.antq_linear8.argtypes = L.antq_linear4.argtypes
                 L.antq_linear8_mm.argtypes = L.antq_linear4.argtypes
                 L.antq_linear4_gemm.argtypes = L.antq_linear4.argtypes
+                L.antq_linear8_gemm.argtypes = L.antq_linear4.argtypes
                 # development: ANTQ_DEBUG_KNOBS="14=2,0=8" applies antq_debug_set(key, value) pairs to the loading thread
                 # (the knobs are thread-local; tools/fuzz_campaign.sh forces code paths with it)
                 for kv in [k for k in os.environ.get("ANTQ_DEBUG_KNOBS", "").split(",") if "=" in k]:
@@ -1059,6 +1062,15 @@ def linear8_mm(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_norm
     (float32 raises AntqError).  Same W, fp32 accumulation in the MFMA accumulator; the order of the sum is not linear8's,
     so the same row has different low bits from the two.  A row's bits do not depend on the other rows or on their number."""
     return _linear4_call("antq_linear8_mm", LINEAR8_MM_MAX_M, False, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out,
+                         per_byte=1)
+
+
+def linear8_gemm(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):
+    """linear8 as a tiled matrix-core product (antq_linear8_gemm): x is [..., K] with at most LINEAR8_GEMM_MAX_M rows, bfloat16
+    or float16 (float32 raises AntqError).  Same W; every y[m, n] is one fp32 MFMA accumulator chain over K, x staged through
+    LDS.  The order of the sum is this kernel's own, neither linear8's nor linear8_mm's: the same row has different low bits from
+    the three.  A row's bits do not depend on the other rows or on their number."""
+    return _linear4_call("antq_linear8_gemm", LINEAR8_GEMM_MAX_M, False, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out,
                          per_byte=1)
 
 

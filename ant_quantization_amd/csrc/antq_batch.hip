@@ -519,8 +519,9 @@ static int launch_linear_mm(const uint8_t *codes, const void *x, const void *bia
     });
 }
 
-// The launch of the tiled matrix-core linear (antq_k_linear_gemm.h) for 1 .. 4096 rows of x, bf16 / f16, 4-bit codes: one
+// The launch of the tiled matrix-core linear (antq_k_linear_gemm.h) for 1 .. 4096 rows of x, bf16 / f16; Codec as above: one
 // workgroup per (64 WAVES rows of x, 64 output rows) tile.
+template <template <typename, bool> class Codec>
 static int launch_linear_gemm(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
                               const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal, bool ovp, int dtype,
                               void *stream)
@@ -532,11 +533,11 @@ static int launch_linear_gemm(const uint8_t *codes, const void *x, const void *b
         if constexpr (std::is_same<T, float>::value) return (int)ANTQ_ERR_UNSUPPORTED;
         else return with_bool(ovp, [&](auto o) {
             return with_value<2, 4>(waves, [&](auto wv) {
-                return with_bool(linear_vec<Lin4Codec>(codes, K), [&](auto v) {
+                return with_bool(linear_vec<Codec>(codes, K), [&](auto v) {
                     constexpr int WAVES = decltype(wv)::value;
                     constexpr size_t BM = (size_t)kGemmWaveRows * WAVES;
                     const dim3 blocks((unsigned)((N + kGemmBN - 1) / kGemmBN), (unsigned)((M + BM - 1) / BM));
-                    launch_k(false, k_linear4_gemm<T, decltype(o)::value, WAVES, decltype(v)::value>, blocks, dim3(64u * WAVES), 0, st,
+                    launch_k(false, k_linear_gemm<Codec<T, decltype(o)::value>, WAVES, decltype(v)::value>, blocks, dim3(64u * WAVES), 0, st,
                              reinterpret_cast<const uint32_t *>(codes), x, bias, y, (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha,
                              per_row ? 1 : 0, gmax, grid, (uint32_t)m, ovp ? n_normal : 0);
                     return launch_status();
@@ -579,8 +580,8 @@ extern "C" int antq_linear4_gemm(const uint8_t *codes, const void *x, const void
     const int rc = linear_checks(codes, x, bias, y, M, N, K, alpha, grid, m, n_normal, flags, dtype, ANTQ_LINEAR4_GEMM_MAX_M, true,
                                  dec4_book_ok, 4, 2);
     if (rc != kLinearGo) return rc;
-    return launch_linear_gemm(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0, dtype,
-                              stream);
+    return launch_linear_gemm<Lin4Codec>(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal,
+                                         (flags & ANTQ_FLAG_OVP) != 0, dtype, stream);
 }
 
 // The byte-code form of antq_linear4 (antq_k_linear8.h): the same launch, W the image antq_decode8 writes.
@@ -606,6 +607,19 @@ extern "C" int antq_linear8_mm(const uint8_t *codes, const void *x, const void *
     if (rc != kLinearGo) return rc;
     return launch_linear_mm<Lin8Codec>(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0,
                                        dtype, stream);
+}
+
+// The byte-code form of antq_linear4_gemm: 1 .. ANTQ_LINEAR8_GEMM_MAX_M rows of x as a tiled matrix-core product, W the image
+// antq_decode8 writes; bf16 / f16.
+extern "C" int antq_linear8_gemm(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
+                                 const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
+                                 unsigned flags, int dtype, void *stream)
+{
+    const int rc = linear_checks(codes, x, bias, y, M, N, K, alpha, grid, m, n_normal, flags, dtype, ANTQ_LINEAR8_GEMM_MAX_M, true,
+                                 dec8_book_ok, 8, 2);
+    if (rc != kLinearGo) return rc;
+    return launch_linear_gemm<Lin8Codec>(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal,
+                                         (flags & ANTQ_FLAG_OVP) != 0, dtype, stream);
 }
 
 namespace antq {

@@ -46,7 +46,7 @@ namespace antq {
     X(20, sort, 1)         /* clip searches from the sorted row (antq_k_sortsearch.h): 0 off, 1 the default rule, 2 every eligible launch */ \
     X(21, sort_short, 1)   /* 0: rows of <= 1024 elements through the 4096-key sorted search (A/B) */                       \
     X(22, mm_tile, 0)      /* antq_linear4_mm / antq_linear8_mm: tiles of 16 output rows per workgroup forced to 1 / 2 / 4 (A/B; 0 = the rule) */ \
-    X(23, gemm_tile, 0)    /* antq_linear4_gemm: wavefronts (tiles of 64 rows of x) per workgroup forced to 2 / 4 (A/B; 0 = the rule) */
+    X(23, gemm_tile, 0)    /* antq_linear4_gemm / antq_linear8_gemm: wavefronts (tiles of 64 rows of x) per workgroup forced to 2 / 4 (A/B; 0 = the rule) */
 #define ANTQ_KNOB_DECLARE(key, name, dflt) extern thread_local int g_knob_##name;
 ANTQ_KNOBS(ANTQ_KNOB_DECLARE)
 #undef ANTQ_KNOB_DECLARE

@@ -50,6 +50,7 @@ template <typename T, bool OVP> struct Lin4Codec {
     static constexpr int WORDS = 1;
     static constexpr uint32_t TS = 256u;
     static constexpr bool TIE = false;
+    static constexpr bool PAIR = OVP;                   // (antq_k_linear_gemm.h builds this codec's tables in place)
     template <int R> struct Lds {
         __attribute__((aligned(16))) Ent tab[R * 256];
         float g[32];

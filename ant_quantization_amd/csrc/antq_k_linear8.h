@@ -91,18 +91,18 @@ template <typename T, bool OVP> struct Lin8Codec {
     // and a wave per SIMD, the select inside the ring costs none -- profiles/packed_linear_specials.md)
     static constexpr bool mm_tail_in_ring(int MT, int NT, bool VEC) { return OVP && ((MT == 1 && NT == 2) || (MT == 2 && NT == 1 && !VEC)); }
 
-    // Every wavefront holds the book in registers (dec8_book's four entries per lane) and builds whole rows r = w, w + 8, ...:
-    // no staging array and no second barrier.
-    template <int ROWS>
-    __device__ __forceinline__ static void mm_build(MmLds<ROWS> &L, uint32_t tid, uint32_t row0, uint32_t N, const float *alpha, int per_row,
-                                                    float gmax, const float *grid, uint32_t m, int n_normal)
+    // Every wavefront holds the book in registers (dec8_book's four entries per lane) and builds whole rows r = w, w + NW, ...
+    // of a workgroup of NW wavefronts: no staging array and no second barrier.
+    template <int ROWS, int NW>
+    __device__ __forceinline__ static void mm_rows(MmLds<ROWS> &L, uint32_t tid, uint32_t row0, uint32_t N, const float *alpha, int per_row,
+                                                   float gmax, const float *grid, uint32_t m, int n_normal)
     {
         const uint32_t lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
         DecDesc D;
         D.grid = grid; D.m = m; D.n_normal = n_normal;
         float nv[4], ov[4];
         dec8_book<OVP>(D, lane, nv, ov);
-        for (uint32_t r = wave; r < (per_row ? (uint32_t)ROWS : 1u); r += kMmWaves) {
+        for (uint32_t r = wave; r < (per_row ? (uint32_t)ROWS : 1u); r += (uint32_t)NW) {
             const float s = ld_global(alpha + (per_row ? min(row0 + r, N - 1u) : 0u)) / gmax;   // AQ:536 scale = alpha / max(grid)
 #pragma unroll
             for (int k = 0; k < 4; k++) {
@@ -111,7 +111,21 @@ template <typename T, bool OVP> struct Lin8Codec {
                 if (OVP) L.tab[r * TS + 256u + b] = Dec8Out<T>::make(ov[k] * s);
             }
         }
+    }
+    template <int ROWS>
+    __device__ __forceinline__ static void mm_build(MmLds<ROWS> &L, uint32_t tid, uint32_t row0, uint32_t N, const float *alpha, int per_row,
+                                                    float gmax, const float *grid, uint32_t m, int n_normal)
+    {
+        mm_rows<ROWS, kMmWaves>(L, tid, row0, N, alpha, per_row, gmax, grid, m, n_normal);
         __syncthreads();
+    }
+    // The tiled kernel's build (antq_k_linear_gemm.h: k_linear_gemm), for a workgroup of NW wavefronts: the same rows, strided by
+    // ITS wavefront count.  No barrier at the end: the caller's next one orders the tables before the reads.
+    template <int ROWS, int NW>
+    __device__ __forceinline__ static void gemm_build(MmLds<ROWS> &L, uint32_t tid, uint32_t row0, uint32_t N, const float *alpha, int per_row,
+                                                      float gmax, const float *grid, uint32_t m, int n_normal)
+    {
+        mm_rows<ROWS, NW>(L, tid, row0, N, alpha, per_row, gmax, grid, m, n_normal);
     }
 
     // two code words are the step's 8 elements; two 16-bit look-ups are one operand register

@@ -126,6 +126,29 @@ B takes up to twice A's time on the other layers (0.51 ... 0.83x), and what the 
 scratch.  At M = 8 B beats antq_linear8 in 12 of 20 rows only (0.81 ... 1.41x): the routing up to 8 rows stays.  The tile rule of
 the 4-bit kernel (mm_ntiles) was within 7.5 % of the best forced shape in every row and is kept.  Not measured: other M, per-tensor
 scales, the 8-byte code path, a whole model's forward time, more than one run; no hardware counters were collected.
+
+`fused_byte_gemm_rows=R` (with fused_linear and fused_bytes, else AntqError naming the missing one; LINEAR8_MM_MAX_M = 64 < R <=
+LINEAR8_GEMM_MAX_M = 4096; off by default -- without it everything above is unchanged) is `fused_gemm_rows` for the byte-coded
+entries: no-grad calls of a fusable byte-coded bfloat16 / float16 layer with more rows than the other byte kernels take -- more
+than 8, or more than `fused_byte_rows` when that is given -- and at most R rows run `antq_linear8_gemm`, the same tiled
+matrix-core kernel instantiated for byte codes (W bit for bit the image `antq_decode8` writes, one fp32 accumulator chain per
+output, its own order of the sum; `.fused_byte_gemm_calls` counts them), and with `keep_images=False` decode nothing and leave
+the scratch buffer alone.  Calls of more than R rows, float32 layers and non-fusable byte entries keep the paths above;
+`fused_gemm_rows` keeps meaning 4-bit entries only.  A mixed-precision model packed with both options, `keep_images=False` and
+R at least its largest call needs no scratch decode at all: the scratch's lifetime rule then binds no layer.
+Measured (profiles/packed_linear8_gemm.md; one MI355X, one run, 5 repetitions of graph-replayed calls per point -- 200 per graph
+up to M = 512, 50 beyond -- with the arms alternated, medians, spread below 11 %; M = 64 / 128 / 256 / 512 / 1024 / 4096, the five
+layer shapes above, bf16 and f16, ANT int-8 and OliVe int-8, per-row scales; A = F.linear on the kept image, C = antq_decode8
+into scratch + F.linear, B = antq_linear8_gemm): B LOSES to C and to A at all 120 points (C / B 0.17 ... 0.78, A / B 0.09 ... 0.46),
+so no R is worth choosing for speed on any layer measured.  Closest to C: [16384, 4096] at M = 64 ... 256 (0.61 ... 0.78) and
+[3072, 768] up to M = 1024 (0.50 ... 0.69); elsewhere B takes 2.2 ... 6 times C's time (4.3 ... 5 times at M = 4096 on the wide
+layers), and at M = 64 it takes 2.8 ... 6.1 times antq_linear8_mm's, so give fused_byte_rows=64 beside it.  The kernel tops out at
+255 ... 304 TFLOP/s against the 4-bit form's 356 ... 404: it makes 128 table look-ups per wavefront and step, twice as many.
+With the plain book the launcher's shared tile rule chose 256 rows per workgroup at 18 points where 128 were 8 ... 20 % faster
+(two 64 KB workgroups fit a CU); the rule was left alone.  What the option buys is the memory (no decoded image, half the weight
+bytes) and the free scratch buffer, at those prices.  Not measured: other M, the 8-byte code path, per-tensor scales, a whole
+model's forward, more than one run; no hardware counters.  Not built: one decode of a B fragment shared by the workgroup's
+wavefronts.
 """
 import torch
 import torch.nn.functional as F
@@ -156,14 +179,15 @@ def _settle(q):
 
 class PackedBank:
     def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True, fused_rows=None,
-                 byte_codes=False, fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None):
+                 byte_codes=False, fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None):
         """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict);
         a layer's code width is then the one its stored size says (numel / 2 bytes: 4-bit, numel bytes: byte codes).
         byte_codes: layers the 4-bit codec refuses and the byte codec accepts are packed one code per byte (width 8).
         fused_bytes (with fused_linear): byte-coded Linear layers of K % 8 == 0 compute from their codes too (antq_linear8).
         fused_byte_rows=R (with fused_linear and fused_bytes): their bf16 / f16 calls of 9 .. R rows too (antq_linear8_mm).
         fused_gemm_rows=R (with fused_linear): bf16 / f16 calls of the 4-bit layers with more rows than the other kernels take
-        and at most R rows run antq_linear4_gemm."""
+        and at most R rows run antq_linear4_gemm.
+        fused_byte_gemm_rows=R (with fused_linear and fused_bytes): the same for the byte-coded layers (antq_linear8_gemm)."""
         self.byte_codes = bool(byte_codes)
         if fused_bytes and not fused_linear:
             raise _lib.AntqError("PackedBank: fused_bytes needs fused_linear=True")
@@ -172,6 +196,9 @@ class PackedBank:
         self.fused_byte_calls = 0  # forwards antq_linear8 served
         self.fused_byte_rows = None if fused_byte_rows is None else int(fused_byte_rows)   # bf16 / f16 calls of 9 .. R rows: antq_linear8_mm
         self.fused_byte_mm_calls = 0   # forwards antq_linear8_mm served
+        _check_fused_byte_gemm_rows("PackedBank", fused_linear, fused_bytes, fused_byte_gemm_rows)
+        self.fused_byte_gemm_rows = None if fused_byte_gemm_rows is None else int(fused_byte_gemm_rows)   # bf16 / f16 calls of more rows, up to this many: antq_linear8_gemm
+        self.fused_byte_gemm_calls = 0     # forwards antq_linear8_gemm served
         if not keep_images and not fused_linear:
             raise _lib.AntqError("PackedBank: keep_images=False needs fused_linear=True (nothing else computes from the codes)")
         _check_fused_rows("PackedBank", fused_linear, fused_rows)
@@ -425,12 +452,12 @@ class PackedBank:
         byte = e["width"] == 8                     # (fused_rows is antq_linear4_mm's, fused_byte_rows antq_linear8_mm's)
         max_rows = _lib.LINEAR8_MAX_M if byte else _lib.LINEAR4_MAX_M
         more_rows = self.fused_byte_rows if byte else self.fused_rows
-        gemm_rows = None if byte else self.fused_gemm_rows     # (the tiled kernel takes 4-bit codes only)
+        gemm_rows = self.fused_byte_gemm_rows if byte else self.fused_gemm_rows     # (fused_gemm_rows is antq_linear4_gemm's)
         if e["dtype"] in (torch.bfloat16, torch.float16):
             if more_rows is not None:
                 max_rows = more_rows
             if gemm_rows is not None:
-                max_rows = gemm_rows               # (> LINEAR4_MM_MAX_M >= fused_rows)
+                max_rows = gemm_rows               # (> LINEAR4_MM_MAX_M = LINEAR8_MM_MAX_M >= fused_rows, fused_byte_rows)
         if (input.is_cuda and input.dtype == e["dtype"] and input.device == e["device"] and input.dim() >= 1 and input.shape[-1] == K
                 and 0 < input.numel() <= max_rows * K and input.is_contiguous() and input.data_ptr() % 16 == 0
                 and not (byte and e["codes"].data_ptr() % 8)
@@ -440,9 +467,12 @@ class PackedBank:
             if byte and input.numel() <= _lib.LINEAR8_MAX_M * K:
                 self.fused_byte_calls += 1
                 fn = _lib.linear8
-            elif byte:
+            elif byte and self.fused_byte_rows is not None and input.numel() <= self.fused_byte_rows * K:
                 self.fused_byte_mm_calls += 1
                 fn = _lib.linear8_mm
+            elif byte:                             # more rows than the other kernels take, at most fused_byte_gemm_rows
+                self.fused_byte_gemm_calls += 1
+                fn = _lib.linear8_gemm
             elif input.numel() <= _lib.LINEAR4_MAX_M * K:
                 self.fused_calls += 1
                 fn = _lib.linear4
@@ -482,6 +512,11 @@ def _check_fused_gemm_rows(who, fused_linear, fused_gemm_rows):
                        _lib.LINEAR4_GEMM_MAX_M)
 
 
+def _check_fused_byte_gemm_rows(who, fused_linear, fused_bytes, fused_byte_gemm_rows):
+    _check_rows_option(who, "fused_byte_gemm_rows", fused_byte_gemm_rows, (("fused_linear", fused_linear), ("fused_bytes", fused_bytes)),
+                       _lib.LINEAR8_MM_MAX_M, _lib.LINEAR8_GEMM_MAX_M)
+
+
 def _no_auto_bank(model):
     """The automatic weight bank steps aside (as for set_weights_at_rest(resident=False)), and the choice stays with the
     module: a deep copy carries the mark, so its forward hook does not arm a fresh AutoBank for it."""
@@ -499,7 +534,7 @@ def _bank_of(model):
 
 
 def pack_model(model, release_weights=False, fused_linear=False, keep_images=True, fused_rows=None, byte_codes=False,
-               fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None):
+               fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
     (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
     byte_codes: layers the 4-bit codec refuses for their codebook (5- to 8-bit layers, OliVe's unsigned 16 + 15) or their row
@@ -536,9 +571,19 @@ def pack_model(model, release_weights=False, fused_linear=False, keep_images=Tru
     scratch + F.linear, B = antq_linear4_gemm; M = 64 ... 4096, five layer shapes, bf16 / f16, ANT and OliVe): B loses to
     C and to A at all 120 points (C / B 0.20 ... 0.92, best on [16384, 4096] at M = 128 / 256), so no R is worth choosing
     for speed; the option buys the memory and the free scratch.  Give fused_rows=64 beside it (at M = 64 B takes 2.9 ...
-    4.7 times antq_linear4_mm's time).  Not measured: other M, the 4-byte code path, per-tensor scales, a whole model."""
+    4.7 times antq_linear4_mm's time).  Not measured: other M, the 4-byte code path, per-tensor scales, a whole model.
+    fused_byte_gemm_rows=R (with fused_linear and fused_bytes, 64 < R <= 4096): the same for the byte-coded layers -- their bf16 /
+    f16 calls with more rows than the other byte kernels take (more than 8, or more than fused_byte_rows) and at most R rows
+    compute from the byte codes as a tiled matrix-core product (antq_linear8_gemm, .fused_byte_gemm_calls) and, with
+    keep_images=False, decode nothing and leave the scratch alone.  Measured (profiles/packed_linear8_gemm.md, one MI355X, one
+    run; A / C / B as above with antq_decode8 and antq_linear8_gemm; M = 64 ... 4096, five layer shapes, bf16 / f16, ANT and
+    OliVe int-8): B loses to C and to A at all 120 points (C / B 0.17 ... 0.78, best on [16384, 4096] at M = 64 ... 256; A / B
+    0.09 ... 0.46), so no R is worth choosing for speed; the option buys the memory and a model without scratch decodes.  Give
+    fused_byte_rows=64 beside it (at M = 64 B takes 2.8 ... 6.1 times antq_linear8_mm's time).  Not measured: other M, the 8-byte
+    code path, per-tensor scales, a whole model."""
     return PackedBank(model, release_weights=release_weights, fused_linear=fused_linear, keep_images=keep_images, fused_rows=fused_rows,
-                      byte_codes=byte_codes, fused_bytes=fused_bytes, fused_byte_rows=fused_byte_rows, fused_gemm_rows=fused_gemm_rows)
+                      byte_codes=byte_codes, fused_bytes=fused_bytes, fused_byte_rows=fused_byte_rows, fused_gemm_rows=fused_gemm_rows,
+                      fused_byte_gemm_rows=fused_byte_gemm_rows)
 
 
 def packed_state_dict(model):
@@ -560,12 +605,12 @@ def _packed_keys(sd, codes):
 
 
 def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, keep_images=True, fused_rows=None,
-                           fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None):
+                           fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None):
     """Load a packed checkpoint into a freshly wrapped, uncalibrated model living on the GPU: the quantiser state is
     installed the way load_ant_state_dict + load_state_dict do (scales keep the dtype they were stored with), a PackedBank is attached from the stored codes without
     re-encoding (a layer's code width is the one its stored size says: numel / 2 bytes are 4-bit codes, numel bytes byte codes;
     any other size raises AntqError naming the layer), and the weights are materialised by the batched decode
-    (release_weights=False: copied into the layers' own float weights instead of replacing them).  fused_linear / keep_images / fused_rows / fused_bytes / fused_byte_rows / fused_gemm_rows: as in pack_model (the code width still comes from the stored size).  Returns the bank."""
+    (release_weights=False: copied into the layers' own float weights instead of replacing them).  fused_linear / keep_images / fused_rows / fused_bytes / fused_byte_rows / fused_gemm_rows / fused_byte_gemm_rows: as in pack_model (the code width still comes from the stored size).  Returns the bank."""
     if not keep_images and not fused_linear:
         raise _lib.AntqError("load_packed_state_dict: keep_images=False needs fused_linear=True")
     _check_fused_rows("load_packed_state_dict", fused_linear, fused_rows)
@@ -573,6 +618,7 @@ def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, 
         raise _lib.AntqError("load_packed_state_dict: fused_bytes needs fused_linear=True")
     _check_fused_byte_rows("load_packed_state_dict", fused_linear, fused_bytes, fused_byte_rows)
     _check_fused_gemm_rows("load_packed_state_dict", fused_linear, fused_gemm_rows)
+    _check_fused_byte_gemm_rows("load_packed_state_dict", fused_linear, fused_bytes, fused_byte_gemm_rows)
     suffix = "." + CODES_KEY
     codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}
     rest = {k: v for k, v in sd.items() if not k.endswith(suffix)}
@@ -591,7 +637,8 @@ def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, 
     for _, _, q, _ in _weight_layers(model):
         _settle(q)
     bank = PackedBank(model, release_weights=release_weights, codes=codes, fused_linear=fused_linear, keep_images=keep_images,
-                      fused_rows=fused_rows, fused_bytes=fused_bytes, fused_byte_rows=fused_byte_rows, fused_gemm_rows=fused_gemm_rows)
+                      fused_rows=fused_rows, fused_bytes=fused_bytes, fused_byte_rows=fused_byte_rows, fused_gemm_rows=fused_gemm_rows,
+                      fused_byte_gemm_rows=fused_byte_gemm_rows)
     if not release_weights:
         with torch.no_grad():
             for e in bank.entries.values():

@@ -46,7 +46,8 @@ extern "C" {
  * that existed changed, so callers built against 7 keep working).  antq_linear4 (the packed 4-bit linear) added likewise,
  * and antq_linear4_mm (its matrix-core form for up to 64 rows), and antq_encode8 / antq_decode8 / antq_decode8_batch_capacity /
  * antq_decode8_batch_build / antq_decode8_batch (the byte-code codec), and antq_linear8 (the linear from byte codes), and
- * antq_linear8_mm (its matrix-core form for up to 64 rows), and antq_linear4_gemm (the tiled 4-bit form for up to 4096 rows).
+ * antq_linear8_mm (its matrix-core form for up to 64 rows), and antq_linear4_gemm (the tiled 4-bit form for up to 4096 rows),
+ * and antq_linear8_gemm (the same from byte codes).
  * A caller built against another version must not call in: the blobs / argument lists differ. */
 #define ANTQ_ABI_VERSION 7
 
@@ -529,7 +530,7 @@ int    antq_decode8_batch(const void *batch_host, const void *batch_dev, void *s
  *          not depend on M or on the other rows of x -- a row computed alone has the bits it has inside a call of 8.
  *   No floating-point atomics, no split-K across workgroups, no inter-workgroup communication, no workspace, no allocation,
  *          no synchronisation: stream-ordered and capturable into a graph.
- *   Non-finite values (this entry point and antq_linear4_mm, antq_linear4_gemm, antq_linear8, antq_linear8_mm alike): NaN and
+ *   Non-finite values (this entry point and antq_linear4_mm, antq_linear4_gemm, antq_linear8, antq_linear8_mm, antq_linear8_gemm alike): NaN and
  *          Inf in x, in W -- a NaN or Inf alpha, a weight that overflows `dtype`; 0 * Inf is a NaN weight, as in the decoder's
  *          image -- and in bias follow IEEE 754 per product and per sum: a NaN product or bias, 0 * Inf either way, or Inf - Inf
  *          give NaN, Inf of one sign gives that Inf.  A non-finite x[m,k] reaches row m of y only, a non-finite weight or
@@ -616,6 +617,38 @@ int antq_linear4_mm(const uint8_t *codes_dev, const void *x_dev, const void *bia
  * ------------------------------------------------------------------------- */
 #define ANTQ_LINEAR4_GEMM_MAX_M 4096
 int antq_linear4_gemm(const uint8_t *codes_dev, const void *x_dev, const void *bias_dev, void *y_dev,
+                      size_t M, size_t N, size_t K,
+                      const float *alpha_dev, int alpha_per_row, float gmax,
+                      const float *grid_dev, int m, int n_normal,
+                      unsigned flags /* 0 | ANTQ_FLAG_OVP */, int dtype /* BF16 | F16 */, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * The byte-code form of antq_linear4_gemm: the same tiled matrix-core product for 1 .. ANTQ_LINEAR8_GEMM_MAX_M rows of x from
+ * the byte codes of W, BF16 and F16 only -- one kernel, written once over the two code widths.  Parameters as antq_linear8.
+ *   W[n,k] is, bit for bit, the element antq_decode8 writes in `dtype` (antq_linear8_mm's tables of the decoder's finished
+ *          16-bit outputs, for the 64 output rows of a tile; two look-ups are one MFMA operand register).
+ *   y[m,n] = round_dtype( sum_k x[m,k] * W[n,k] + bias[n] ): ONE fp32 MFMA accumulator chain over K in steps of 128 elements in
+ *          rising order, the bias added in fp32, one rounding to `dtype`.  K is split neither across wavefronts nor across
+ *          workgroups.
+ *   The bits of y[m,n] depend only on row m of x, row n of W, bias[n], K and the code path (below): not on M, not on N, not on
+ *          the other rows of x, not on the tile shape, not on the run.  The order of the sum is this kernel's own -- NOT
+ *          antq_linear8's and NOT antq_linear8_mm's.
+ *   No floating-point atomics, no workspace, no allocation, no synchronisation: stream-ordered and capturable into a graph.
+ *          Rows m >= M, n >= N and k >= K of the last step clamp their addresses into the buffers; k >= K adds exactly +0
+ *          whatever the weights, padded rows are not stored (non-finite values: as antq_linear4).
+ *   At most 128 KB of LDS per workgroup (the pair rule's tables of 64 rows and the staged x of 256 rows).
+ * Checked before anything touches HIP, in this order:
+ *   ANTQ_ERR_ARG          as antq_linear8
+ *   ANTQ_OK, no launch    M == 0 or N == 0
+ *   ANTQ_ERR_UNSUPPORTED  dtype == ANTQ_F32; M > ANTQ_LINEAR8_GEMM_MAX_M; K == 0 or K % 8 != 0; the byte decoder's refusals;
+ *                         N >= 2^31 or K >= 2^31
+ *   ANTQ_ERR_ALIGN        x_dev not 16-byte aligned, codes_dev not 8-byte aligned, y_dev / bias_dev not 2-byte aligned
+ * Codes are read 16 bytes per load (two loads per lane, output row and step) when K % 16 == 0 and codes_dev is 16-byte aligned,
+ * 8 bytes per load (four) otherwise (the order of the sum differs between the two, nothing else).  antq_debug_set key 23
+ * forces the tile shape as for antq_linear4_gemm.  Measurements: profiles/packed_linear8_gemm.md.
+ * ------------------------------------------------------------------------- */
+#define ANTQ_LINEAR8_GEMM_MAX_M 4096
+int antq_linear8_gemm(const uint8_t *codes_dev, const void *x_dev, const void *bias_dev, void *y_dev,
                       size_t M, size_t N, size_t K,
                       const float *alpha_dev, int alpha_per_row, float gmax,
                       const float *grid_dev, int m, int n_normal,
@@ -739,7 +772,7 @@ int antq_copy(const void *src_dev, void *dst_dev, size_t bytes, void *stream);
  *           with or without the pair rule, one-scale fp32 tensors from 4096)
  *   key 21: 0 sends rows of <= 1024 elements through the 4096-key kernel instead of one row per wavefront (A/B)
  *   key 22: antq_linear4_mm / antq_linear8_mm: tiles of 16 output rows per workgroup, 1 / 2 / 4 (A/B; 0 = the launcher's rule; no result changes)
- *   key 23: antq_linear4_gemm: wavefronts per workgroup, 2 / 4, i.e. tiles of 128 / 256 rows of x (A/B; 0 = the launcher's rule:
+ *   key 23: antq_linear4_gemm / antq_linear8_gemm: wavefronts per workgroup, 2 / 4, i.e. tiles of 128 / 256 rows of x (A/B; 0 = the launcher's rule:
  *           2 while the tiles of 128 rows number at most 256; no result changes) */
 int antq_debug_set(int key, int value);
 
