@@ -5,7 +5,8 @@
 // workgroup on ONE address (256 of them arrive together at the end of a 5 us stream and serialise: 9.3 us for a 33.5 MB
 // bf16 tensor, 45 % of the roofline) and it needs its accumulator zeroed first; alpha gradient = a second launch that adds
 // the partials.  Here: hierarchical last-arriver tickets in a small caller-owned block (ANTQ_REDUCE_WS_BYTES, zeroed ONCE by
-// the caller; every call leaves it zeroed, so calls issued one after the other on one stream share it):
+// the caller; every call leaves its counters -- kTkCounterBytes, all it relies on -- zeroed and its partials behind, so calls
+// issued one after the other on one stream share it):
 //   * workgroup b stores its partial, fences, and takes a ticket of its GROUP (kGroup workgroups, one counter per group,
 //     128 bytes apart: the counters of different groups live in different cache lines / channels and do not queue up);
 //   * the last arriver of a group folds the group's partials IN INDEX ORDER (so the result does not depend on who came

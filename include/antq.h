@@ -212,8 +212,12 @@ int antq_absmax(const void *x_dev, float *amax_dev, size_t rows, size_t row_len,
 int antq_absmax_into(const void *x_dev, float *amax_dev, size_t n, int dtype, void *stream);
 
 /* Whole-tensor reductions in ONE launch with nothing to zero per call (ABI 7).  reduce_ws_dev: ANTQ_REDUCE_WS_BYTES of
- * device memory owned by the caller, 16-byte aligned, ZEROED ONCE after allocation (hipMemsetAsync); every call leaves it
- * zeroed again, so calls issued one after the other on ONE stream share one block -- two streams never do.  Inside:
+ * device memory owned by the caller, 16-byte aligned, ZEROED ONCE after allocation (hipMemsetAsync).  What a call relies on
+ * is the ticket counters -- the first 8320 bytes (65 counters, 128 bytes apart) -- and those every call leaves zeroed again,
+ * so calls issued one after the other on ONE stream share one block -- two streams never do.  The bytes behind the counters
+ * are scratch: the workgroup partials (16 KiB from byte 16384) and the group partials (1 KiB from byte 40960) keep what the
+ * last call wrote, no call reads them before it has written them, and the rest of the block is never written
+ * (tests/test_gpu_scratch_contracts.py).  Inside:
  * last-arriver tickets, one counter per group of workgroups (no more than 32 atomics ever queue on one address) and the
  * workgroup / group partials, folded in index order: results do not depend on which workgroup finishes last.
  *   antq_absmax_t     : *amax_dev = max_i |x[i]| over n elements, WRITTEN (not accumulated; amax_dev need not be
