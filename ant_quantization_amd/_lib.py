@@ -26,6 +26,7 @@ MAX_GRID = 1024
 LINEAR4_MAX_M = 8      # include/antq.h ANTQ_LINEAR4_MAX_M: input rows antq_linear4 takes
 LINEAR4_MM_MAX_M = 64  # include/antq.h ANTQ_LINEAR4_MM_MAX_M: input rows antq_linear4_mm takes
 LINEAR4_GEMM_MAX_M = 4096  # include/antq.h ANTQ_LINEAR4_GEMM_MAX_M: input rows antq_linear4_gemm takes
+LINEAR4_T_MAX_M = 8    # include/antq.h ANTQ_LINEAR4_T_MAX_M: input rows antq_linear4_t takes
 LINEAR8_MAX_M = 8      # include/antq.h ANTQ_LINEAR8_MAX_M: input rows antq_linear8 takes
 LINEAR8_MM_MAX_M = 64  # include/antq.h ANTQ_LINEAR8_MM_MAX_M: input rows antq_linear8_mm takes
 LINEAR8_GEMM_MAX_M = 4096  # include/antq.h ANTQ_LINEAR8_GEMM_MAX_M: input rows antq_linear8_gemm takes
@@ -67,7 +68,7 @@ def lib():
                              "antq_absmax_t", "antq_alpha_grad_t", "antq_calibrate_install", "antq_decode4_batch_build", "antq_decode4_batch",
                              "antq_linear4", "antq_linear4_mm", "antq_encode8", "antq_decode8", "antq_decode8_batch_build",
                              "antq_decode8_batch", "antq_linear8", "antq_linear8_mm", "antq_linear4_gemm",
-                             "antq_linear8_gemm"):
+                             "antq_linear8_gemm", "antq_linear4_t"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
                 L.antq_decode4_batch_capacity.restype = ctypes.c_size_t
@@ -93,6 +94,7 @@ def lib():
                 L.antq_linear8_mm.argtypes = L.antq_linear4.argtypes
                 L.antq_linear4_gemm.argtypes = L.antq_linear4.argtypes
                 L.antq_linear8_gemm.argtypes = L.antq_linear4.argtypes
+                L.antq_linear4_t.argtypes = L.antq_linear4.argtypes
                 # development: ANTQ_DEBUG_KNOBS="14=2,0=8" applies antq_debug_set(key, value) pairs to the loading thread
                 # (the knobs are thread-local; tools/fuzz_campaign.sh forces code paths with it)
                 for kv in [k for k in os.environ.get("ANTQ_DEBUG_KNOBS", "").split(",") if "=" in k]:
@@ -989,8 +991,10 @@ def decode8(codes, alpha, plan, gmax, rows, row_len, per_row, dtype, n_normal=0,
     return out.view(rows, row_len)
 
 
-def _linear4_call(entry, max_m, allow_f32, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out, per_byte=2):
-    """per_byte: codes a byte holds (2: the 4-bit layout, 1: byte codes)."""
+def _linear4_call(entry, max_m, allow_f32, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out, per_byte=2,
+                  scales=None):
+    """per_byte: codes a byte holds (2: the 4-bit layout, 1: byte codes); scales: entries alpha holds when per_row (None: N,
+    one per output row; linear4_t: K, one per row of the codes)."""
     _require_gpu(x, "x")
     _require_gpu(codes, "codes")
     _require_gpu(alpha, "alpha")
@@ -1005,7 +1009,7 @@ def _linear4_call(entry, max_m, allow_f32, codes, x, alpha, grid_dev, gmax, N, K
         raise AntqError("%s takes at most %d rows of x (got %d)" % (entry, max_m, M))
     if codes.dtype != torch.uint8 or codes.numel() * per_byte != N * K:
         raise AntqError("codes must be uint8 of N*K%s bytes" % ("/2" if per_byte == 2 else ""))
-    if alpha.dtype != torch.float32 or alpha.numel() < (N if per_row else 1) or grid_dev.dtype != torch.float32:
+    if alpha.dtype != torch.float32 or alpha.numel() < ((N if scales is None else scales) if per_row else 1) or grid_dev.dtype != torch.float32:
         raise AntqError("alpha must be float32, one per row (per_row) or one; grid_dev float32")
     if bias is not None:
         _require_gpu(bias, "bias")
@@ -1048,6 +1052,18 @@ def linear4_gemm(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_no
     LDS.  The order of the sum is this kernel's own, neither linear4's nor linear4_mm's: the same row has different low bits from
     the three.  A row's bits do not depend on the other rows or on their number."""
     return _linear4_call("antq_linear4_gemm", LINEAR4_GEMM_MAX_M, False, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
+
+
+def linear4_t(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):
+    """y = x . W (+ bias) straight from the packed 4-bit codes of W stored [K, N] (antq_linear4_t; GPT-2's Conv1D layout): N, K
+    are the logical output and input widths, the codes hold K rows of N elements, x is [..., K] with at most LINEAR4_T_MAX_M
+    rows.  W[k, n] is bit for bit the element decode4 writes in x's dtype, products and sum in fp32 in a fixed order that
+    depends on K alone (128 phases of k, one fixed tree: include/antq.h), so a row computed alone has the bits it has in a call
+    of 8.  alpha: float32, K scales (per_row: one per row k of the codes, i.e. per input feature) or one.  Returns [..., N].
+    Measured (profiles/packed_linear_t.md): faster than decode4 + addmm at M = 1 everywhere, faster than addmm on a kept image
+    only at M = 1 and not on every layer, slower at M >= 2."""
+    return _linear4_call("antq_linear4_t", LINEAR4_T_MAX_M, True, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out,
+                         scales=K)
 
 
 def linear8(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):

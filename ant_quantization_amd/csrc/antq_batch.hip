@@ -9,6 +9,7 @@
 #include "antq_k_linear8.h"
 #include "antq_k_linear_mm.h"
 #include "antq_k_linear_gemm.h"
+#include "antq_k_linear_t.h"
 
 #include <type_traits>
 
@@ -439,17 +440,18 @@ extern "C" int antq_decode8_batch(const void *batch_host, const void *batch_dev,
 //   max_m       the most rows of x            no_f32      f32 is refused as unsupported, after the empty call
 //   book_ok     the code width's book rule    code_align  bytes the codes are aligned to
 //   esz         bytes y and bias are aligned to
+//   n_mult      what N must be a multiple of (antq_linear4_t: 8, a whole code word per row of codes)
 constexpr int kLinearGo = 1;
 static int linear_checks(const uint8_t *codes, const void *x, const void *bias, const void *y, size_t M, size_t N, size_t K,
                          const float *alpha, const float *grid, int m, int n_normal, unsigned flags, int dtype, size_t max_m,
-                         bool no_f32, bool (*book_ok)(int, int, bool), uintptr_t code_align, uintptr_t esz)
+                         bool no_f32, bool (*book_ok)(int, int, bool), uintptr_t code_align, uintptr_t esz, size_t n_mult = 1)
 {
     if (!codes || !x || !y || !alpha || !grid || m < 1) return ANTQ_ERR_ARG;
     if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_ARG;
     if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
     if (M == 0 || N == 0) return ANTQ_OK;
     if (no_f32 && dtype == ANTQ_F32) return ANTQ_ERR_UNSUPPORTED;
-    if (M > max_m || K == 0 || K % 8 != 0) return ANTQ_ERR_UNSUPPORTED;
+    if (M > max_m || K == 0 || K % 8 != 0 || N % n_mult != 0) return ANTQ_ERR_UNSUPPORTED;
     if (!book_ok(m, n_normal, (flags & ANTQ_FLAG_OVP) != 0)) return ANTQ_ERR_UNSUPPORTED;
     if (N > 0x7fffffffull || K > 0x7ffffff8ull) return ANTQ_ERR_UNSUPPORTED;      // (rows and row length in 32 bits)
     if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(codes) % code_align || reinterpret_cast<uintptr_t>(y) % esz ||
@@ -547,6 +549,27 @@ static int launch_linear_gemm(const uint8_t *codes, const void *x, const void *b
     });
 }
 
+// The launch of the [K, N] linear (antq_k_linear_t.h) for 1 .. 8 rows of x: one workgroup per 64 output columns.
+static int launch_linear_t(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
+                           const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal, bool ovp, int dtype,
+                           void *stream)
+{
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int mt = M <= 2 ? (int)M : (M <= 4 ? 4 : 8);           // rows the kernel computes: 3 runs as 4, 5 .. 7 as 8
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return with_bool(ovp, [&](auto o) {
+            return with_value<1, 2, 4, 8>(mt, [&](auto mm) {
+                const unsigned blocks = (unsigned)((N + kLinTCols - 1) / kLinTCols);
+                launch_k(false, k_linear_t<T, decltype(o)::value, decltype(mm)::value>, dim3(blocks), dim3(64u * kLinTWaves), 0, st,
+                         codes, x, bias, y, (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha, per_row ? 1 : 0, gmax, grid, (uint32_t)m,
+                         ovp ? n_normal : 0);
+                return launch_status();
+            });
+        });
+    });
+}
+
 // y = x . W^T (+ bias) for 1 .. ANTQ_LINEAR4_MAX_M rows of x from the packed codes of W (antq_k_linear4.h).
 extern "C" int antq_linear4(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
                             const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
@@ -557,6 +580,18 @@ extern "C" int antq_linear4(const uint8_t *codes, const void *x, const void *bia
     if (rc != kLinearGo) return rc;
     return launch_linear<Lin4Codec>(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0,
                                     dtype, stream);
+}
+
+// y = x . W (+ bias) for 1 .. ANTQ_LINEAR4_T_MAX_M rows of x from the packed codes of W stored [K, N] (antq_k_linear_t.h).
+extern "C" int antq_linear4_t(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
+                              const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
+                              unsigned flags, int dtype, void *stream)
+{
+    const int rc = linear_checks(codes, x, bias, y, M, N, K, alpha, grid, m, n_normal, flags, dtype, ANTQ_LINEAR4_T_MAX_M, false,
+                                 dec4_book_ok, 4, dtype == ANTQ_F32 ? 4 : 2, 8);
+    if (rc != kLinearGo) return rc;
+    return launch_linear_t(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0, dtype,
+                           stream);
 }
 
 // The same product for 1 .. ANTQ_LINEAR4_MM_MAX_M rows of x on the matrix cores (antq_k_linear_mm.h; bf16 / f16).

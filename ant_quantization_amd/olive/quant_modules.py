@@ -478,6 +478,9 @@ class Conv1dQuantizer(nn.Module):
             self.quant_input.prefetch_sign(input)          # (first call: its sign is on its way while the weight calibrates)
         weight = self.quant_weight(self.weight, input)
         input = self.quant_input(input, self.weight)
+        bank = self.quant_weight._bank
+        if bank is not None and bank.fused_linear:         # packed.pack_model(fused_linear=True, fused_conv1d=True): few rows run from the codes
+            return bank.linear(self, input, weight)
         return self._conv_forward(input, weight)
 
 

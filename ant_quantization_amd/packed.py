@@ -149,6 +149,36 @@ With the plain book the launcher's shared tile rule chose 256 rows per workgroup
 bytes) and the free scratch buffer, at those prices.  Not measured: other M, the 8-byte code path, per-tensor scales, a whole
 model's forward, more than one run; no hardware counters.  Not built: one decode of a B fragment shared by the workgroup's
 wavefronts.
+
+`fused_conv1d=True` (with fused_linear, else AntqError; off by default -- without it everything above is unchanged) is for GPT-2,
+whose projections are all HF `Conv1D` layers behind OliVe's `Conv1dQuantizer`: weight [in, out] = [K, N], y = x @ W + b, one scale
+per INPUT feature k, the pairs of the pair rule adjacent output columns.  Such a layer is packed with or without the option (the
+codec does not care about orientation), but no other kernel can sum across the rows of its codes: without the option it always
+keeps its decoded image, also under `keep_images=False`, and runs its `addmm` on it.  With the option a 4-bit entry whose module is
+a Conv1dQuantizer with a 2-D weight, `w.shape[1] == nf` and `w.shape[0] % 8 == 0` is fusable with kind `conv1d`: its no-grad calls
+of at most `_lib.LINEAR4_T_MAX_M` = 8 rows, under the input conditions of the 4-bit path, run `antq_linear4_t` -- the product from
+the codes, W[k, n] bit for bit the image `antq_decode4` writes, the sum in fp32 in the kernel's own fixed order, a function of K
+alone (`.fused_t_calls` counts them).  Every other call runs the layer's own `addmm` (`_conv_forward`, so the bits are today's) on
+the image or, with `keep_images=False`, on the scratch decode; the scratch's lifetime rule is the same.  `fused_rows` and
+`fused_gemm_rows` do not apply to `conv1d` entries (there is no matrix-core form for this layout); byte-coded Conv1D entries keep
+their image as byte entries did before `fused_bytes`.  `release_weights` and the "float weight is gone" error behave as for Linear
+entries.
+Measured (profiles/packed_linear_t.md; one MI355X, one run, 5 repetitions of graph-replayed calls per point -- 200 ... 1200 per
+graph, each arm rotating over more than 256 MiB of distinct weights where 1200 calls reach that -- with the arms alternated,
+medians, spread below 4.3 %; M = 1 / 2 / 4 / 8, GPT-2 small's and GPT-2 XL's four Conv1D shapes [K, N], bf16 / f16 / fp32, ANT
+flint-4 and OliVe flint with the pair rule, one scale per k; A = addmm on the kept image, C = antq_decode4 into scratch + addmm,
+B = antq_linear4_t; 192 points).  Against C, the path `keep_images=False` would otherwise take: B wins at all 48 points of M = 1
+(1.02 ... 2.26x), at 40 of 48 at M = 2 (0.73 ... 1.89x), 32 of 48 at M = 4 (0.59 ... 1.92x) and 21 of 48 at M = 8 (0.52 ... 1.56x);
+it loses on the long-K layers [3072, 768] and [6400, 1600] in f16 / bf16 from M = 2 on.  Against A: B wins only at M = 1 -- at 30
+of 48 points, 0.72 ... 1.28x: on GPT-2 XL's [1600, 4800], [1600, 1600] and [1600, 6400] in every run (1.03 ... 1.19x) and in fp32 on
+every layer (1.06 ... 1.28x) -- and LOSES at every point of M = 2 (0.48 ... 1.00x), M = 4 (0.38 ... 0.93x) and M = 8 (0.34 ... 0.76x).
+The codes stream at 0.2 ... 4.5 % of 8 TB/s: the kernel is nowhere near a stream.  Its time follows K, not N -- it is bound by
+each lane's chain of dependent steps and by 10 ... 20 instructions per weight (every pair is scaled and rounded per use), with
+24 ... 200 workgroups on 256 CUs; inferred from the scaling and the ISA, no hardware counters were collected.  The tile is half
+the first one built (64 columns, 64 phases), which was 1.06 ... 1.66x slower at M >= 4 and K >= 3072 and 8 ... 16 % faster at M = 1
+with K = 768.  So the option buys a GPT-2 the memory (no decoded image: a quarter of the bf16 bytes) and, at batch 1, roughly the
+speed of the image; with kept images it is not worth turning on beyond one row.  Not measured: other M, per-tensor scales,
+K > 8192, a whole model's decode step, more than one run, smaller tiles or a tile chosen by N.
 """
 import torch
 import torch.nn.functional as F
@@ -179,7 +209,8 @@ def _settle(q):
 
 class PackedBank:
     def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True, fused_rows=None,
-                 byte_codes=False, fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None):
+                 byte_codes=False, fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None,
+                 fused_conv1d=False):
         """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict);
         a layer's code width is then the one its stored size says (numel / 2 bytes: 4-bit, numel bytes: byte codes).
         byte_codes: layers the 4-bit codec refuses and the byte codec accepts are packed one code per byte (width 8).
@@ -187,8 +218,14 @@ class PackedBank:
         fused_byte_rows=R (with fused_linear and fused_bytes): their bf16 / f16 calls of 9 .. R rows too (antq_linear8_mm).
         fused_gemm_rows=R (with fused_linear): bf16 / f16 calls of the 4-bit layers with more rows than the other kernels take
         and at most R rows run antq_linear4_gemm.
-        fused_byte_gemm_rows=R (with fused_linear and fused_bytes): the same for the byte-coded layers (antq_linear8_gemm)."""
+        fused_byte_gemm_rows=R (with fused_linear and fused_bytes): the same for the byte-coded layers (antq_linear8_gemm).
+        fused_conv1d (with fused_linear): 4-bit Conv1dQuantizer layers (weight [K, N]) of K % 8 == 0 compute calls of at most
+        _lib.LINEAR4_T_MAX_M rows from their codes (antq_linear4_t); fused_rows / fused_gemm_rows do not apply to them."""
         self.byte_codes = bool(byte_codes)
+        if fused_conv1d and not fused_linear:
+            raise _lib.AntqError("PackedBank: fused_conv1d needs fused_linear=True")
+        self.fused_conv1d = bool(fused_conv1d)   # 4-bit Conv1D layers ([K, N] weights) with few input rows compute from the codes (antq_linear4_t)
+        self.fused_t_calls = 0     # forwards antq_linear4_t served
         if fused_bytes and not fused_linear:
             raise _lib.AntqError("PackedBank: fused_bytes needs fused_linear=True")
         _check_fused_byte_rows("PackedBank", fused_linear, fused_bytes, fused_byte_rows)
@@ -250,9 +287,13 @@ class PackedBank:
                 # (byte codes: only with fused_bytes -- without it a byte-coded layer always keeps its image)
                 fusable = ((width == 4 or self.fused_bytes) and self.fused_linear and w.dim() == 2
                            and getattr(mod, "in_features", None) == w.shape[1] and w.shape[1] % 8 == 0)
+                kind = "linear"
+                if (self.fused_conv1d and width == 4 and _is_conv1d(mod) and w.dim() == 2 and getattr(mod, "nf", None) == w.shape[1]
+                        and w.shape[0] % 8 == 0):
+                    fusable, kind = True, "conv1d"     # weight [K, N]: the codes' rows are k (antq_linear4_t)
                 image = self.keep_images or not fusable
                 self.entries[id(q)] = dict(name=name, q=q, mod=mod, rows=rows, row_len=row_len, per_row=per_row, codes=c, width=width,
-                                           fusable=fusable, shape=tuple(w.shape), dtype=w.dtype, device=w.device,
+                                           fusable=fusable, kind=kind, shape=tuple(w.shape), dtype=w.dtype, device=w.device,
                                            out=torch.empty_like(w, memory_format=torch.contiguous_format) if image else None)
             if not self.entries:
                 raise _lib.AntqError("PackedBank: no weight quantiser to pack (run one forward to calibrate first): %r" % (self.skipped,))
@@ -432,9 +473,19 @@ class PackedBank:
         dec(e["codes"], e["alpha"], plan, gmax, e["rows"], e["row_len"], e["per_row"], e["dtype"], n_normal=n_normal, ovp=ovp, out=buf)
         return buf.view(e["shape"])
 
+    def _fits(self, e, input, bias, K, max_rows):
+        """Whether a call may run from the codes: a contiguous, 16-byte-aligned no-grad input [..., K] of at most max_rows rows
+        in the layer's dtype on its device, the bias (if any) alike."""
+        return (input.is_cuda and input.dtype == e["dtype"] and input.device == e["device"] and input.dim() >= 1 and input.shape[-1] == K
+                and 0 < input.numel() <= max_rows * K and input.is_contiguous() and input.data_ptr() % 16 == 0
+                and not (torch.is_grad_enabled() and (input.requires_grad or (bias is not None and bias.requires_grad)))
+                and (bias is None or (bias.dtype == input.dtype and bias.is_contiguous() and bias.device == input.device)))
+
     def linear(self, mod, input, weight):
-        """The output of a LinearQuantizer whose weight quantiser this bank serves (fused_linear): `input` after quant_input,
-        `weight` what quant_weight returned.  From the codes when the call qualifies, F.linear on the image otherwise."""
+        """The output of a LinearQuantizer or Conv1dQuantizer whose weight quantiser this bank serves (fused_linear): `input`
+        after quant_input, `weight` what quant_weight returned.  From the codes when the call qualifies, otherwise the layer's
+        own product on the image: F.linear, or a Conv1dQuantizer's addmm (`_conv_forward`)."""
+        conv = _is_conv1d(mod)
         q = mod.quant_weight
         e = self.entries.get(id(q))
         if e is not None and e["out"] is None:     # (lookup()'s own conditions again: a mark left by a call that failed is stale)
@@ -446,9 +497,17 @@ class PackedBank:
                 raise _lib.AntqError("layer %s was packed with keep_images=False and release_weights=True: its float weight is "
                                      "gone, so it cannot run with its quantiser disabled or re-calibrating (only from its "
                                      "codes)" % e["name"])
-            return F.linear(input, weight, mod.bias)
-        K = e["shape"][1]
+            return mod._conv_forward(input, weight) if conv else F.linear(input, weight, mod.bias)
         bias = mod.bias
+        if e["kind"] == "conv1d":                  # weight [K, N]; fused_rows / fused_gemm_rows do not apply
+            K, N = e["shape"]
+            if self._fits(e, input, bias, K, _lib.LINEAR4_T_MAX_M):
+                plan, gmax, n_normal, ovp = _codebook(e["q"])
+                self.fused_t_calls += 1
+                return _lib.linear4_t(e["codes"], input, e["alpha"], plan.grid_dev(e["device"]), gmax, N, K, e["per_row"],
+                                      bias=None if bias is None else bias.detach(), n_normal=n_normal, ovp=ovp)
+            return mod._conv_forward(input, weight if e["out"] is not None else self._image(e))
+        K = e["shape"][1]
         byte = e["width"] == 8                     # (fused_rows is antq_linear4_mm's, fused_byte_rows antq_linear8_mm's)
         max_rows = _lib.LINEAR8_MAX_M if byte else _lib.LINEAR4_MAX_M
         more_rows = self.fused_byte_rows if byte else self.fused_rows
@@ -458,11 +517,7 @@ class PackedBank:
                 max_rows = more_rows
             if gemm_rows is not None:
                 max_rows = gemm_rows               # (> LINEAR4_MM_MAX_M = LINEAR8_MM_MAX_M >= fused_rows, fused_byte_rows)
-        if (input.is_cuda and input.dtype == e["dtype"] and input.device == e["device"] and input.dim() >= 1 and input.shape[-1] == K
-                and 0 < input.numel() <= max_rows * K and input.is_contiguous() and input.data_ptr() % 16 == 0
-                and not (byte and e["codes"].data_ptr() % 8)
-                and not (torch.is_grad_enabled() and (input.requires_grad or (bias is not None and bias.requires_grad)))
-                and (bias is None or (bias.dtype == input.dtype and bias.is_contiguous() and bias.device == input.device))):
+        if self._fits(e, input, bias, K, max_rows) and not (byte and e["codes"].data_ptr() % 8):
             plan, gmax, n_normal, ovp = _codebook(e["q"])
             if byte and input.numel() <= _lib.LINEAR8_MAX_M * K:
                 self.fused_byte_calls += 1
@@ -517,6 +572,12 @@ def _check_fused_byte_gemm_rows(who, fused_linear, fused_bytes, fused_byte_gemm_
                        _lib.LINEAR8_MM_MAX_M, _lib.LINEAR8_GEMM_MAX_M)
 
 
+def _is_conv1d(mod):
+    """Whether `mod` is OliVe's Conv1dQuantizer (GPT-2's Conv1D: weight [in, out], y = x @ W + b)."""
+    from .olive.quant_modules import Conv1dQuantizer       # (here: that module is loaded by whoever built such a layer)
+    return isinstance(mod, Conv1dQuantizer)
+
+
 def _no_auto_bank(model):
     """The automatic weight bank steps aside (as for set_weights_at_rest(resident=False)), and the choice stays with the
     module: a deep copy carries the mark, so its forward hook does not arm a fresh AutoBank for it."""
@@ -534,7 +595,7 @@ def _bank_of(model):
 
 
 def pack_model(model, release_weights=False, fused_linear=False, keep_images=True, fused_rows=None, byte_codes=False,
-               fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None):
+               fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None, fused_conv1d=False):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
     (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
     byte_codes: layers the 4-bit codec refuses for their codebook (5- to 8-bit layers, OliVe's unsigned 16 + 15) or their row
@@ -580,10 +641,14 @@ def pack_model(model, release_weights=False, fused_linear=False, keep_images=Tru
     OliVe int-8): B loses to C and to A at all 120 points (C / B 0.17 ... 0.78, best on [16384, 4096] at M = 64 ... 256; A / B
     0.09 ... 0.46), so no R is worth choosing for speed; the option buys the memory and a model without scratch decodes.  Give
     fused_byte_rows=64 beside it (at M = 64 B takes 2.8 ... 6.1 times antq_linear8_mm's time).  Not measured: other M, the 8-byte
-    code path, per-tensor scales, a whole model."""
+    code path, per-tensor scales, a whole model.
+    fused_conv1d (with fused_linear, else AntqError): the 4-bit Conv1dQuantizer layers of a GPT-2 (weight [K, N] with N = nf and
+    K % 8 == 0) compute calls of at most _lib.LINEAR4_T_MAX_M rows from their codes (antq_linear4_t, .fused_t_calls) and, with
+    keep_images=False, keep no image; calls of more rows run the layer's addmm on the image or on the scratch decode.
+    fused_rows / fused_gemm_rows do not apply to them.  Measurements: see the module docstring (profiles/packed_linear_t.md)."""
     return PackedBank(model, release_weights=release_weights, fused_linear=fused_linear, keep_images=keep_images, fused_rows=fused_rows,
                       byte_codes=byte_codes, fused_bytes=fused_bytes, fused_byte_rows=fused_byte_rows, fused_gemm_rows=fused_gemm_rows,
-                      fused_byte_gemm_rows=fused_byte_gemm_rows)
+                      fused_byte_gemm_rows=fused_byte_gemm_rows, fused_conv1d=fused_conv1d)
 
 
 def packed_state_dict(model):
@@ -605,12 +670,12 @@ def _packed_keys(sd, codes):
 
 
 def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, keep_images=True, fused_rows=None,
-                           fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None):
+                           fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None, fused_conv1d=False):
     """Load a packed checkpoint into a freshly wrapped, uncalibrated model living on the GPU: the quantiser state is
     installed the way load_ant_state_dict + load_state_dict do (scales keep the dtype they were stored with), a PackedBank is attached from the stored codes without
     re-encoding (a layer's code width is the one its stored size says: numel / 2 bytes are 4-bit codes, numel bytes byte codes;
     any other size raises AntqError naming the layer), and the weights are materialised by the batched decode
-    (release_weights=False: copied into the layers' own float weights instead of replacing them).  fused_linear / keep_images / fused_rows / fused_bytes / fused_byte_rows / fused_gemm_rows / fused_byte_gemm_rows: as in pack_model (the code width still comes from the stored size).  Returns the bank."""
+    (release_weights=False: copied into the layers' own float weights instead of replacing them).  fused_linear / keep_images / fused_rows / fused_bytes / fused_byte_rows / fused_gemm_rows / fused_byte_gemm_rows / fused_conv1d: as in pack_model (the code width still comes from the stored size).  Returns the bank."""
     if not keep_images and not fused_linear:
         raise _lib.AntqError("load_packed_state_dict: keep_images=False needs fused_linear=True")
     _check_fused_rows("load_packed_state_dict", fused_linear, fused_rows)
@@ -619,6 +684,8 @@ def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, 
     _check_fused_byte_rows("load_packed_state_dict", fused_linear, fused_bytes, fused_byte_rows)
     _check_fused_gemm_rows("load_packed_state_dict", fused_linear, fused_gemm_rows)
     _check_fused_byte_gemm_rows("load_packed_state_dict", fused_linear, fused_bytes, fused_byte_gemm_rows)
+    if fused_conv1d and not fused_linear:
+        raise _lib.AntqError("load_packed_state_dict: fused_conv1d needs fused_linear=True")
     suffix = "." + CODES_KEY
     codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}
     rest = {k: v for k, v in sd.items() if not k.endswith(suffix)}
@@ -638,7 +705,7 @@ def load_packed_state_dict(model, sd, release_weights=True, fused_linear=False, 
         _settle(q)
     bank = PackedBank(model, release_weights=release_weights, codes=codes, fused_linear=fused_linear, keep_images=keep_images,
                       fused_rows=fused_rows, fused_bytes=fused_bytes, fused_byte_rows=fused_byte_rows, fused_gemm_rows=fused_gemm_rows,
-                      fused_byte_gemm_rows=fused_byte_gemm_rows)
+                      fused_byte_gemm_rows=fused_byte_gemm_rows, fused_conv1d=fused_conv1d)
     if not release_weights:
         with torch.no_grad():
             for e in bank.entries.values():

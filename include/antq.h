@@ -47,7 +47,7 @@ extern "C" {
  * and antq_linear4_mm (its matrix-core form for up to 64 rows), and antq_encode8 / antq_decode8 / antq_decode8_batch_capacity /
  * antq_decode8_batch_build / antq_decode8_batch (the byte-code codec), and antq_linear8 (the linear from byte codes), and
  * antq_linear8_mm (its matrix-core form for up to 64 rows), and antq_linear4_gemm (the tiled 4-bit form for up to 4096 rows),
- * and antq_linear8_gemm (the same from byte codes).
+ * and antq_linear8_gemm (the same from byte codes), and antq_linear4_t (the 4-bit linear for weights stored [K, N]).
  * A caller built against another version must not call in: the blobs / argument lists differ. */
 #define ANTQ_ABI_VERSION 7
 
@@ -561,6 +561,45 @@ int antq_linear4(const uint8_t *codes_dev,          /* N*K/2 bytes, antq_encode4
                  const float *alpha_dev, int alpha_per_row, float gmax,
                  const float *grid_dev, int m, int n_normal,   /* as in antq_decode_job */
                  unsigned flags /* 0 | ANTQ_FLAG_OVP */, int dtype /* F32 | BF16 | F16 */, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Packed 4-bit linear for weights stored [K, N] (GPT-2's Conv1D: weight [in, out], y = x @ W + b): y = x . W (+ bias) for
+ * 1 .. ANTQ_LINEAR4_T_MAX_M rows of x, computed straight from the codes of W.  codes: K rows of N codes in antq_encode4's
+ * layout (N / 2 bytes per row, element 2 j in the low nibble: OliVe's pairs are adjacent output columns); alpha_per_row: one
+ * scale per row k of the codes, that is per INPUT feature; gmax / grid / m / n_normal / flags as in antq_linear4.
+ *   W[k,n] is, bit for bit, the element antq_decode4 writes for the same codes, alpha, gmax, grid, flags and dtype: the
+ *          decoder's own pair, scaled by alpha[k] / gmax (a true division) and rounded to `dtype` -- the scale is never
+ *          factored out of the sum or folded into x.
+ *   y[m,n] = round_dtype( sum_k x[m,k] * W[k,n] + bias[n] ), products and sum accumulated in fp32 (fused multiply-adds).
+ *   The tile rule, a function of K alone: partial sum P (0 .. 127) takes k = P, P + 128, ... < K in rising order from +0; the
+ *          128 partial sums are combined in one fixed tree -- the 16 of a wavefront (P = 16 w + p) as four groups of four, each
+ *          (p0 + p2) + (p1 + p3), the groups as (g0 + g1) + (g2 + g3), then the eight wavefronts' sums as
+ *          ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7)) -- then the bias is added in fp32 and the result rounded once.
+ *          A workgroup owns 32 consecutive output columns over the whole of K.  The bits of y[m,n] depend only on row m of
+ *          x, column n of W, bias[n] and K: not on M, not on N, not on the other rows of x, not on the run.
+ *   No floating-point atomics, no split of K across workgroups, no workspace, no allocation, no synchronisation:
+ *          stream-ordered and capturable into a graph.  Reads stay inside the buffers: a step past the end of K and a column
+ *          group past the end of N load nothing and add nothing (never a zero x against a repeated weight); padded rows of x
+ *          repeat the last real row and are not stored.  The accumulators start at +0.
+ *   Non-finite values follow IEEE 754 per product and per sum, as for antq_linear4.  With a scale per k, a NaN or Inf
+ *          alpha[k] makes ROW k of W non-finite: it reaches every y[m, .], also where x[m,k] == 0 (0 * Inf is NaN), exactly
+ *          as a product with the decoded image does.  A non-finite x[m,k] reaches row m of y only.
+ * Checked before anything touches HIP, in this order:
+ *   ANTQ_ERR_ARG          a null codes / x / y / alpha / grid, m < 1, a bad dtype, a flag bit other than ANTQ_FLAG_OVP
+ *   ANTQ_OK, no launch    M == 0 or N == 0
+ *   ANTQ_ERR_UNSUPPORTED  M > ANTQ_LINEAR4_T_MAX_M; K == 0 or K % 8 != 0; N % 8 != 0; the decoder's refusals (as antq_linear4);
+ *                         N >= 2^31 or K >= 2^31
+ *   ANTQ_ERR_ALIGN        x_dev not 16-byte aligned, codes_dev not 4-byte aligned, y_dev / bias_dev not aligned to their element
+ * F32 / BF16 / F16.  The scales are staged in LDS up to K = 8192 and divided per step beyond (the same bits).  Measured
+ * (profiles/packed_linear_t.md; one MI355X, one run, GPT-2 small's and XL's Conv1D shapes, M = 1 / 2 / 4 / 8): faster than
+ * antq_decode4 + addmm at every point of M = 1 (1.02 ... 2.26x) and at 21 ... 40 of 48 points beyond; faster than addmm on a
+ * decoded image only at M = 1 (30 of 48 points, 0.72 ... 1.28x), slower at every point of M >= 2 (0.34 ... 1.00x); the codes
+ * stream at 0.2 ... 4.5 % of 8 TB/s (the kernel is bound by latency and instruction count, not bandwidth).
+ * ------------------------------------------------------------------------- */
+#define ANTQ_LINEAR4_T_MAX_M 8
+int antq_linear4_t(const uint8_t *codes_dev /* K*N/2 bytes */, const void *x_dev /* [M, K] */, const void *bias_dev /* N or NULL */,
+                   void *y_dev /* [M, N] */, size_t M, size_t N, size_t K, const float *alpha_dev, int alpha_per_row, float gmax,
+                   const float *grid_dev, int m, int n_normal, unsigned flags, int dtype, void *stream);
 
 /* ---------------------------------------------------------------------------
  * The same product for 1 .. ANTQ_LINEAR4_MM_MAX_M rows of x on the matrix cores (v_mfma_f32_16x16x32_bf16 / _f16), BF16 and
