@@ -2,7 +2,9 @@
 y = x . W (+ bias) from the code bytes, W being the image antq_decode4 writes for K rows of N codes with one scale per row k.
 The yardstick is that of tests/test_gpu_linear4.py -- include/antq.h's decode rule restated in numpy on the code bytes, and a
 float64 product x64 @ W -- with the rows of the codes being k.  Exact tests compare bits; the general test holds the result
-to the bound of an fp32 sum.
+to the bound of an fp32 sum; the order of the sum that include/antq.h fixes (the tile rule) is held bit for bit against its
+restatement in numpy (tests/linear_t_cases.py, proved on the CPU by tests/test_linear_t_cases_host.py), up to K = 8200 where
+the scales are no longer staged in LDS.
 
 Shapes: the kernel's tile rule has two switch points only -- 128 phases of k (K = 8 ... 72 stay inside a partial pass, 128 is
 exactly one pass, 136 one pass plus a partial one, 520 and 1600 are several passes -- at 1600 more than one group of steps in
@@ -15,12 +17,12 @@ import types
 import numpy as np
 import pytest
 
-from conftest import golden
+import linear_t_cases as lt
+from linear_t_cases import DTYPES, PREC
+from linear_t_cases import books as _books, book as _book, round_bits as _round, value as _value, image_bits as _image_bits
+from linear_t_cases import random_codes as _random_codes
 
 pytestmark = pytest.mark.gpu
-
-DTYPES = ("float32", "bfloat16", "float16")
-PREC = {"float32": 23, "float16": 10, "bfloat16": 7}
 
 
 @pytest.fixture(scope="module")
@@ -29,68 +31,6 @@ def dev():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     return torch.device("cuda:0")
-
-
-def _books():
-    """(name, grid as the kernel takes it, gmax, n_normal, pair rule)"""
-    G, O = golden("ant_grids.npz"), golden("olive_grids.npz")
-    out = [(k, np.ascontiguousarray(G[k], np.float32), float(G[k].max()), 0, False)
-           for k in ("flint_b4_s", "int_b4_s", "pot_b4_s", "flint_b4_u", "int_b3_u")]
-    for t in ("flint", "int"):
-        gn, go = O["%s_b4_s" % t], O["outlier_b4_s"]
-        out.append(("olive_" + t, np.ascontiguousarray(np.concatenate([gn, go]), np.float32), float(gn.max()), int(gn.size), True))
-    return out
-
-
-def _book(name):
-    return [b for b in _books() if b[0] == name][0]
-
-
-def _round(v, dtype_name):
-    """fp32 -> the output type's bits, round to nearest even"""
-    v = np.ascontiguousarray(v, np.float32)
-    if dtype_name == "float32":
-        return v.view(np.uint32)
-    if dtype_name == "float16":
-        with np.errstate(all="ignore"):
-            return v.astype(np.float16).view(np.uint16)
-    u = v.view(np.uint32).astype(np.uint64)
-    return ((u + 0x7fff + ((u >> 16) & 1)) >> 16).astype(np.uint16)
-
-
-def _value(bits, dtype_name):
-    """the output type's bits -> float64"""
-    if dtype_name == "float32":
-        return bits.view(np.float32).astype(np.float64)
-    if dtype_name == "float16":
-        return bits.view(np.float16).astype(np.float64)
-    return (bits.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
-
-
-def _yardstick(codes, alpha, rows, row_len, per_row, g, gmax, n_normal, ovp, dtype_name):
-    """include/antq.h restated on the code bytes: element 2j in the low nibble; with the pair rule nibble 15 -> 0 and its
-    partner read from the outlier list; value = fl((g[c] + 0) * (alpha / gmax)) rounded to the output type.  Returns bits."""
-    gp = np.zeros(48, np.float32)
-    gp[:g.size] = g
-    gp = gp + np.float32(0)
-    b = np.asarray(codes, np.uint8).reshape(-1).astype(np.int64)
-    c0, c1 = b & 15, b >> 4
-    if ovp:
-        q0 = np.where(c0 == 15, np.float32(0), np.where(c1 == 15, gp[n_normal + c0], gp[c0]))
-        q1 = np.where(c1 == 15, np.float32(0), np.where(c0 == 15, gp[n_normal + c1], gp[c1]))
-    else:
-        q0, q1 = gp[c0], gp[c1]
-    q = np.stack([q0, q1], 1).astype(np.float32).reshape(rows, row_len)
-    with np.errstate(all="ignore"):
-        s = (np.asarray(alpha, np.float32).reshape(-1) / np.float32(gmax)).astype(np.float32)
-        v = (q * (s.reshape(rows, 1) if per_row else s[0])).astype(np.float32)
-    return _round(v, dtype_name).reshape(rows, row_len)
-
-
-def _image_bits(codes, alpha, K, N, per_row, book, dtype_name):
-    """the yardstick's image of K rows of N codes as [K, N] bits"""
-    name, g, gmax, nn, ovp = book
-    return _yardstick(codes, alpha, K if per_row else 1, N if per_row else K * N, per_row, g, gmax, nn, ovp, dtype_name).reshape(K, N)
 
 
 def _bits(t):
@@ -107,13 +47,6 @@ def _tensor(bits, dtype_name, dev):
     if dtype_name == "float32":
         return torch.from_numpy(np.ascontiguousarray(bits).view(np.float32)).to(dev)
     return torch.from_numpy(np.ascontiguousarray(bits).view(np.int16)).to(dev).view(dt)
-
-
-def _random_codes(rng, n_bytes, ovp):
-    c = rng.integers(0, 256, n_bytes, dtype=np.uint8)
-    if ovp:
-        c[rng.random(n_bytes) < 0.02] = 0xFF
-    return c
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -166,44 +99,6 @@ EXACT_K = (8, 64, 72, 128, 136, 520, 1600)
 EXACT_N = (8, 16, 32, 40, 56, 64, 72, 136)
 
 
-def _lowest_bit_exponent(t):
-    """exponent of the lowest set bit of every nonzero float64 in t"""
-    m, e = np.frexp(t[t != 0])
-    mi = np.round(np.abs(m) * 2.0 ** 53).astype(np.int64)
-    low = mi & -mi
-    return e - 53 + np.round(np.log2(low.astype(np.float64))).astype(np.int64)
-
-
-def _exact_case(rng, K, book, dtype_name, per_row, N=max(EXACT_N)):
-    """Codes [K, N], power-of-two scales and small-integer x (8 rows) for which every product and every partial sum, in any
-    order, is an integer below 2^24 in units of one power of two -- asserted here in float64 -- with the exact result.  A
-    prefix of the columns is a narrower layer with the same property."""
-    name, g, gmax, nn, ovp = book
-    codes = _random_codes(rng, K * N // 2, ovp)
-    j = rng.integers(-2, 2, K if per_row else 1)
-    alpha = (np.float32(gmax) * np.exp2(j).astype(np.float32)).astype(np.float32)        # alpha / gmax = 2^j exactly
-    assert np.array_equal((alpha / np.float32(gmax)).astype(np.float32), np.exp2(j).astype(np.float32))
-    W = _value(_image_bits(codes, alpha, K, N, per_row, book, dtype_name), dtype_name)    # [K, N]
-    bias = rng.integers(-8, 9, N).astype(np.float64)
-    density = 1.0
-    while True:
-        x = rng.integers(-3, 4, (8, K)).astype(np.float64) * (rng.random((8, K)) < density)
-        x[:, 0] = np.where(x[:, 0] == 0, 1.0, x[:, 0])
-        terms = x[:, :, None] * W[None, :, :]                          # [8, K, N]
-        nz = np.abs(terms[terms != 0])
-        unit = 2.0 ** min(int(_lowest_bit_exponent(terms).min()), 0)   # (the bias: whole numbers)
-        mass = (np.abs(terms).sum(1) + np.abs(bias)[None, :]) / unit
-        if mass.max() < 2.0 ** 24:
-            break
-        density *= 0.5
-    # the premise, in float64: every term a whole multiple of the unit, and the sum of magnitudes below 2^24 units -- a
-    # fortiori below 2^24 in units of the smallest nonzero |term|
-    assert np.array_equal(terms / unit, np.round(terms / unit)) and mass.max() < 2.0 ** 24
-    assert ((np.abs(terms).sum(1) + np.abs(bias)[None, :]) / nz.min()).max() < 2.0 ** 24
-    y = terms.sum(1)                                                    # exact in float64: < 2^24 units
-    return codes, alpha, x, bias, y, density
-
-
 @pytest.mark.parametrize("dtype_name", DTYPES)
 def test_exact_sums(antq_lib, dev, dtype_name):
     """Dyadic codebooks, power-of-two scales (per row k, and per tensor), small-integer activations: whatever the order of
@@ -219,7 +114,7 @@ def test_exact_sums(antq_lib, dev, dtype_name):
         for ki, K in enumerate(EXACT_K):
             per_row = ki % 2 == 0 or ovp
             NW = max(EXACT_N)
-            codes_np, a_np, x_np, b_np, y_np, density = _exact_case(rng, K, book, dtype_name, per_row)
+            codes_np, a_np, x_np, b_np, y_np, density = lt.exact_case(rng, K, book, dtype_name, per_row, max(EXACT_N))
             x = _tensor(_round(x_np.astype(np.float32), dtype_name), dtype_name, dev)
             bias = _tensor(_round(b_np.astype(np.float32), dtype_name), dtype_name, dev)
             a = torch.from_numpy(a_np).to(dev)
@@ -322,9 +217,7 @@ def test_same_bits_every_run_and_for_every_batch(antq_lib, dev, dtype_name):
 GUARD = 64
 
 
-@pytest.mark.parametrize("dtype_name", DTYPES)
-def test_guard_words_and_inputs_untouched(antq_lib, dev, dtype_name):
-    """y between poisoned guard bands; x, codes, alpha and bias are tensors of exactly their sizes and come back unchanged."""
+def _check_guard_words(antq_lib, dev, dtype_name, Ks, Ns, Ms):
     import torch
     dt = getattr(torch, dtype_name)
     rng = np.random.default_rng(31)
@@ -334,12 +227,12 @@ def test_guard_words_and_inputs_untouched(antq_lib, dev, dtype_name):
     gd = plan.grid_dev(dev)
     guard = _bits(torch.full((1,), 3.0, dtype=dt))[0]
     checks = []
-    for K in (8, 72, 520):
-        for N in (72, 8):
+    for K in Ks:
+        for N in Ns:
             codes = torch.from_numpy(_random_codes(rng, K * N // 2, ovp)).to(dev)
             a = torch.from_numpy(np.exp(rng.uniform(-4, 0, K)).astype(np.float32)).to(dev)
             bias = torch.randn(N, device=dev).to(dt)
-            for M in (1, 3, 5, 8):
+            for M in Ms:
                 x = torch.randn(M, K, device=dev).to(dt)
                 keep = (x.clone(), codes.clone(), a.clone(), bias.clone())
                 full = torch.full((M * N + 2 * GUARD,), 3.0, dtype=dt, device=dev)
@@ -353,6 +246,12 @@ def test_guard_words_and_inputs_untouched(antq_lib, dev, dtype_name):
         assert not (b[GUARD:GUARD + M * N] == guard).all(), (dtype_name, K, N, M, "y not written")
         for what, t, t0 in zip(("x", "codes", "alpha", "bias"), now, keep):
             assert torch.equal(t, t0), (dtype_name, K, N, M, what)
+
+
+@pytest.mark.parametrize("dtype_name", DTYPES)
+def test_guard_words_and_inputs_untouched(antq_lib, dev, dtype_name):
+    """y between poisoned guard bands; x, codes, alpha and bias are tensors of exactly their sizes and come back unchanged."""
+    _check_guard_words(antq_lib, dev, dtype_name, (8, 72, 520), (72, 8), (1, 3, 5, 8))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -432,7 +331,109 @@ def test_padding_and_non_finite_values(antq_lib, dev, dtype_name, K):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# 7. module level
+# 7. the order of the sum: include/antq.h's tile rule, bit for bit
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype_name", DTYPES)
+def test_bits_follow_the_tile_rule(antq_lib, dev, dtype_name):
+    """The kernel's bits are those of linear_t_cases.tile_rule -- the text of include/antq.h in numpy -- with no tolerance:
+    Gaussian weights through two books (plain, pair rule with planted outliers), a scale per k and one per tensor, K on both
+    sides of one pass over the 128 phases, of a group of steps in flight and of the staged scales (8192 | 8200), N = 8 and 40,
+    1, 2, 3 and 8 rows; no bias, a Gaussian bias and, for the 16-bit types, the biases that bring the low bits of the fp32
+    sum into the output (cancelling, near-tie).  test_linear_t_cases_host.py shows how many of these outputs another fixed
+    order would change: float32 carries the test."""
+    import torch
+    dt = getattr(torch, dtype_name)
+    for c in lt.rule_cases(dtype_name):
+        name, g, gmax, nn, ovp = c["book"]
+        K, per_row = c["K"], c["per_row"]
+        plan = antq_lib.plan_for(g)
+        gd = plan.grid_dev(dev)
+        sums = lt.rule_sums(c["x"], c["W"], dtype_name)
+        variants = lt.bias_variants(c, sums)
+        a = torch.from_numpy(c["alpha"]).to(dev)
+        x = _tensor(c["x"], dtype_name, dev)
+        image = antq_lib.decode4(torch.from_numpy(c["codes"]).to(dev), a, plan, gmax, K if per_row else 1, c["N"] if per_row else K * c["N"],
+                                 per_row, dt, n_normal=nn, ovp=ovp)
+        runs = []
+        for N in lt.RULE_N:
+            d = lt.columns(c, N)
+            codes = torch.from_numpy(d["codes"]).to(dev)
+            for vname, bias, rows in variants:
+                b = None if bias is None else _tensor(bias[:N], dtype_name, dev)
+                want = lt.finish(sums[:, :N], None if bias is None else bias[:N], dtype_name)
+                for M in lt.RULE_M:
+                    if rows is not None and min(rows) >= M:      # (a row's cancelling bias: calls that hold the row)
+                        continue
+                    y = antq_lib.linear4_t(codes, x[:M], a, gd, gmax, N, K, per_row, bias=b, n_normal=nn, ovp=ovp)
+                    runs.append((N, vname, M, y, want[:M]))
+        torch.cuda.synchronize()
+        assert np.array_equal(_bits(image).reshape(K, c["N"]), c["W"]), (lt.case_id(c), "antq_decode4 against the yardstick")
+        assert {r[1] for r in runs} >= {"none", "gauss"} and {r[2] for r in runs} == set(lt.RULE_M)
+        for N, vname, M, y, want in runs:
+            got = _bits(y)
+            assert got.shape == want.shape == (M, N)
+            assert np.array_equal(got, want), (lt.case_id(c), N, vname, M, "%d of %d outputs differ" % (int((got != want).sum()), got.size))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# 8. K > 8192: the scales divided per step instead of staged
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("K", [lt.STAGED_K, lt.STAGED_K + 8])
+@pytest.mark.parametrize("dtype_name", DTYPES)
+def test_unstaged_scales_have_the_same_bits(antq_lib, dev, dtype_name, K):
+    """The last K whose scales are staged in LDS and the first one beyond (a lane then divides alpha[k] / gmax per step): one-hot
+    rows read the image, the order-free sums are exact, and nothing outside y is written.  (The order of the sum at these K
+    is test_bits_follow_the_tile_rule's.)"""
+    import torch
+    dt = getattr(torch, dtype_name)
+    N = 40
+    # (a) one-hot rows e_k, 8 per call: the first and last k, both sides of the first pass, the last staged index, two mid ones
+    tiny = 1.5e-4 if dtype_name == "float16" else 3.0e-38
+    ks = [0, 127, 128, lt.STAGED_K - 1, K - 1, 4102, 6004, 127]
+    assert len(ks) == 8 and max(ks) < K and {lt.STAGED_K - 1, K - 1} <= set(ks)
+    codes_np = np.concatenate([(np.arange(N // 2) + 37 * k) % 256 for k in range(K)]).astype(np.uint8)
+    assert np.unique(codes_np).size == 256
+    per_k = np.resize(np.float32([1.0, 0.06, tiny, 20 * tiny, 0.37]), K).astype(np.float32)
+    assert {float(per_k[k]) for k in ks} == {float(v) for v in np.float32([1.0, 0.06, tiny, 20 * tiny, 0.37])}
+    xh = np.zeros((8, K), np.float32)
+    xh[np.arange(8), ks] = 1.0
+    x = _tensor(_round(xh, dtype_name), dtype_name, dev)
+    codes, a = torch.from_numpy(codes_np).to(dev), torch.from_numpy(per_k).to(dev)
+    lim = {"float32": 2.0 ** -126, "bfloat16": 2.0 ** -126, "float16": 2.0 ** -14}[dtype_name]
+    for book in _books():
+        name, g, gmax, nn, ovp = book
+        plan = antq_lib.plan_for(g)
+        want = _image_bits(codes_np, per_k, K, N, True, book, dtype_name)
+        sub = np.abs(_value(want[ks], dtype_name))
+        assert ((sub > 0) & (sub < lim)).any(), "no subnormal weight in these rows"
+        image = antq_lib.decode4(codes, a, plan, gmax, K, N, True, dt, n_normal=nn, ovp=ovp).view(K, N)
+        y = antq_lib.linear4_t(codes, x, a, plan.grid_dev(dev), gmax, N, K, True, n_normal=nn, ovp=ovp)
+        torch.cuda.synchronize()
+        assert np.array_equal(_bits(image), want), (name, dtype_name, K, "antq_decode4 against the yardstick")
+        assert np.array_equal(_bits(y), want[ks]), (name, dtype_name, K)
+    # (b) order-free exact sums
+    rng = np.random.default_rng(53)
+    for bname in ("pot_b4_s", "olive_flint"):
+        book = _book(bname)
+        name, g, gmax, nn, ovp = book
+        plan = antq_lib.plan_for(g)
+        codes_e, a_e, x_e, b_e, y_e, density = lt.exact_case(rng, K, book, dtype_name, True, N)
+        xe = _tensor(_round(x_e.astype(np.float32), dtype_name), dtype_name, dev)
+        be = _tensor(_round(b_e.astype(np.float32), dtype_name), dtype_name, dev)
+        ce, ae = torch.from_numpy(codes_e).to(dev), torch.from_numpy(a_e).to(dev)
+        outs = [(M, wb, antq_lib.linear4_t(ce, xe[:M], ae, plan.grid_dev(dev), gmax, N, K, True, bias=be if wb else None, n_normal=nn, ovp=ovp))
+                for M in (1, 3, 8) for wb in (True, False)]
+        torch.cuda.synchronize()
+        for M, wb, y in outs:
+            want = y_e[:M] + (b_e[None, :] if wb else 0.0)
+            assert np.array_equal(_bits(y), _round(want.astype(np.float32), dtype_name)), (name, dtype_name, K, M, wb, density)
+    # (c) footprint
+    if K > lt.STAGED_K:
+        _check_guard_words(antq_lib, dev, dtype_name, (K,), (8, 40), (1, 8))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# 9. module level
 # ---------------------------------------------------------------------------------------------------------------------------
 def _args(**kw):
     d = dict(w_up=150, a_up=150, w_low=75, a_low=75, percent=100, search=False, no_outlier=False)
@@ -440,8 +441,9 @@ def _args(**kw):
     return types.SimpleNamespace(**d)
 
 
-def _conv1d_model(dev, dt, K=136, N=72, seed=1):
-    """nn.Sequential of one OliVe Conv1dQuantizer (4-bit, flint) built from a plain stand-in for HF's Conv1D"""
+def _conv1d_model(dev, dt, K=136, N=72, seed=1, eight_bit=False):
+    """nn.Sequential of one OliVe Conv1dQuantizer (4-bit, flint; eight_bit: reset to 8 bits the way a mixed-precision model's
+    layers are) built from a plain stand-in for HF's Conv1D"""
     import torch
     import torch.nn as nn
     from ant_quantization_amd.olive import quant_utils as qutil
@@ -450,7 +452,11 @@ def _conv1d_model(dev, dt, K=136, N=72, seed=1):
     conv = types.SimpleNamespace(nf=N, weight=nn.Parameter(torch.randn(K, N) * 0.05), bias=nn.Parameter(torch.randn(N) * 0.1))
     layer = Conv1dQuantizer(mode="flint", wbit=4, abit=4, args=_args(mode="flint", wbit=4, abit=4))
     layer.set_param(conv)
-    model = nn.Sequential(layer).to(dev).to(dt).eval()
+    model = nn.Sequential(layer)
+    if eight_bit:
+        from ant_quantization_amd.olive import quant_model as qmod
+        qmod.set_8_bit_layer_l(model, "0")
+    model = model.to(dev).to(dt).eval()
     qutil.enable_quantization(model)
     return model, qutil
 
@@ -522,4 +528,104 @@ def test_packed_conv1d_layer(antq_lib, dev, dtype_name, capsys):
     # a forward that wants gradients: there is no float weight to train
     with pytest.raises(antq_lib.AntqError):
         fused(x1)
+    capsys.readouterr()
+
+
+COUNTERS = ("fused_t_calls", "fused_calls", "fused_mm_calls", "fused_gemm_calls", "fused_byte_calls", "fused_byte_mm_calls", "fused_byte_gemm_calls")
+
+
+def _counters(bank):
+    return tuple(getattr(bank, n) for n in COUNTERS)
+
+
+@pytest.mark.parametrize("dtype_name", ["float32", "bfloat16"])
+def test_packed_conv1d_reload_capture_retype(antq_lib, dev, dtype_name, capsys):
+    """What every sibling kernel's module test does, for the Conv1D path: a packed checkpoint loaded into a fresh model, a
+    forward captured into a graph and replayed, the model retyped."""
+    import torch
+    dt = getattr(torch, dtype_name)
+    K, N = 136, 72
+    base, qutil = _conv1d_model(dev, dt, K, N)
+    gen = torch.Generator(device=dev).manual_seed(3)
+    x1, x3, x8, x9 = (torch.randn(r, K, device=dev, generator=gen).to(dt) for r in (1, 3, 8, 9))
+    with torch.no_grad():
+        base(torch.randn(4, K, device=dev, generator=gen).to(dt))       # calibration
+        lean = copy.deepcopy(base)
+        lbank = qutil.pack_model(lean, fused_linear=True, fused_conv1d=True, keep_images=False)
+        want = {x.shape[0]: lean(x) for x in (x1, x3, x8, x9)}
+        assert _counters(lbank) == (3, 0, 0, 0, 0, 0, 0)               # 9 rows: the layer's addmm on the scratch decode
+
+        # the checkpoint holds codes and no weight: into a differently seeded model with the same options
+        sd = qutil.packed_state_dict(lean)
+        assert "0.weight" not in sd and sd["0.quant_weight.codes"].dtype == torch.uint8 and sd["0.quant_weight.codes"].numel() == K * N // 2
+        fresh, _ = _conv1d_model(dev, dt, K, N, seed=99)
+        assert not torch.equal(fresh[0].bias, lean[0].bias)
+        bank2 = qutil.load_packed_state_dict(fresh, sd, fused_linear=True, fused_conv1d=True, keep_images=False)
+        (e2,) = bank2.entries.values()
+        assert e2["fusable"] and e2["kind"] == "conv1d" and e2["out"] is None and e2["width"] == 4 and e2["shape"] == (K, N)
+        assert torch.equal(e2["codes"], sd["0.quant_weight.codes"])
+        for calls, x in ((1, x1), (2, x8), (2, x9)):
+            assert torch.equal(fresh(x), want[x.shape[0]]), (dtype_name, x.shape[0])
+            assert _counters(bank2) == (calls, 0, 0, 0, 0, 0, 0)
+
+        # a captured 3-row forward replays to the same bits (one stream, no parallel branches)
+        static_x = x3.clone()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            lean(static_x)
+        torch.cuda.current_stream().wait_stream(side)
+        n_calls = lbank.fused_t_calls
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            static_y = lean(static_x)
+        assert lbank.fused_t_calls == n_calls + 1
+        for step in range(2):
+            static_y.zero_()
+            graph.replay()
+            torch.cuda.synchronize()
+            assert torch.equal(static_y, want[3]), (dtype_name, step)
+        assert lbank.fused_t_calls == n_calls + 1
+
+        # the model retyped: the bank rebuilds codes, scales and scratch from the shape it remembers (bf16 <-> fp32)
+        other = torch.float32 if dt == torch.bfloat16 else torch.bfloat16
+        fresh.to(other)
+        before = _counters(bank2)
+        for x in (x1, x9):
+            y = fresh(x.to(other))
+            assert y.dtype == other and y.shape == (x.shape[0], N) and bool(torch.isfinite(y.float()).all())
+        assert _counters(bank2) == (before[0] + 1,) + before[1:]        # the 1-row call from the codes, the 9-row one not
+        assert all(t.dtype == other for t in bank2._scratch.values()) and len(bank2._scratch) == 1
+        assert e2["out"] is None and e2["codes"].dtype == torch.uint8 and e2["dtype"] == other
+    capsys.readouterr()
+
+
+@pytest.mark.parametrize("dtype_name", ["float32", "bfloat16"])
+@pytest.mark.parametrize("what", ["K = 132", "byte codes"])
+def test_conv1d_layers_the_kernel_does_not_take(antq_lib, dev, dtype_name, what, capsys):
+    """A Conv1D layer whose K is no multiple of 8, and a byte-coded (8-bit) one, packed with fused_conv1d=True: the entry is
+    not fusable, keeps its image whatever keep_images says, no call is counted, and the output is the layer's own addmm on the
+    image, bit for bit -- the same as without the option."""
+    import torch
+    dt = getattr(torch, dtype_name)
+    byte = what == "byte codes"
+    K, N = (136, 72) if byte else (132, 72)
+    base, qutil = _conv1d_model(dev, dt, K, N, eight_bit=byte)
+    gen = torch.Generator(device=dev).manual_seed(3)
+    xs = [torch.randn(r, K, device=dev, generator=gen).to(dt) for r in (1, 8, 9)]
+    with torch.no_grad():
+        base(torch.randn(4, K, device=dev, generator=gen).to(dt))       # calibration
+        plain, fused = copy.deepcopy(base), copy.deepcopy(base)
+        pbank = qutil.pack_model(plain, byte_codes=byte)
+        fbank = qutil.pack_model(fused, fused_linear=True, fused_conv1d=True, keep_images=False, byte_codes=byte, fused_bytes=byte)
+        (pe,), (fe,) = pbank.entries.values(), fbank.entries.values()
+        assert pe["width"] == fe["width"] == (8 if byte else 4) and fe["shape"] == (K, N) and fbank.skipped == []
+        assert not fe["fusable"] and fe["kind"] == "linear" and fe["out"] is not None and torch.equal(fe["out"], pe["out"])
+        assert len(fbank._scratch) == 0
+        for x in xs:
+            y = fused(x)
+            assert y.shape == (x.shape[0], N) and y.dtype == dt
+            assert torch.equal(y, torch.addmm(fused[0].bias, fused[0].quant_input(x), fe["out"])), (what, dtype_name, x.shape[0])
+            assert torch.equal(y, plain(x)), (what, dtype_name, x.shape[0])
+        assert _counters(fbank) == (0,) * len(COUNTERS) and _counters(pbank) == (0,) * len(COUNTERS)
     capsys.readouterr()
