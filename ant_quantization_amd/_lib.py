@@ -5,6 +5,7 @@ computation is done by the hand-written gfx950 kernels behind the C ABI.
 There is NO CPU or PyTorch fallback: if the shared library is missing, or a
 tensor is not on a HIP device, the call raises.
 """
+import collections
 import ctypes
 import os
 import threading
@@ -991,10 +992,24 @@ def decode8(codes, alpha, plan, gmax, rows, row_len, per_row, dtype, n_normal=0,
     return out.view(rows, row_len)
 
 
-def _linear4_call(entry, max_m, allow_f32, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out, per_byte=2,
-                  scales=None):
-    """per_byte: codes a byte holds (2: the 4-bit layout, 1: byte codes); scales: entries alpha holds when per_row (None: N,
-    one per output row; linear4_t: K, one per row of the codes)."""
+# The packed linears by public name.  symbol: the C entry point; max_m: the row limit checked here (None: the C side checks
+# it); f32: float32 allowed; per_byte: codes a byte holds (2: the 4-bit layout, 1: byte codes); scales_k: with per_row, alpha
+# holds K scales, one per row of the codes (linear4_t), not N, one per output row.
+_Linear = collections.namedtuple("_Linear", "symbol max_m f32 per_byte scales_k")
+_LINEARS = {
+    "linear4": _Linear("antq_linear4", None, True, 2, False),
+    "linear4_mm": _Linear("antq_linear4_mm", LINEAR4_MM_MAX_M, False, 2, False),
+    "linear4_gemm": _Linear("antq_linear4_gemm", LINEAR4_GEMM_MAX_M, False, 2, False),
+    "linear4_t": _Linear("antq_linear4_t", LINEAR4_T_MAX_M, True, 2, True),
+    "linear8": _Linear("antq_linear8", None, True, 1, False),
+    "linear8_mm": _Linear("antq_linear8_mm", LINEAR8_MM_MAX_M, False, 1, False),
+    "linear8_gemm": _Linear("antq_linear8_gemm", LINEAR8_GEMM_MAX_M, False, 1, False),
+}
+
+
+def _linear_call(name, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out):
+    """The one call path of the packed linears: `name` is a key of _LINEARS."""
+    entry, max_m, allow_f32, per_byte, scales_k = _LINEARS[name]
     _require_gpu(x, "x")
     _require_gpu(codes, "codes")
     _require_gpu(alpha, "alpha")
@@ -1009,7 +1024,7 @@ def _linear4_call(entry, max_m, allow_f32, codes, x, alpha, grid_dev, gmax, N, K
         raise AntqError("%s takes at most %d rows of x (got %d)" % (entry, max_m, M))
     if codes.dtype != torch.uint8 or codes.numel() * per_byte != N * K:
         raise AntqError("codes must be uint8 of N*K%s bytes" % ("/2" if per_byte == 2 else ""))
-    if alpha.dtype != torch.float32 or alpha.numel() < ((N if scales is None else scales) if per_row else 1) or grid_dev.dtype != torch.float32:
+    if alpha.dtype != torch.float32 or alpha.numel() < ((K if scales_k else N) if per_row else 1) or grid_dev.dtype != torch.float32:
         raise AntqError("alpha must be float32, one per row (per_row) or one; grid_dev float32")
     if bias is not None:
         _require_gpu(bias, "bias")
@@ -1017,7 +1032,7 @@ def _linear4_call(entry, max_m, allow_f32, codes, x, alpha, grid_dev, gmax, N, K
             raise AntqError("bias must hold N elements of x's dtype")
     for t in (codes, alpha, grid_dev, bias, out):
         if t is not None and t.device != x.device:
-            raise AntqError("every tensor of %s must live on one device" % ("linear4" if per_byte == 2 else "linear8"))
+            raise AntqError("every tensor of %s must live on one device" % name.split("_")[0])       # (linear4 / linear8)
     shape = tuple(x.shape[:-1]) + (N,)
     if out is None:
         out = torch.empty(shape, dtype=x.dtype, device=x.device)
@@ -1036,14 +1051,14 @@ def linear4(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=
     """y = x . W^T (+ bias) straight from the packed 4-bit codes of W [N, K] (antq_linear4): x is [..., K] with at most
     LINEAR4_MAX_M rows, W[n, k] is bit for bit the element decode4 writes in x's dtype, products and sum in fp32.
     alpha: float32, N scales (per_row) or one; grid_dev: the codebook on the device (Plan.grid_dev).  Returns [..., N]."""
-    return _linear4_call("antq_linear4", None, True, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
+    return _linear_call("linear4", codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
 
 
 def linear4_mm(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):
     """linear4 on the matrix cores (antq_linear4_mm): x is [..., K] with at most LINEAR4_MM_MAX_M rows, bfloat16 or float16
     (float32 raises AntqError).  Same W, fp32 accumulation in the MFMA accumulator; the order of the sum is not linear4's,
     so the same row has different low bits from the two.  A row's bits do not depend on the other rows or on their number."""
-    return _linear4_call("antq_linear4_mm", LINEAR4_MM_MAX_M, False, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
+    return _linear_call("linear4_mm", codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
 
 
 def linear4_gemm(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):
@@ -1051,7 +1066,7 @@ def linear4_gemm(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_no
     or float16 (float32 raises AntqError).  Same W; every y[m, n] is one fp32 MFMA accumulator chain over K, x staged through
     LDS.  The order of the sum is this kernel's own, neither linear4's nor linear4_mm's: the same row has different low bits from
     the three.  A row's bits do not depend on the other rows or on their number."""
-    return _linear4_call("antq_linear4_gemm", LINEAR4_GEMM_MAX_M, False, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
+    return _linear_call("linear4_gemm", codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
 
 
 def linear4_t(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):
@@ -1062,23 +1077,21 @@ def linear4_t(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_norma
     of 8.  alpha: float32, K scales (per_row: one per row k of the codes, i.e. per input feature) or one.  Returns [..., N].
     Measured (profiles/packed_linear_t.md): faster than decode4 + addmm at M = 1 everywhere, faster than addmm on a kept image
     only at M = 1 and not on every layer, slower at M >= 2."""
-    return _linear4_call("antq_linear4_t", LINEAR4_T_MAX_M, True, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out,
-                         scales=K)
+    return _linear_call("linear4_t", codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
 
 
 def linear8(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):
     """linear4 for the BYTE codes of W [N, K] (antq_linear8): x is [..., K] with at most LINEAR8_MAX_M rows, W[n, k] is bit for
     bit the element decode8 writes in x's dtype, products and sum in fp32; a row's bits do not depend on the other rows or on
     their number.  codes: uint8 of N*K bytes (encode8's layout), 8-byte aligned.  Returns [..., N]."""
-    return _linear4_call("antq_linear8", None, True, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out, per_byte=1)
+    return _linear_call("linear8", codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
 
 
 def linear8_mm(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):
     """linear8 on the matrix cores (antq_linear8_mm): x is [..., K] with at most LINEAR8_MM_MAX_M rows, bfloat16 or float16
     (float32 raises AntqError).  Same W, fp32 accumulation in the MFMA accumulator; the order of the sum is not linear8's,
     so the same row has different low bits from the two.  A row's bits do not depend on the other rows or on their number."""
-    return _linear4_call("antq_linear8_mm", LINEAR8_MM_MAX_M, False, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out,
-                         per_byte=1)
+    return _linear_call("linear8_mm", codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
 
 
 def linear8_gemm(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):
@@ -1086,8 +1099,7 @@ def linear8_gemm(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_no
     or float16 (float32 raises AntqError).  Same W; every y[m, n] is one fp32 MFMA accumulator chain over K, x staged through
     LDS.  The order of the sum is this kernel's own, neither linear8's nor linear8_mm's: the same row has different low bits from
     the three.  A row's bits do not depend on the other rows or on their number."""
-    return _linear4_call("antq_linear8_gemm", LINEAR8_GEMM_MAX_M, False, codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out,
-                         per_byte=1)
+    return _linear_call("linear8_gemm", codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
 
 
 # ---------------------------------------------------------------------------------
