@@ -28,6 +28,7 @@ LINEAR4_MAX_M = 8      # include/antq.h ANTQ_LINEAR4_MAX_M: input rows antq_line
 LINEAR4_MM_MAX_M = 64  # include/antq.h ANTQ_LINEAR4_MM_MAX_M: input rows antq_linear4_mm takes
 LINEAR4_GEMM_MAX_M = 4096  # include/antq.h ANTQ_LINEAR4_GEMM_MAX_M: input rows antq_linear4_gemm takes
 LINEAR4_T_MAX_M = 8    # include/antq.h ANTQ_LINEAR4_T_MAX_M: input rows antq_linear4_t takes
+LINEAR4_T_MM_MAX_M = 64  # include/antq.h ANTQ_LINEAR4_T_MM_MAX_M: input rows antq_linear4_t_mm takes
 LINEAR8_MAX_M = 8      # include/antq.h ANTQ_LINEAR8_MAX_M: input rows antq_linear8 takes
 LINEAR8_MM_MAX_M = 64  # include/antq.h ANTQ_LINEAR8_MM_MAX_M: input rows antq_linear8_mm takes
 LINEAR8_GEMM_MAX_M = 4096  # include/antq.h ANTQ_LINEAR8_GEMM_MAX_M: input rows antq_linear8_gemm takes
@@ -69,7 +70,7 @@ def lib():
                              "antq_absmax_t", "antq_alpha_grad_t", "antq_calibrate_install", "antq_decode4_batch_build", "antq_decode4_batch",
                              "antq_linear4", "antq_linear4_mm", "antq_encode8", "antq_decode8", "antq_decode8_batch_build",
                              "antq_decode8_batch", "antq_linear8", "antq_linear8_mm", "antq_linear4_gemm",
-                             "antq_linear8_gemm", "antq_linear4_t"):
+                             "antq_linear8_gemm", "antq_linear4_t", "antq_linear4_t_mm"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
                 L.antq_decode4_batch_capacity.restype = ctypes.c_size_t
@@ -96,6 +97,7 @@ def lib():
                 L.antq_linear4_gemm.argtypes = L.antq_linear4.argtypes
                 L.antq_linear8_gemm.argtypes = L.antq_linear4.argtypes
                 L.antq_linear4_t.argtypes = L.antq_linear4.argtypes
+                L.antq_linear4_t_mm.argtypes = L.antq_linear4.argtypes
                 # development: ANTQ_DEBUG_KNOBS="14=2,0=8" applies antq_debug_set(key, value) pairs to the loading thread
                 # (the knobs are thread-local; tools/fuzz_campaign.sh forces code paths with it)
                 for kv in [k for k in os.environ.get("ANTQ_DEBUG_KNOBS", "").split(",") if "=" in k]:
@@ -1001,6 +1003,7 @@ _LINEARS = {
     "linear4_mm": _Linear("antq_linear4_mm", LINEAR4_MM_MAX_M, False, 2, False),
     "linear4_gemm": _Linear("antq_linear4_gemm", LINEAR4_GEMM_MAX_M, False, 2, False),
     "linear4_t": _Linear("antq_linear4_t", LINEAR4_T_MAX_M, True, 2, True),
+    "linear4_t_mm": _Linear("antq_linear4_t_mm", LINEAR4_T_MM_MAX_M, False, 2, True),
     "linear8": _Linear("antq_linear8", None, True, 1, False),
     "linear8_mm": _Linear("antq_linear8_mm", LINEAR8_MM_MAX_M, False, 1, False),
     "linear8_gemm": _Linear("antq_linear8_gemm", LINEAR8_GEMM_MAX_M, False, 1, False),
@@ -1078,6 +1081,15 @@ def linear4_t(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_norma
     Measured (profiles/packed_linear_t.md): faster than decode4 + addmm at M = 1 everywhere, faster than addmm on a kept image
     only at M = 1 and not on every layer, slower at M >= 2."""
     return _linear_call("linear4_t", codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
+
+
+def linear4_t_mm(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):
+    """linear4_t on the matrix cores (antq_linear4_t_mm): x is [..., K] with at most LINEAR4_T_MM_MAX_M rows, bfloat16 or float16
+    (float32 raises AntqError); codes, N, K and alpha as for linear4_t.  Same W, bit for bit the element decode4 writes; fp32
+    accumulation in the MFMA accumulator in a fixed order that depends on K alone (steps of 32 k dealt to eight wavefronts, one
+    fixed tree: include/antq.h).  The order is neither linear4_t's nor linear4_mm's, so the same row has different low bits from
+    those.  A row's bits do not depend on the other rows, on their number or on N.  Returns [..., N]."""
+    return _linear_call("linear4_t_mm", codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
 
 
 def linear8(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):

@@ -10,6 +10,7 @@
 #include "antq_k_linear_mm.h"
 #include "antq_k_linear_gemm.h"
 #include "antq_k_linear_t.h"
+#include "antq_k_linear_t_mm.h"
 
 #include <type_traits>
 
@@ -570,6 +571,30 @@ static int launch_linear_t(const uint8_t *codes, const void *x, const void *bias
     });
 }
 
+// The launch of the [K, N] matrix-core linear (antq_k_linear_t_mm.h) for 1 .. 64 rows of x, bf16 / f16: one workgroup per
+// 32 kLinTMmPairs output columns, all M tiles in it.
+static int launch_linear_t_mm(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
+                              const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal, bool ovp, int dtype,
+                              void *stream)
+{
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int mt = mm_mtiles(M);
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if constexpr (std::is_same<T, float>::value) return (int)ANTQ_ERR_UNSUPPORTED;
+        else return with_bool(ovp, [&](auto o) {
+            return with_value<1, 2, 4>(mt, [&](auto mm) {
+                constexpr size_t TW = 32 * kLinTMmPairs;
+                const unsigned blocks = (unsigned)((N + TW - 1) / TW);
+                launch_k(false, k_linear_t_mm<T, decltype(o)::value, decltype(mm)::value, kLinTMmPairs>, dim3(blocks),
+                         dim3(64u * kLinTMmWaves), 0, st, codes, x, bias, y, (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha,
+                         per_row ? 1 : 0, gmax, grid, (uint32_t)m, ovp ? n_normal : 0);
+                return launch_status();
+            });
+        });
+    });
+}
+
 // y = x . W^T (+ bias) for 1 .. ANTQ_LINEAR4_MAX_M rows of x from the packed codes of W (antq_k_linear4.h).
 extern "C" int antq_linear4(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
                             const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
@@ -592,6 +617,18 @@ extern "C" int antq_linear4_t(const uint8_t *codes, const void *x, const void *b
     if (rc != kLinearGo) return rc;
     return launch_linear_t(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0, dtype,
                            stream);
+}
+
+// The same product for 1 .. ANTQ_LINEAR4_T_MM_MAX_M rows of x on the matrix cores (antq_k_linear_t_mm.h; bf16 / f16).
+extern "C" int antq_linear4_t_mm(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
+                                 const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
+                                 unsigned flags, int dtype, void *stream)
+{
+    const int rc = linear_checks(codes, x, bias, y, M, N, K, alpha, grid, m, n_normal, flags, dtype, ANTQ_LINEAR4_T_MM_MAX_M, true,
+                                 dec4_book_ok, 4, 2, 8);
+    if (rc != kLinearGo) return rc;
+    return launch_linear_t_mm(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0, dtype,
+                              stream);
 }
 
 // The same product for 1 .. ANTQ_LINEAR4_MM_MAX_M rows of x on the matrix cores (antq_k_linear_mm.h; bf16 / f16).

@@ -92,9 +92,17 @@ every point measured; it buys the memory, and wants fused_byte_rows=64 beside it
 weight [in, out] = [K, N], y = x @ W + b, one scale per INPUT feature k.  Such a layer is packed with or without the option, but
 without it always keeps its image.  With it a 4-bit entry whose module is a Conv1dQuantizer with a 2-D weight, `w.shape[1] ==
 nf` and `w.shape[0] % 8 == 0` is fusable with kind `conv1d`: calls of at most `_lib.LINEAR4_T_MAX_M` rows run `antq_linear4_t`
-(`.fused_t_calls`), its sum order a function of K alone.  There is no matrix-core form for this layout, so `fused_rows` and
-`fused_gemm_rows` do not apply; byte-coded Conv1D entries keep their image.  Buys a GPT-2 the memory and, at one row, roughly the
-speed of the image; with kept images not worth turning on beyond one row (profiles/packed_linear_t.md).
+(`.fused_t_calls`), its sum order a function of K alone.  `fused_rows` and `fused_gemm_rows` mean Linear entries only and do not
+apply (the matrix-core form of this layout is `fused_conv1d_mm`, below); byte-coded Conv1D entries keep their image.  Buys a GPT-2
+the memory and, at one row, roughly the speed of the image; with kept images not worth turning on beyond one row
+(profiles/packed_linear_t.md).
+
+`fused_conv1d_mm=True` (needs fused_linear and fused_conv1d): bf16 / f16 calls of 9 .. `_lib.LINEAR4_T_MM_MAX_M` = 64 rows of
+the fusable Conv1D entries run `antq_linear4_t_mm`, the same product on the matrix cores (`.fused_t_mm_calls`): batched decode,
+speculative or chunked decode and short prompts then decode nothing into the scratch buffer.  Calls of at most 8 rows keep
+`antq_linear4_t`, float32 calls and calls of more than 64 rows the layer's `addmm`.  A flag, not a rows option: the set of
+rows options is pinned (tests/test_packed_routing_host.py).  Faster than the scratch decode + `addmm` at 98 of 128 points of 9 ... 64 rows (0.69 ... 1.84x) and than `addmm` on a kept image at
+19 of 128 (0.45 ... 1.09x): turn it on with `keep_images=False`; with kept images it is not worth turning on (profiles/packed_linear_t_mm.md).
 """
 from collections import namedtuple
 
@@ -114,6 +122,7 @@ CODES_KEY = "quant_weight.codes"
 _Option = namedtuple("_Option", "name default needs limits")
 _OPTIONS = (
     _Option("fused_conv1d", False, ("fused_linear",), None),
+    _Option("fused_conv1d_mm", False, ("fused_linear", "fused_conv1d"), None),
     _Option("fused_bytes", False, ("fused_linear",), None),
     _Option("fused_byte_rows", None, ("fused_linear", "fused_bytes"), ("LINEAR8_MAX_M", "LINEAR8_MM_MAX_M")),
     _Option("fused_byte_gemm_rows", None, ("fused_linear", "fused_bytes"), ("LINEAR8_MM_MAX_M", "LINEAR8_GEMM_MAX_M")),
@@ -125,8 +134,9 @@ _NOTES = {("PackedBank", "keep_images"): " (nothing else computes from the codes
 
 # The routing rule: a fusable entry's call of M rows runs the FIRST route of its (kind, code width) whose row limit is at least
 # M and, if half_only, whose dtype is bfloat16 / float16 -- else the layer's own product on the image.  fn: the function of _lib;
-# counter: the bank's attribute that counts its calls; limit: a constant of _lib, or an option of the bank (None: no such route).
-_Route = namedtuple("_Route", "fn counter limit half_only")
+# counter: the bank's attribute that counts its calls; limit: a constant of _lib, or an option of the bank (None: no such route);
+# when: the flag of the bank that has to be on for the route to exist (None: always).
+_Route = namedtuple("_Route", "fn counter limit half_only when", defaults=(None,))
 _ROUTES = {
     ("linear", 4): (_Route("linear4", "fused_calls", "LINEAR4_MAX_M", False),
                     _Route("linear4_mm", "fused_mm_calls", "fused_rows", True),
@@ -134,7 +144,8 @@ _ROUTES = {
     ("linear", 8): (_Route("linear8", "fused_byte_calls", "LINEAR8_MAX_M", False),
                     _Route("linear8_mm", "fused_byte_mm_calls", "fused_byte_rows", True),
                     _Route("linear8_gemm", "fused_byte_gemm_calls", "fused_byte_gemm_rows", True)),
-    ("conv1d", 4): (_Route("linear4_t", "fused_t_calls", "LINEAR4_T_MAX_M", False),),
+    ("conv1d", 4): (_Route("linear4_t", "fused_t_calls", "LINEAR4_T_MAX_M", False),
+                    _Route("linear4_t_mm", "fused_t_mm_calls", "LINEAR4_T_MM_MAX_M", True, "fused_conv1d_mm")),
 }
 _HALF = (torch.bfloat16, torch.float16)
 
@@ -177,7 +188,7 @@ def _settle(q):
 class PackedBank:
     def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True, fused_rows=None,
                  byte_codes=False, fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None,
-                 fused_conv1d=False):
+                 fused_conv1d=False, fused_conv1d_mm=False):
         """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict);
         a layer's code width is then the one its stored size says (numel / 2 bytes: 4-bit, numel bytes: byte codes).
         Every other parameter: see the module docstring."""
@@ -421,6 +432,8 @@ class PackedBank:
         """The route (of _ROUTES) that serves a call of M rows of entry `e`, or None: the rule stated at the table.  Looks at
         the entry's kind, width and dtype and at the bank's options; touches no tensor."""
         for r in _ROUTES.get((e["kind"], e["width"]), ()):
+            if r.when is not None and not getattr(self, r.when, False):      # (a route whose flag is off or absent does not exist)
+                continue
             limit = getattr(_lib, r.limit) if r.limit.isupper() else getattr(self, r.limit)
             if limit is not None and M <= limit and (e["dtype"] in _HALF or not r.half_only):
                 return r
@@ -491,7 +504,7 @@ def pack_model(model, release_weights=False, **options):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
     (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
     options: fused_linear, keep_images, fused_rows, byte_codes, fused_bytes, fused_byte_rows, fused_gemm_rows,
-    fused_byte_gemm_rows, fused_conv1d -- PackedBank's keywords with its defaults; see the module docstring."""
+    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm -- PackedBank's keywords with its defaults; see the module docstring."""
     return PackedBank(model, release_weights, None, **options)     # (codes: not an option here -- given, it is a TypeError)
 
 
@@ -520,7 +533,7 @@ def load_packed_state_dict(model, sd, release_weights=True, **options):
     any other size raises AntqError naming the layer), and the weights are materialised by the batched decode
     (release_weights=False: copied into the layers' own float weights instead of replacing them).
     options: fused_linear, keep_images, fused_rows, fused_bytes, fused_byte_rows, fused_gemm_rows, fused_byte_gemm_rows,
-    fused_conv1d, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
+    fused_conv1d, fused_conv1d_mm, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
     _check_options("load_packed_state_dict", **options)        # (before the model is touched)
     suffix = "." + CODES_KEY
     codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}

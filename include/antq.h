@@ -47,7 +47,8 @@ extern "C" {
  * and antq_linear4_mm (its matrix-core form for up to 64 rows), and antq_encode8 / antq_decode8 / antq_decode8_batch_capacity /
  * antq_decode8_batch_build / antq_decode8_batch (the byte-code codec), and antq_linear8 (the linear from byte codes), and
  * antq_linear8_mm (its matrix-core form for up to 64 rows), and antq_linear4_gemm (the tiled 4-bit form for up to 4096 rows),
- * and antq_linear8_gemm (the same from byte codes), and antq_linear4_t (the 4-bit linear for weights stored [K, N]).
+ * and antq_linear8_gemm (the same from byte codes), and antq_linear4_t (the 4-bit linear for weights stored [K, N]),
+ * and antq_linear4_t_mm (its matrix-core form for up to 64 rows).
  * A caller built against another version must not call in: the blobs / argument lists differ. */
 #define ANTQ_ABI_VERSION 7
 
@@ -600,6 +601,56 @@ int antq_linear4(const uint8_t *codes_dev,          /* N*K/2 bytes, antq_encode4
 int antq_linear4_t(const uint8_t *codes_dev /* K*N/2 bytes */, const void *x_dev /* [M, K] */, const void *bias_dev /* N or NULL */,
                    void *y_dev /* [M, N] */, size_t M, size_t N, size_t K, const float *alpha_dev, int alpha_per_row, float gmax,
                    const float *grid_dev, int m, int n_normal, unsigned flags, int dtype, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * antq_linear4_t's product for 1 .. ANTQ_LINEAR4_T_MM_MAX_M rows of x on the matrix cores (v_mfma_f32_16x16x32_bf16 / _f16), BF16
+ * and F16 only.  Parameters, layout and scales as antq_linear4_t: K rows of N / 2 bytes, one scale per row k or one per tensor,
+ * OliVe's pairs in adjacent columns.
+ *   W[k,n] is, bit for bit, the element antq_decode4 writes for the same codes, alpha, gmax, grid, flags and dtype: the
+ *          decoder's own pair, scaled by alpha[k] / gmax (a true division) and rounded to `dtype`, then the MFMA operand as it
+ *          is -- no widening, the scale never factored out of the sum or folded into x.
+ *   y[m,n] = round_dtype( sum_k x[m,k] * W[k,n] + bias[n] ): products exact, the sum in fp32 in the MFMA accumulator.
+ *   The sum:
+ *          Step s covers k in [32 s, 32 s + 32).
+ *          Wavefront w takes steps w, w + 8, w + 16, ... in rising order.  They are chained in one fp32 MFMA accumulator from +0.
+ *          Inside a step the place of k is fixed: k group kg, element r (k = 32 s + 8 kg + r).
+ *          A wavefront without a step contributes +0.
+ *          The eight partial tiles meet in LDS, in rounds (one tile of 16 rows of x per round, in the scales' memory).
+ *          They are combined as ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7)).  Then the bias is added in fp32, then ONE
+ *          rounding to the type.
+ *          The bits of y[m,n] depend on row m of x, column n of W, bias[n] and K only.  They do not depend on M, the number of
+ *          16-row tiles, the position of the row in its tile, N, the tile width (64 columns per workgroup), the column's place
+ *          in its tile, the other rows of x, or the run.
+ *          The order is neither antq_linear4_t's nor antq_linear4_mm's: the same row has different low bits from those entry
+ *          points (each within the bound of an fp32 sum).
+ *   No atomics, no split of K across workgroups, no workspace, no allocation, no synchronisation: stream-ordered and capturable
+ *          into a graph.  Reads stay inside the buffers: K % 32 may not be 0, and a group of 8 k past the end of K loads nothing
+ *          and has an all-zero W fragment AND an all-zero x fragment (exactly +0, whatever the weights); a column group past N
+ *          loads nothing and is not stored; rows m >= M have all-zero x fragments and are not stored (a zero against an Inf
+ *          weight there makes a NaN that nobody sees).
+ *   Non-finite values follow IEEE 754 per product and per sum.  A NaN or Inf alpha[k] makes ROW k of W non-finite and reaches
+ *          every y[m, .], also where x[m,k] == 0, exactly as a product with the decoded image does.  A non-finite x[m,k] reaches
+ *          row m of y only.  Subnormal bf16 / f16 weights are kept by the 16-bit MFMA, as for antq_linear4_mm.
+ * Checked before anything touches HIP, in antq_linear4_t's order:
+ *   ANTQ_ERR_ARG          a null codes / x / y / alpha / grid, m < 1, a bad dtype, a flag bit other than ANTQ_FLAG_OVP
+ *   ANTQ_OK, no launch    M == 0 or N == 0
+ *   ANTQ_ERR_UNSUPPORTED  dtype == ANTQ_F32 (the f32-input MFMA runs at the vector rate: such calls stay with antq_linear4_t or
+ *                         the image); M > ANTQ_LINEAR4_T_MM_MAX_M; K == 0 or K % 8 != 0; N % 8 != 0; the decoder's refusals (as
+ *                         antq_linear4); N >= 2^31 or K >= 2^31
+ *   ANTQ_ERR_ALIGN        x_dev not 16-byte aligned, codes_dev not 4-byte aligned, y_dev / bias_dev not aligned to their element
+ * The scales are staged in LDS up to K = 8192 and divided per use beyond (the same bits).
+ * Measured (profiles/packed_linear_t_mm.md; one MI355X, one run, GPT-2 small's and XL's Conv1D shapes, M = 9 / 16 / 32 / 64, bf16 / f16,
+ * two books): faster than antq_decode4 + addmm at 98 of 128 points (0.69 ... 1.84x), faster than addmm on a decoded image at 19 of 128
+ * (0.45 ... 1.09x); at M = 8 faster than antq_linear4_t at 32 of 32 points (1.01 ... 1.91x).  Its own time grows 1.35 ... 1.49x from 9 to 64 rows;
+ * the codes stream at 0.3 ... 4.4 % of 8 TB/s (bound by the decode's instruction count and by latency, not bandwidth).
+ * Loses to antq_decode4 + addmm on the long-K layers [3072, 768] and [6400, 1600] at every M, and to addmm on the image everywhere but at
+ * M = 32 on the K = 768 layers and on [1600, 4800] / [1600, 6400], and at M = 9 on those two in bf16 (by at most 9 %): an option for
+ * memory and for the scratch buffer's lifetime rule, off by default in the packed bank.
+ * ------------------------------------------------------------------------- */
+#define ANTQ_LINEAR4_T_MM_MAX_M 64
+int antq_linear4_t_mm(const uint8_t *codes_dev /* K*N/2 bytes */, const void *x_dev /* [M, K] */, const void *bias_dev /* N or NULL */,
+                      void *y_dev /* [M, N] */, size_t M, size_t N, size_t K, const float *alpha_dev, int alpha_per_row, float gmax,
+                      const float *grid_dev, int m, int n_normal, unsigned flags, int dtype /* BF16 | F16 */, void *stream);
 
 /* ---------------------------------------------------------------------------
  * The same product for 1 .. ANTQ_LINEAR4_MM_MAX_M rows of x on the matrix cores (v_mfma_f32_16x16x32_bf16 / _f16), BF16 and
