@@ -70,7 +70,8 @@ def lib():
                              "antq_absmax_t", "antq_alpha_grad_t", "antq_calibrate_install", "antq_decode4_batch_build", "antq_decode4_batch",
                              "antq_linear4", "antq_linear4_mm", "antq_encode8", "antq_decode8", "antq_decode8_batch_build",
                              "antq_decode8_batch", "antq_linear8", "antq_linear8_mm", "antq_linear4_gemm",
-                             "antq_linear8_gemm", "antq_linear4_t", "antq_linear4_t_mm"):
+                             "antq_linear8_gemm", "antq_linear4_t", "antq_linear4_t_mm", "antq_fakequant_outlier",
+                             "antq_abs_order_stats"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
                 L.antq_decode4_batch_capacity.restype = ctypes.c_size_t
@@ -78,6 +79,7 @@ def lib():
                 L.antq_search_workspace_bytes.restype = ctypes.c_size_t
                 L.antq_calibrate_workspace_bytes.restype = ctypes.c_size_t
                 L.antq_calibrate_batch_workspace_bytes.restype = ctypes.c_size_t
+                L.antq_abs_order_stats_workspace_bytes.restype = ctypes.c_size_t
                 # declared signatures: plain python ints go straight through (no per-call wrapper objects)
                 vp, sz, ci, cf, cu = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_float, ctypes.c_uint
                 L.antq_fakequant.argtypes = [vp, vp, vp, sz, sz, vp, ci, cf, vp, vp, cu, ci, vp]
@@ -98,6 +100,8 @@ def lib():
                 L.antq_linear8_gemm.argtypes = L.antq_linear4.argtypes
                 L.antq_linear4_t.argtypes = L.antq_linear4.argtypes
                 L.antq_linear4_t_mm.argtypes = L.antq_linear4.argtypes
+                L.antq_fakequant_outlier.argtypes = [vp, vp, sz, vp, vp, cf, vp, vp, vp, ci, ci, cu, ci, vp]
+                L.antq_abs_order_stats.argtypes = [vp, sz, sz, vp, vp, ci, vp]
                 # development: ANTQ_DEBUG_KNOBS="14=2,0=8" applies antq_debug_set(key, value) pairs to the loading thread
                 # (the knobs are thread-local; tools/fuzz_campaign.sh forces code paths with it)
                 for kv in [k for k in os.environ.get("ANTQ_DEBUG_KNOBS", "").split(",") if "=" in k]:
@@ -591,6 +595,53 @@ def absmax_t(x):
         _check(lib().antq_absmax_t(x.data_ptr(), amax.data_ptr(), x.numel(), dt, _reduce_ws(x.device).data_ptr(),
                                    _stream_int(x.device)), "antq_absmax_t")
     return amax
+
+
+FLAG_OUTLIER_TAIL = 8     # include/antq.h ANTQ_FLAG_OUTLIER_TAIL
+
+
+def fakequant_outlier(x, p4, p16, plan, gmax, signed, tail, out=None, grid=None):
+    """The steady-state forward of ANT's `outlier` mode (AQ:438-465) as one launch (antq_fakequant_outlier): fp32 x of any
+    element count, p4 / p16 one-element float32 device tensors (never read on the host), `tail` = (percent < 100).
+    out: None (a new tensor) or a contiguous fp32 tensor of x's size, x itself included.  grid: the quantiser's device
+    buffer (float32, plan.grid.size values) -- the kernel then takes `plan` and `gmax` as a hint it verifies against it."""
+    _require_gpu(x, "x")
+    if x.dtype != torch.float32:
+        raise AntqError("fakequant_outlier: float32 only (got %s)" % x.dtype)
+    for t, name in ((p4, "p4"), (p16, "p16")):
+        if not (t.is_cuda and t.device == x.device and t.dtype == torch.float32 and t.numel() == 1):
+            raise AntqError("%s must be one float32 on x's device" % name)
+    if grid is not None and not (grid.is_cuda and grid.device == x.device and grid.dtype == torch.float32
+                                 and grid.is_contiguous() and grid.numel() == plan.grid.size):
+        raise AntqError("grid must be %d contiguous float32 values on x's device" % plan.grid.size)
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _require_out(out, x)
+    if x.numel() == 0:
+        return out
+    with _on_device(x.device):
+        rc = lib().antq_fakequant_outlier(x.data_ptr(), out.data_ptr(), x.numel(), p4.data_ptr(), p16.data_ptr(), gmax,
+                                          plan.host_addr, plan.dev(x.device).data_ptr(), _ptr(grid),
+                                          plan.grid.size, 65535 if signed else 32767,
+                                          FLAG_OUTLIER_TAIL if tail else 0, F32, _stream_int(x.device))
+    if rc:
+        _check(rc, "antq_fakequant_outlier")
+    return out
+
+
+def abs_order_stats(x, k):
+    """[4] float32 on x's device: the k-th and the min(k + 1, n - 1)-th smallest |x| (0-based), the largest non-NaN |x| and
+    the number of NaNs -- exact, by radix select on the device (antq_abs_order_stats); fp32 x of fewer than 2^32 elements."""
+    _require_gpu(x, "x")
+    if x.dtype != torch.float32:
+        raise AntqError("abs_order_stats: float32 only (got %s)" % x.dtype)
+    stats = torch.empty(4, dtype=torch.float32, device=x.device)
+    ws = torch.empty(lib().antq_abs_order_stats_workspace_bytes(), dtype=torch.uint8, device=x.device)
+    with _on_device(x.device):
+        _check(lib().antq_abs_order_stats(x.data_ptr(), x.numel(), k, stats.data_ptr(), ws.data_ptr(), F32,
+                                          _stream_int(x.device)), "antq_abs_order_stats")
+    return stats
 
 
 def moments(x, rows, row_len, per_row=True):

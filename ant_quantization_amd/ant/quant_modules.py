@@ -28,6 +28,33 @@ from .quant_affine import *  # noqa: F401,F403  (the reference star-imports it, 
 _TYPE_ORDER = ("int", "flint", "pot", "float", "float1", "float2", "float3", "float4", "apot")
 
 
+def _percentile_rank(n, q):
+    """np.percentile(a, q) of a float32 array of n values (method `linear`), first half: numpy forms the virtual index
+    (n - 1) * (q / 100) in float32.  Returns (k, t): the result interpolates between the k-th and the (k + 1)-th
+    smallest value with weight t (a float32)."""
+    f = np.float32
+    v = f(n - 1) * (f(q) / f(100))
+    i = np.floor(v)
+    return int(min(max(i, 0), n - 1)), f(v - i)
+
+
+def _percentile_lerp(lo, hi, t):
+    """Second half: numpy's float32 interpolation between the two order statistics (the form changes at t = 0.5)."""
+    f = np.float32
+    lo, hi, t = f(lo), f(hi), f(t)
+    d = hi - lo
+    return hi - d * (f(1) - t) if t >= 0.5 else lo + d * t
+
+
+def _outlier_ends(stats, t):
+    """(p4, p16) of AQ:423-424 from antq_abs_order_stats' four floats: any NaN in the tensor makes both NaN, as
+    np.percentile and Tensor.max do."""
+    lo, hi, top, nans = stats
+    if nans:
+        return np.float32(np.nan), np.float32(np.nan)
+    return _percentile_lerp(lo, hi, t), np.float32(top)
+
+
 def _dist_on():
     return dist.is_available() and dist.is_initialized()
 
@@ -284,9 +311,16 @@ class Quantizer(HostMirrorMixin, WeightsAtRestMixin, CalibrationMixin, nn.Module
     def outlier_set(self, data):
         """'outlier' baseline mode (AQ:417-436): an int4 body up to the `percent`-th percentile of |x| and an
         int16 grid for what lies beyond; the two range ends are averaged over DDP ranks."""
-        absx = data.abs()
-        p4 = torch.tensor(np.percentile(absx.cpu().numpy(), self.percent * 100), device=data.device)
-        p16 = absx.max()
+        if data.is_cuda and data.dtype == torch.float32 and data.is_contiguous() and 0 < data.numel() < 2 ** 32:
+            # the two order statistics np.percentile interpolates between, the maximum and the NaN count, selected on the
+            # device (antq_abs_order_stats): four floats come back instead of the tensor
+            n = data.numel()
+            k, t = _percentile_rank(n, self.percent * 100)
+            p4, p16 = (torch.tensor(v, device=data.device) for v in _outlier_ends(_lib.abs_order_stats(data, k).cpu().numpy(), t))
+        else:
+            absx = data.abs()
+            p4 = torch.tensor(np.percentile(absx.cpu().numpy(), self.percent * 100), device=data.device)
+            p16 = absx.max()
         if _dist_on():
             for t in (p4, p16):
                 dist.all_reduce(t, op=dist.ReduceOp.SUM)
@@ -305,6 +339,14 @@ class Quantizer(HostMirrorMixin, WeightsAtRestMixin, CalibrationMixin, nn.Module
         on a uniform int16 grid over (p4, p16] with a straight-through combination.  Same fp32 op order as the
         reference, written with `where` instead of masked assignment."""
         p4, p16 = self.percent_value_int4, self.percent_value_int16
+        if (data.is_cuda and data.dtype == torch.float32 and data.is_contiguous() and 0 < data.numel() < 2 ** 32
+                and not (data.requires_grad and torch.is_grad_enabled())
+                and all(t.dtype == torch.float32 and t.device == data.device for t in (p4, p16, self.quant_grid))
+                and self.quant_grid.is_contiguous() and self.quant_grid.numel() == self._ensure_plan().grid.size):
+            # one launch, p4 / p16 stay on the device (antq_fakequant_outlier): no `if p4 > 0` synchronisation; the plan is a
+            # hint the kernel verifies against the grid buffer, as QuantBase.forward's is
+            return _lib.fakequant_outlier(data, p4, p16, self._ensure_plan(), self._gmax, self.is_signed, self.percent < 100,
+                                          grid=self.quant_grid)
         if p4 > 0:
             scale = p4 / torch.max(self.quant_grid)
             body = QuantBase.forward(data / scale, self.quant_grid, self._ensure_plan()).clone().detach() * scale

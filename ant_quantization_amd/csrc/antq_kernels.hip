@@ -508,3 +508,71 @@ extern "C" int antq_encode8(const void *x, uint8_t *codes, size_t rows, size_t r
         return launch_encode8<decltype(tag)>(x, codes, rows, row_len, alpha, per_row ? 1 : 0, gmax, pa, plan_host, plan_dev, n_normal, ovp, st);
     });
 }
+
+// ======================================================================================
+// ANT `outlier` mode (AQ:417-465): fused forward, exact order statistics of |x| (antq_k_outlier.h)
+// ======================================================================================
+#include "antq_k_outlier.h"
+
+extern "C" int antq_fakequant_outlier(const void *x, void *out, size_t n, const float *p4, const float *p16, float gmax,
+                                      const void *plan_host, const void *plan_dev, const float *grid_dev, int m, int level,
+                                      unsigned flags, int dtype, void *stream)
+{
+    if (!x || !out || !p4 || !p16 || !plan_host || !plan_dev || n == 0 || level < 1) return ANTQ_ERR_ARG;
+    if (flags & ~ANTQ_FLAG_OUTLIER_TAIL) return ANTQ_ERR_ARG;
+    if (dtype != ANTQ_F32) return ANTQ_ERR_UNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(p4) |
+         reinterpret_cast<uintptr_t>(p16)) % 4)
+        return ANTQ_ERR_ALIGN;
+    PlanArgs pa;
+    if (!plan_args_from_host(plan_host, pa)) return ANTQ_ERR_PLAN;
+    if (grid_dev && (uint32_t)m != pa.m) return ANTQ_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(grid_dev) % 4) return ANTQ_ERR_ALIGN;
+    const bool vec = n >= 4 && (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) % 16 == 0;
+    const size_t per_wg = vec ? 256u * 4u * kOutlierU : 1024u;
+    const size_t blocks = ((vec ? n - n % 4 : n) + per_wg - 1) / per_wg;
+    if (blocks > 0x7fffffffull) return ANTQ_ERR_UNSUPPORTED;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t lds = (size_t)pa.tab_units * 16;
+    const uint4 *tab = plan_tab_ptr(plan_dev);
+    const float levelf = (float)level;
+    return with_bool((flags & ANTQ_FLAG_OUTLIER_TAIL) != 0, [&](auto tail) {
+        constexpr bool TAIL = decltype(tail)::value;
+        if (vec)
+            hipLaunchKernelGGL((k_fq_outlier<TAIL>), dim3((unsigned)blocks), dim3(256), lds, st, static_cast<const uint4 *>(x),
+                               static_cast<uint4 *>(out), n / 4, (uint32_t)(n % 4), p4, p16, gmax, levelf, pa, tab, grid_dev);
+        else
+            hipLaunchKernelGGL((k_fq_outlier_scalar<TAIL>), dim3((unsigned)blocks), dim3(256), lds, st,
+                               static_cast<const float *>(x), static_cast<float *>(out), n, p4, p16, gmax, levelf, pa, tab,
+                               grid_dev);
+        return launch_status();
+    });
+}
+
+extern "C" size_t antq_abs_order_stats_workspace_bytes(void) { return (size_t)kOsWords * 4; }
+
+extern "C" int antq_abs_order_stats(const void *x, size_t n, size_t k, float *stats, void *workspace, int dtype, void *stream)
+{
+    if (!x || !stats || !workspace || n == 0 || k >= n) return ANTQ_ERR_ARG;
+    if (dtype != ANTQ_F32 || n > 0xffffffffull) return ANTQ_ERR_UNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(stats) | reinterpret_cast<uintptr_t>(workspace)) % 4)
+        return ANTQ_ERR_ALIGN;
+    const float *xf = static_cast<const float *>(x);
+    uint32_t *ws = static_cast<uint32_t *>(workspace);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    size_t head = ((16 - reinterpret_cast<uintptr_t>(x) % 16) % 16) / 4;
+    if (head > n) head = n;
+    const size_t n_vec = (n - head) / 4;
+    size_t blocks = (n_vec + 1023) / 1024;
+    if (blocks > kOsMaxBlocks) blocks = kOsMaxBlocks;
+    if (blocks < 1) blocks = 1;
+    const dim3 g((unsigned)blocks), one(1), b(256);
+    hipLaunchKernelGGL(k_os_init, one, b, 0, st, ws, (uint32_t)k, (uint32_t)(k + 1 < n ? k + 1 : n - 1));
+    hipLaunchKernelGGL((k_os_count<0>), g, b, 0, st, xf, n, (uint32_t)head, n_vec, ws);
+    hipLaunchKernelGGL((k_os_scan<0>), one, b, 0, st, ws, stats);
+    hipLaunchKernelGGL((k_os_count<1>), g, b, 0, st, xf, n, (uint32_t)head, n_vec, ws);
+    hipLaunchKernelGGL((k_os_scan<1>), one, b, 0, st, ws, stats);
+    hipLaunchKernelGGL((k_os_count<2>), g, b, 0, st, xf, n, (uint32_t)head, n_vec, ws);
+    hipLaunchKernelGGL((k_os_scan<2>), one, b, 0, st, ws, stats);
+    return launch_status();
+}

@@ -183,6 +183,44 @@ int antq_fakequant_f64(const double *x_dev, double *out_dev, size_t rows, size_t
                        const void *plan_host, const void *plan_dev, unsigned flags, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * ANT's `outlier` baseline mode (AQ:417-465; added under ABI 7, nothing that existed changed).
+ *
+ * antq_fakequant_outlier: the steady-state forward of AQ:438-465 as one launch -- one read of x, one write of out, F32
+ * only (any other dtype: ANTQ_ERR_UNSUPPORTED).  p4_dev / p16_dev: one device float each (the two range ends of
+ * AQ:417-436); nothing is read on the host.  Per element, every operation a separately rounded fp32 operation:
+ *     a = |x|
+ *     body = p4 > 0 ? nearest(x / s) * s : x            s = p4 / gmax; nearest: antq_nearest's rule on the plan's grid
+ *     out  = (flags & ANTQ_FLAG_OUTLIER_TAIL) && a > p4 ? (fine - body) + body : body
+ *     fine = (rint((a - p4) / step) * step + p4) * sign(x)      step = (p16 - p4) / (float)level; rint: half to even
+ * level: 65535 for a signed quantiser, 32767 unsigned (AQ:456).  Set ANTQ_FLAG_OUTLIER_TAIL iff percent < 100 (AQ:451).
+ * grid_dev (nullable; m floats, m = the plan's grid size or ANTQ_ERR_ARG): the device array the quantiser's grid lives in,
+ * with the plan as a HINT of its contents, as in antq_nearest_hinted: every workgroup compares the m values with the plan's
+ * copy bit for bit and, on any difference, scans the device values literally and takes gmax = their maximum (what
+ * AQ:441-442 read from the buffer) -- a stale plan costs time, never a wrong result.  NULL: the plan and gmax are trusted.
+ * A NaN p4 gives out = x; a NaN x gives 0 * s; Inf and step == 0 follow IEEE through the sequence.  n >= 1; out_dev may
+ * be x_dev; pointers need element alignment only (tensors that are not 16-byte aligned take an element-granular kernel
+ * with the same results).  Refusals, before anything is launched: a null pointer, n == 0, level < 1 or another flag
+ * bit: ANTQ_ERR_ARG; a pointer off its element: ANTQ_ERR_ALIGN; a malformed plan: ANTQ_ERR_PLAN.
+ *
+ * antq_abs_order_stats: exact order statistics of |x| (what np.percentile needs of AQ:423, and the maximum of AQ:424)
+ * without sorting or copying the tensor: a radix select over the 31-bit pattern of |x|, three passes over x.  Writes
+ *     stats_dev[0] = the k-th smallest |x| (0-based)        stats_dev[1] = the min(k + 1, n - 1)-th smallest
+ *     stats_dev[2] = the largest |x| that is not a NaN (0 when there is none)
+ *     stats_dev[3] = the number of NaNs, as a float
+ * NaNs rank above Inf, by their bits.  workspace_dev: antq_abs_order_stats_workspace_bytes() bytes, 4-byte aligned,
+ * need not be initialised (the entry clears it with a launch of its own); counts are integer atomics, so every run
+ * gives the same bits.  F32 only and n < 2^32 (otherwise ANTQ_ERR_UNSUPPORTED); a null pointer, n == 0 or k >= n:
+ * ANTQ_ERR_ARG; a pointer off its element: ANTQ_ERR_ALIGN.  Stream-ordered, capturable, nothing is read back.
+ * ------------------------------------------------------------------------- */
+#define ANTQ_FLAG_OUTLIER_TAIL 8u  /* antq_fakequant_outlier only: percent < 100, the int16 tail is applied */
+int antq_fakequant_outlier(const void *x_dev, void *out_dev, size_t n, const float *p4_dev, const float *p16_dev,
+                           float gmax, const void *plan_host, const void *plan_dev, const float *grid_dev, int m,
+                           int level, unsigned flags, int dtype, void *stream);
+size_t antq_abs_order_stats_workspace_bytes(void);
+int antq_abs_order_stats(const void *x_dev, size_t n, size_t k, float *stats_dev, void *workspace_dev, int dtype,
+                         void *stream);
+
+/* ---------------------------------------------------------------------------
  * Same, with alpha computed in the kernel from the data (the initial alpha of
  * _init_quant_para, AQ:473-477, times one clip ratio as in search_mse AQ:300):
  *     alpha[r] = fl32(max_c |x[r,c]| * ratio)
