@@ -29,6 +29,7 @@ LINEAR4_MM_MAX_M = 64  # include/antq.h ANTQ_LINEAR4_MM_MAX_M: input rows antq_l
 LINEAR4_GEMM_MAX_M = 4096  # include/antq.h ANTQ_LINEAR4_GEMM_MAX_M: input rows antq_linear4_gemm takes
 LINEAR4_T_MAX_M = 8    # include/antq.h ANTQ_LINEAR4_T_MAX_M: input rows antq_linear4_t takes
 LINEAR4_T_MM_MAX_M = 64  # include/antq.h ANTQ_LINEAR4_T_MM_MAX_M: input rows antq_linear4_t_mm takes
+LINEAR4_T_GEMM_MAX_M = 4096  # include/antq.h ANTQ_LINEAR4_T_GEMM_MAX_M: input rows antq_linear4_t_gemm takes
 LINEAR8_MAX_M = 8      # include/antq.h ANTQ_LINEAR8_MAX_M: input rows antq_linear8 takes
 LINEAR8_MM_MAX_M = 64  # include/antq.h ANTQ_LINEAR8_MM_MAX_M: input rows antq_linear8_mm takes
 LINEAR8_GEMM_MAX_M = 4096  # include/antq.h ANTQ_LINEAR8_GEMM_MAX_M: input rows antq_linear8_gemm takes
@@ -70,7 +71,7 @@ def lib():
                              "antq_absmax_t", "antq_alpha_grad_t", "antq_calibrate_install", "antq_decode4_batch_build", "antq_decode4_batch",
                              "antq_linear4", "antq_linear4_mm", "antq_encode8", "antq_decode8", "antq_decode8_batch_build",
                              "antq_decode8_batch", "antq_linear8", "antq_linear8_mm", "antq_linear4_gemm",
-                             "antq_linear8_gemm", "antq_linear4_t", "antq_linear4_t_mm", "antq_fakequant_outlier",
+                             "antq_linear8_gemm", "antq_linear4_t", "antq_linear4_t_mm", "antq_linear4_t_gemm", "antq_fakequant_outlier",
                              "antq_abs_order_stats"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
@@ -100,6 +101,7 @@ def lib():
                 L.antq_linear8_gemm.argtypes = L.antq_linear4.argtypes
                 L.antq_linear4_t.argtypes = L.antq_linear4.argtypes
                 L.antq_linear4_t_mm.argtypes = L.antq_linear4.argtypes
+                L.antq_linear4_t_gemm.argtypes = L.antq_linear4.argtypes
                 L.antq_fakequant_outlier.argtypes = [vp, vp, sz, vp, vp, cf, vp, vp, vp, ci, ci, cu, ci, vp]
                 L.antq_abs_order_stats.argtypes = [vp, sz, sz, vp, vp, ci, vp]
                 # development: ANTQ_DEBUG_KNOBS="14=2,0=8" applies antq_debug_set(key, value) pairs to the loading thread
@@ -1055,6 +1057,7 @@ _LINEARS = {
     "linear4_gemm": _Linear("antq_linear4_gemm", LINEAR4_GEMM_MAX_M, False, 2, False),
     "linear4_t": _Linear("antq_linear4_t", LINEAR4_T_MAX_M, True, 2, True),
     "linear4_t_mm": _Linear("antq_linear4_t_mm", LINEAR4_T_MM_MAX_M, False, 2, True),
+    "linear4_t_gemm": _Linear("antq_linear4_t_gemm", LINEAR4_T_GEMM_MAX_M, False, 2, True),
     "linear8": _Linear("antq_linear8", None, True, 1, False),
     "linear8_mm": _Linear("antq_linear8_mm", LINEAR8_MM_MAX_M, False, 1, False),
     "linear8_gemm": _Linear("antq_linear8_gemm", LINEAR8_GEMM_MAX_M, False, 1, False),
@@ -1141,6 +1144,16 @@ def linear4_t_mm(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_no
     fixed tree: include/antq.h).  The order is neither linear4_t's nor linear4_mm's, so the same row has different low bits from
     those.  A row's bits do not depend on the other rows, on their number or on N.  Returns [..., N]."""
     return _linear_call("linear4_t_mm", codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
+
+
+def linear4_t_gemm(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):
+    """linear4_t as a tiled matrix-core product (antq_linear4_t_gemm): x is [..., K] with at most LINEAR4_T_GEMM_MAX_M rows,
+    bfloat16 or float16 (float32 raises AntqError); codes, N, K and alpha as for linear4_t.  Same W, bit for bit the element
+    decode4 writes, decoded once per workgroup and stage of 128 k into LDS and shared by the 128 or 256 rows of x of the tile;
+    every y[m, n] is one fp32 MFMA accumulator chain over K (stages of 128 k, four MFMAs each, in rising order: include/antq.h).
+    The order is neither linear4_t's nor linear4_t_mm's, so the same row has different low bits from those.  A row's bits do not
+    depend on the other rows, on their number or on N.  Returns [..., N]."""
+    return _linear_call("linear4_t_gemm", codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
 
 
 def linear8(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_normal=0, ovp=False, out=None):

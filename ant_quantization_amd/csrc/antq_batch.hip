@@ -11,6 +11,7 @@
 #include "antq_k_linear_gemm.h"
 #include "antq_k_linear_t.h"
 #include "antq_k_linear_t_mm.h"
+#include "antq_k_linear_t_gemm.h"
 
 #include <type_traits>
 
@@ -595,6 +596,30 @@ static int launch_linear_t_mm(const uint8_t *codes, const void *x, const void *b
     });
 }
 
+// The launch of the [K, N] tiled matrix-core linear (antq_k_linear_t_gemm.h) for 1 .. 4096 rows of x, bf16 / f16: one workgroup
+// per (64 WAVES rows of x, 64 output columns) tile.
+static int launch_linear_t_gemm(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
+                                const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal, bool ovp, int dtype,
+                                void *stream)
+{
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int waves = one_of<2, 4>(g_knob_gemm_tile, gemm_waves(M, N));
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if constexpr (std::is_same<T, float>::value) return (int)ANTQ_ERR_UNSUPPORTED;
+        else return with_bool(ovp, [&](auto o) {
+            return with_value<2, 4>(waves, [&](auto wv) {
+                constexpr int WAVES = decltype(wv)::value;
+                constexpr size_t BM = (size_t)kGemmWaveRows * WAVES;
+                const dim3 blocks((unsigned)((N + kGemmBN - 1) / kGemmBN), (unsigned)((M + BM - 1) / BM));
+                launch_k(false, k_linear_t_gemm<T, decltype(o)::value, WAVES>, blocks, dim3(64u * WAVES), 0, st, codes, x, bias, y,
+                         (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha, per_row ? 1 : 0, gmax, grid, (uint32_t)m, ovp ? n_normal : 0);
+                return launch_status();
+            });
+        });
+    });
+}
+
 // y = x . W^T (+ bias) for 1 .. ANTQ_LINEAR4_MAX_M rows of x from the packed codes of W (antq_k_linear4.h).
 extern "C" int antq_linear4(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
                             const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
@@ -629,6 +654,18 @@ extern "C" int antq_linear4_t_mm(const uint8_t *codes, const void *x, const void
     if (rc != kLinearGo) return rc;
     return launch_linear_t_mm(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0, dtype,
                               stream);
+}
+
+// The same product for 1 .. ANTQ_LINEAR4_T_GEMM_MAX_M rows of x as a tiled matrix-core product (antq_k_linear_t_gemm.h; bf16 / f16).
+extern "C" int antq_linear4_t_gemm(const uint8_t *codes, const void *x, const void *bias, void *y, size_t M, size_t N, size_t K,
+                                   const float *alpha, int per_row, float gmax, const float *grid, int m, int n_normal,
+                                   unsigned flags, int dtype, void *stream)
+{
+    const int rc = linear_checks(codes, x, bias, y, M, N, K, alpha, grid, m, n_normal, flags, dtype, ANTQ_LINEAR4_T_GEMM_MAX_M, true,
+                                 dec4_book_ok, 4, 2, 8);
+    if (rc != kLinearGo) return rc;
+    return launch_linear_t_gemm(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal, (flags & ANTQ_FLAG_OVP) != 0, dtype,
+                                stream);
 }
 
 // The same product for 1 .. ANTQ_LINEAR4_MM_MAX_M rows of x on the matrix cores (antq_k_linear_mm.h; bf16 / f16).

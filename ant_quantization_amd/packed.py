@@ -103,6 +103,13 @@ speculative or chunked decode and short prompts then decode nothing into the scr
 `antq_linear4_t`, float32 calls and calls of more than 64 rows the layer's `addmm`.  A flag, not a rows option: the set of
 rows options is pinned (tests/test_packed_routing_host.py).  Faster than the scratch decode + `addmm` at 98 of 128 points of 9 ... 64 rows (0.69 ... 1.84x) and than `addmm` on a kept image at
 19 of 128 (0.45 ... 1.09x): turn it on with `keep_images=False`; with kept images it is not worth turning on (profiles/packed_linear_t_mm.md).
+
+`fused_conv1d_gemm=True` (needs fused_linear and fused_conv1d): bf16 / f16 calls of the fusable Conv1D entries with more rows than
+the kernels above take -- more than 8, or more than 64 when `fused_conv1d_mm` is on as well -- and at most
+`_lib.LINEAR4_T_GEMM_MAX_M` = 4096 rows run `antq_linear4_t_gemm`, a tiled matrix-core product whose workgroups decode each
+weight once into LDS for 128 or 256 rows of x (`.fused_t_gemm_calls`).  A GPT-2 packed with it and `keep_images=False` computes
+its 1024-token forwards without a scratch decode.  A flag like `fused_conv1d_mm`, for the same reason.  What it costs against
+the scratch decode + `addmm` and against a kept image is in profiles/packed_linear_t_gemm.md and DESIGN.md 5p.
 """
 from collections import namedtuple
 
@@ -123,6 +130,7 @@ _Option = namedtuple("_Option", "name default needs limits")
 _OPTIONS = (
     _Option("fused_conv1d", False, ("fused_linear",), None),
     _Option("fused_conv1d_mm", False, ("fused_linear", "fused_conv1d"), None),
+    _Option("fused_conv1d_gemm", False, ("fused_linear", "fused_conv1d"), None),
     _Option("fused_bytes", False, ("fused_linear",), None),
     _Option("fused_byte_rows", None, ("fused_linear", "fused_bytes"), ("LINEAR8_MAX_M", "LINEAR8_MM_MAX_M")),
     _Option("fused_byte_gemm_rows", None, ("fused_linear", "fused_bytes"), ("LINEAR8_MM_MAX_M", "LINEAR8_GEMM_MAX_M")),
@@ -136,6 +144,9 @@ _NOTES = {("PackedBank", "keep_images"): " (nothing else computes from the codes
 # M and, if half_only, whose dtype is bfloat16 / float16 -- else the layer's own product on the image.  fn: the function of _lib;
 # counter: the bank's attribute that counts its calls; limit: a constant of _lib, or an option of the bank (None: no such route);
 # when: the flag of the bank that has to be on for the route to exist (None: always).
+# The last key is no kind of entry: ("conv1d", "tiled") holds the routes a ("conv1d", 4) entry tries AFTER its own list while the
+# bank's flag `fused_conv1d_gemm` is on (_TAILS: key -> (flag, key of the routes appended)).  Without the flag -- off, or absent
+# from a bank built before it existed -- the list of ("conv1d", 4) is all there is, as before.
 _Route = namedtuple("_Route", "fn counter limit half_only when", defaults=(None,))
 _ROUTES = {
     ("linear", 4): (_Route("linear4", "fused_calls", "LINEAR4_MAX_M", False),
@@ -146,7 +157,9 @@ _ROUTES = {
                     _Route("linear8_gemm", "fused_byte_gemm_calls", "fused_byte_gemm_rows", True)),
     ("conv1d", 4): (_Route("linear4_t", "fused_t_calls", "LINEAR4_T_MAX_M", False),
                     _Route("linear4_t_mm", "fused_t_mm_calls", "LINEAR4_T_MM_MAX_M", True, "fused_conv1d_mm")),
+    ("conv1d", "tiled"): (_Route("linear4_t_gemm", "fused_t_gemm_calls", "LINEAR4_T_GEMM_MAX_M", True),),
 }
+_TAILS = {("conv1d", 4): ("fused_conv1d_gemm", ("conv1d", "tiled"))}
 _HALF = (torch.bfloat16, torch.float16)
 
 
@@ -188,7 +201,7 @@ def _settle(q):
 class PackedBank:
     def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True, fused_rows=None,
                  byte_codes=False, fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None,
-                 fused_conv1d=False, fused_conv1d_mm=False):
+                 fused_conv1d=False, fused_conv1d_mm=False, fused_conv1d_gemm=False):
         """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict);
         a layer's code width is then the one its stored size says (numel / 2 bytes: 4-bit, numel bytes: byte codes).
         Every other parameter: see the module docstring."""
@@ -431,7 +444,12 @@ class PackedBank:
     def _route(self, e, M):
         """The route (of _ROUTES) that serves a call of M rows of entry `e`, or None: the rule stated at the table.  Looks at
         the entry's kind, width and dtype and at the bank's options; touches no tensor."""
-        for r in _ROUTES.get((e["kind"], e["width"]), ()):
+        key = (e["kind"], e["width"])
+        routes = _ROUTES.get(key, ())
+        flag, tail = _TAILS.get(key, (None, None))
+        if flag is not None and getattr(self, flag, False):
+            routes = routes + _ROUTES[tail]
+        for r in routes:
             if r.when is not None and not getattr(self, r.when, False):      # (a route whose flag is off or absent does not exist)
                 continue
             limit = getattr(_lib, r.limit) if r.limit.isupper() else getattr(self, r.limit)
@@ -504,7 +522,7 @@ def pack_model(model, release_weights=False, **options):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
     (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
     options: fused_linear, keep_images, fused_rows, byte_codes, fused_bytes, fused_byte_rows, fused_gemm_rows,
-    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm -- PackedBank's keywords with its defaults; see the module docstring."""
+    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm -- PackedBank's keywords with its defaults; see the module docstring."""
     return PackedBank(model, release_weights, None, **options)     # (codes: not an option here -- given, it is a TypeError)
 
 
@@ -533,7 +551,7 @@ def load_packed_state_dict(model, sd, release_weights=True, **options):
     any other size raises AntqError naming the layer), and the weights are materialised by the batched decode
     (release_weights=False: copied into the layers' own float weights instead of replacing them).
     options: fused_linear, keep_images, fused_rows, fused_bytes, fused_byte_rows, fused_gemm_rows, fused_byte_gemm_rows,
-    fused_conv1d, fused_conv1d_mm, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
+    fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
     _check_options("load_packed_state_dict", **options)        # (before the model is touched)
     suffix = "." + CODES_KEY
     codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}

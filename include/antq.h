@@ -48,7 +48,7 @@ extern "C" {
  * antq_decode8_batch_build / antq_decode8_batch (the byte-code codec), and antq_linear8 (the linear from byte codes), and
  * antq_linear8_mm (its matrix-core form for up to 64 rows), and antq_linear4_gemm (the tiled 4-bit form for up to 4096 rows),
  * and antq_linear8_gemm (the same from byte codes), and antq_linear4_t (the 4-bit linear for weights stored [K, N]),
- * and antq_linear4_t_mm (its matrix-core form for up to 64 rows).
+ * and antq_linear4_t_mm (its matrix-core form for up to 64 rows), and antq_linear4_t_gemm (its tiled form for up to 4096 rows).
  * A caller built against another version must not call in: the blobs / argument lists differ. */
 #define ANTQ_ABI_VERSION 7
 
@@ -666,7 +666,8 @@ int antq_linear4_t(const uint8_t *codes_dev /* K*N/2 bytes */, const void *x_dev
  *          and has an all-zero W fragment AND an all-zero x fragment (exactly +0, whatever the weights); a column group past N
  *          loads nothing and is not stored; rows m >= M have all-zero x fragments and are not stored (a zero against an Inf
  *          weight there makes a NaN that nobody sees).
- *   Non-finite values follow IEEE 754 per product and per sum.  A NaN or Inf alpha[k] makes ROW k of W non-finite and reaches
+ *   Non-finite values (this entry point and antq_linear4_t_gemm alike) follow IEEE 754 per product and per sum.  A NaN or Inf
+ *          alpha[k] makes ROW k of W non-finite and reaches
  *          every y[m, .], also where x[m,k] == 0, exactly as a product with the decoded image does.  A non-finite x[m,k] reaches
  *          row m of y only.  Subnormal bf16 / f16 weights are kept by the 16-bit MFMA, as for antq_linear4_mm.
  * Checked before anything touches HIP, in antq_linear4_t's order:
@@ -689,6 +690,44 @@ int antq_linear4_t(const uint8_t *codes_dev /* K*N/2 bytes */, const void *x_dev
 int antq_linear4_t_mm(const uint8_t *codes_dev /* K*N/2 bytes */, const void *x_dev /* [M, K] */, const void *bias_dev /* N or NULL */,
                       void *y_dev /* [M, N] */, size_t M, size_t N, size_t K, const float *alpha_dev, int alpha_per_row, float gmax,
                       const float *grid_dev, int m, int n_normal, unsigned flags, int dtype /* BF16 | F16 */, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * antq_linear4_t's product for 1 .. ANTQ_LINEAR4_T_GEMM_MAX_M rows of x as a tiled matrix-core product (v_mfma_f32_16x16x32_bf16 /
+ * _f16), BF16 and F16 only.  Parameters, layout and scales as antq_linear4_t: K rows of N / 2 bytes, one scale per row k or one
+ * per tensor, OliVe's pairs in adjacent columns.
+ *   W[k,n] is, bit for bit, the element antq_decode4 writes for the same codes, alpha, gmax, grid, flags and dtype: the
+ *          decoder's own pair, scaled by alpha[k] / gmax (a true division) and rounded to `dtype`, then the MFMA operand as it
+ *          is.  A workgroup decodes each weight of its 64 columns ONCE per stage of 128 k into a fragment-ordered image in LDS
+ *          that all of its wavefronts read: the decode is shared by the 128 or 256 rows of x of the tile.
+ *   y[m,n] = round_dtype( sum_k x[m,k] * W[k,n] + bias[n] ): products exact, the sum in fp32 in the MFMA accumulator.
+ *   The sum:
+ *          y[m,n] is ONE fp32 MFMA accumulator chain from +0.
+ *          Stage c covers k in [128 c, 128 c + 128); stages run in rising order.
+ *          The four MFMAs of a stage (step j: k in [128 c + 32 j, 128 c + 32 j + 32)) run in rising order.
+ *          Inside an MFMA the place of k is fixed: k group kg, element r (k = 128 c + 32 j + 8 kg + r).
+ *          Then the bias is added in fp32, then ONE rounding to the type.
+ *          The bits of y[m,n] depend on row m of x, column n of W, bias[n] and K only.  They do not depend on M, N, the tile
+ *          height (128 or 256 rows of x: antq_debug_set key 23 forces it), the position in a tile, the other rows, or the run.
+ *          The order is this kernel's own: it is neither antq_linear4_t's (128 phases and a tree) nor antq_linear4_t_mm's (steps
+ *          dealt to eight wavefronts and a tree), so the same row has different low bits from those entry points.
+ *   No atomics, no split of K across wavefronts or workgroups, no workspace, no allocation, no synchronisation: one launch,
+ *          stream-ordered and capturable into a graph.  Reads stay inside the buffers: a group of 8 k past the end of K (the
+ *          last stage only) loads nothing and has an all-zero W fragment AND an all-zero x piece; a column group past N loads
+ *          nothing and is not stored; rows m >= M clamp their address, are staged as zero and are not stored.  Padding adds
+ *          exactly +0 whatever the weights, Inf and NaN included.
+ *   Non-finite values: as antq_linear4_t_mm.
+ * Checked before anything touches HIP, in antq_linear4_t's order:
+ *   ANTQ_ERR_ARG          a null codes / x / y / alpha / grid, m < 1, a bad dtype, a flag bit other than ANTQ_FLAG_OVP
+ *   ANTQ_OK, no launch    M == 0 or N == 0
+ *   ANTQ_ERR_UNSUPPORTED  dtype == ANTQ_F32; M > ANTQ_LINEAR4_T_GEMM_MAX_M; K == 0 or K % 8 != 0; N % 8 != 0; the decoder's
+ *                         refusals (as antq_linear4); N >= 2^31 or K >= 2^31
+ *   ANTQ_ERR_ALIGN        x_dev not 16-byte aligned, codes_dev not 4-byte aligned, y_dev / bias_dev not aligned to their element
+ * The scales of a stage are staged in LDS whatever K is (no limit, one code path).  Measured: profiles/packed_linear_t_gemm.md.
+ * ------------------------------------------------------------------------- */
+#define ANTQ_LINEAR4_T_GEMM_MAX_M 4096
+int antq_linear4_t_gemm(const uint8_t *codes_dev /* K*N/2 bytes */, const void *x_dev /* [M, K] */, const void *bias_dev /* N or NULL */,
+                        void *y_dev /* [M, N] */, size_t M, size_t N, size_t K, const float *alpha_dev, int alpha_per_row, float gmax,
+                        const float *grid_dev, int m, int n_normal, unsigned flags, int dtype /* BF16 | F16 */, void *stream);
 
 /* ---------------------------------------------------------------------------
  * The same product for 1 .. ANTQ_LINEAR4_MM_MAX_M rows of x on the matrix cores (v_mfma_f32_16x16x32_bf16 / _f16), BF16 and
@@ -904,7 +943,7 @@ int antq_copy(const void *src_dev, void *dst_dev, size_t bytes, void *stream);
  *           with or without the pair rule, one-scale fp32 tensors from 4096)
  *   key 21: 0 sends rows of <= 1024 elements through the 4096-key kernel instead of one row per wavefront (A/B)
  *   key 22: antq_linear4_mm / antq_linear8_mm: tiles of 16 output rows per workgroup, 1 / 2 / 4 (A/B; 0 = the launcher's rule; no result changes)
- *   key 23: antq_linear4_gemm / antq_linear8_gemm: wavefronts per workgroup, 2 / 4, i.e. tiles of 128 / 256 rows of x (A/B; 0 = the launcher's rule:
+ *   key 23: antq_linear4_gemm / antq_linear8_gemm / antq_linear4_t_gemm: wavefronts per workgroup, 2 / 4, i.e. tiles of 128 / 256 rows of x (A/B; 0 = the launcher's rule:
  *           2 while the tiles of 128 rows number at most 256; no result changes) */
 int antq_debug_set(int key, int value);
 
