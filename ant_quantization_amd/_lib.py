@@ -33,6 +33,7 @@ LINEAR4_T_GEMM_MAX_M = 4096  # include/antq.h ANTQ_LINEAR4_T_GEMM_MAX_M: input r
 LINEAR8_MAX_M = 8      # include/antq.h ANTQ_LINEAR8_MAX_M: input rows antq_linear8 takes
 LINEAR8_MM_MAX_M = 64  # include/antq.h ANTQ_LINEAR8_MM_MAX_M: input rows antq_linear8_mm takes
 LINEAR8_GEMM_MAX_M = 4096  # include/antq.h ANTQ_LINEAR8_GEMM_MAX_M: input rows antq_linear8_gemm takes
+LINEAR4_I8_MAX_M = 1 << 20  # include/antq.h ANTQ_LINEAR4_I8_MAX_M: rows of xq antq_linear4_i8 takes
 PLAN_MAX_BYTES = 128 + 4 * MAX_GRID + 16 * 3072 + 20 * 1024 + 16 * 64
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16, torch.float64: F64}
@@ -72,7 +73,7 @@ def lib():
                              "antq_linear4", "antq_linear4_mm", "antq_encode8", "antq_decode8", "antq_decode8_batch_build",
                              "antq_decode8_batch", "antq_linear8", "antq_linear8_mm", "antq_linear4_gemm",
                              "antq_linear8_gemm", "antq_linear4_t", "antq_linear4_t_mm", "antq_linear4_t_gemm", "antq_fakequant_outlier",
-                             "antq_abs_order_stats"):
+                             "antq_abs_order_stats", "antq_quant_i8", "antq_linear4_i8"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
                 L.antq_decode4_batch_capacity.restype = ctypes.c_size_t
@@ -104,6 +105,8 @@ def lib():
                 L.antq_linear4_t_gemm.argtypes = L.antq_linear4.argtypes
                 L.antq_fakequant_outlier.argtypes = [vp, vp, sz, vp, vp, cf, vp, vp, vp, ci, ci, cu, ci, vp]
                 L.antq_abs_order_stats.argtypes = [vp, sz, sz, vp, vp, ci, vp]
+                L.antq_quant_i8.argtypes = [vp, vp, sz, sz, vp, ci, cf, vp, vp, ci, vp, cu, ci, vp]
+                L.antq_linear4_i8.argtypes = [vp, vp, vp, vp, sz, sz, sz, vp, ci, ci, vp, ci, ci, vp, ci, cu, ci, vp]
                 # development: ANTQ_DEBUG_KNOBS="14=2,0=8" applies antq_debug_set(key, value) pairs to the loading thread
                 # (the knobs are thread-local; tools/fuzz_campaign.sh forces code paths with it)
                 for kv in [k for k in os.environ.get("ANTQ_DEBUG_KNOBS", "").split(",") if "=" in k]:
@@ -320,6 +323,21 @@ class Plan:
         t = self._dev.get(key)
         if t is None:
             t = self._dev[key] = torch.from_numpy(self.grid).to(device)
+        return t
+
+    def integer_image(self):
+        """(I, int8 numpy array) of this grid, or None when it has no integer image (grids.integer_image); found once."""
+        if not hasattr(self, "_image"):
+            from . import grids
+            self._image = grids.integer_image(self.grid)
+        return self._image
+
+    def image_dev(self, device):
+        """The integer image's m bytes (int8) on `device`, next to grid_dev; the grid must have one."""
+        key = ("image", device.index if device.index is not None else torch.cuda.current_device())
+        t = self._dev.get(key)
+        if t is None:
+            t = self._dev[key] = torch.from_numpy(self.integer_image()[1]).to(device)
         return t
 
     def eval_host(self, d):
@@ -1176,6 +1194,74 @@ def linear8_gemm(codes, x, alpha, grid_dev, gmax, N, K, per_row, bias=None, n_no
     LDS.  The order of the sum is this kernel's own, neither linear8's nor linear8_mm's: the same row has different low bits from
     the three.  A row's bits do not depend on the other rows or on their number."""
     return _linear_call("linear8_gemm", codes, x, alpha, grid_dev, gmax, N, K, per_row, bias, n_normal, ovp, out)
+
+
+# ---------------------------------------------------------------------------------
+# The integer-domain 4-bit linear (include/antq.h: antq_quant_i8 + antq_linear4_i8).  Not one of the packed linears above: another
+# signature and another contract -- the scales are factored out of an exact int32 sum -- so it is no key of _LINEARS.
+# ---------------------------------------------------------------------------------
+def quant_i8(x, alpha, plan, gmax, rows, row_len, per_row, image, n_normal=0, ovp=False, out=None):
+    """The int8 image of the quantised tensor (antq_quant_i8): q[i] = image[code], the code exactly the byte encode8 stores for
+    the same arguments (a victim: 0, an outlier: image[n_normal + its index]).  image: int8 tensor of the book's m integer
+    values on x's device (grids.integer_image).  out: a caller-owned contiguous int8 buffer of numel bytes.  Returns it."""
+    _require_gpu(x, "x")
+    _require_gpu(image, "image")
+    dt = _DTYPES.get(x.dtype)
+    if dt is None or dt == F64:
+        raise AntqError("unsupported dtype %s" % x.dtype)
+    if image.dtype != torch.int8 or image.numel() != plan.grid.size or image.device != x.device or not image.is_contiguous():
+        raise AntqError("image must be a contiguous int8 tensor of the book's %d values on x's device" % plan.grid.size)
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.int8, device=x.device)
+    elif not (out.is_cuda and out.device == x.device and out.dtype == torch.int8 and out.numel() == x.numel() and out.is_contiguous()):
+        raise AntqError("out must be a contiguous int8 tensor of numel bytes on x's device")
+    pd = plan.dev(x.device)
+    with _on_device(x.device):
+        rc = lib().antq_quant_i8(x.data_ptr(), out.data_ptr(), rows, row_len, alpha.data_ptr(), 1 if per_row else 0, gmax,
+                                 plan.host_ptr(), pd.data_ptr(), n_normal, image.data_ptr(), FLAG_OVP if ovp else 0, dt,
+                                 _stream_int(x.device))
+    if rc:
+        _check(rc, "antq_quant_i8")
+    return out
+
+
+def int_linear4(codes, xq, alpha_w, image_w, I_w, alpha_x, I_x, N, K, per_row, dtype, bias=None, n_normal=0, ovp=False, out=None):
+    """y = fl32(S) * (alpha_x / I_x) * (alpha_w[n] / I_w) (+ bias) in `dtype`, S = xq . V^T the exact int32 sum of the operands'
+    int8 images on the int8 matrix cores (antq_linear4_i8): xq int8 [..., K] (quant_i8), V the image_w entries of the packed
+    4-bit codes of W [N, K] with the decoder's pair rule.  alpha_w: float32, N scales (per_row) or one; alpha_x: one float32;
+    both already the images' units times I (packed.PackedBank.integer_linear_call).  The bits of y[m, n] depend on row m of xq,
+    row n of the codes, the scales and the bias alone.  Not the image product of linear4*: see include/antq.h.  Returns [..., N]."""
+    for t, name in ((codes, "codes"), (xq, "xq"), (alpha_w, "alpha_w"), (image_w, "image_w"), (alpha_x, "alpha_x")):
+        _require_gpu(t, name)
+    dt = _DTYPES.get(dtype)
+    if dt is None or dt == F64:
+        raise AntqError("unsupported dtype %s" % dtype)
+    if xq.dtype != torch.int8 or K <= 0 or xq.numel() % K != 0 or (xq.dim() and xq.shape[-1] != K) or not xq.is_contiguous():
+        raise AntqError("xq must be a contiguous int8 tensor [..., K]")
+    M = xq.numel() // K
+    if codes.dtype != torch.uint8 or codes.numel() * 2 != N * K:
+        raise AntqError("codes must be uint8 of N*K/2 bytes")
+    if (alpha_w.dtype != torch.float32 or alpha_w.numel() < (N if per_row else 1) or alpha_x.dtype != torch.float32 or alpha_x.numel() < 1
+            or image_w.dtype != torch.int8):
+        raise AntqError("alpha_w must be float32, one per row (per_row) or one; alpha_x one float32; image_w int8")
+    if bias is not None:
+        _require_gpu(bias, "bias")
+        if bias.dtype != dtype or bias.numel() != N:
+            raise AntqError("bias must hold N elements of `dtype`")
+    for t in (codes, alpha_w, image_w, alpha_x, bias, out):
+        if t is not None and t.device != xq.device:
+            raise AntqError("every tensor of int_linear4 must live on one device")
+    if out is None:
+        out = torch.empty(tuple(xq.shape[:-1]) + (N,), dtype=dtype, device=xq.device)
+    elif not (out.is_cuda and out.dtype == dtype and out.numel() == M * N and out.is_contiguous()):
+        raise AntqError("out must be a contiguous tensor of `dtype` with M*N elements on xq's device")
+    with _on_device(xq.device):
+        rc = lib().antq_linear4_i8(codes.data_ptr(), xq.data_ptr(), _ptr(bias), out.data_ptr(), M, N, K, alpha_w.data_ptr(),
+                                   1 if per_row else 0, I_w, image_w.data_ptr(), image_w.numel(), n_normal, alpha_x.data_ptr(), I_x,
+                                   FLAG_OVP if ovp else 0, dt, _stream_int(xq.device))
+    if rc:
+        _check(rc, "antq_linear4_i8")
+    return out
 
 
 # ---------------------------------------------------------------------------------

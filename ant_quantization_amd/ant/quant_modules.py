@@ -613,8 +613,12 @@ class LinearQuantizer(nn.Module):
         if not self.quant_input._steady:
             self.quant_input.prefetch_sign(input)
         weight = self.quant_weight(self.weight, input)
-        input = self.quant_input(input, self.weight)
         bank = self.quant_weight._bank
+        if bank is not None and getattr(bank, "integer_linear", False):     # packed.pack_model(integer_linear=True): the raw input
+            out = bank.integer_linear_call(self, input, weight)
+            if out is not None:
+                return out
+        input = self.quant_input(input, self.weight)
         if bank is not None and bank.fused_linear:         # packed.pack_model(fused_linear=True): few rows run from the codes
             return bank.linear(self, input, weight)
         return F.linear(input, weight, self.bias)

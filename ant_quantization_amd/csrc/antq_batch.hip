@@ -12,6 +12,7 @@
 #include "antq_k_linear_t.h"
 #include "antq_k_linear_t_mm.h"
 #include "antq_k_linear_t_gemm.h"
+#include "antq_k_linear_i8.h"
 
 #include <type_traits>
 
@@ -729,6 +730,51 @@ extern "C" int antq_linear8_gemm(const uint8_t *codes, const void *x, const void
     if (rc != kLinearGo) return rc;
     return launch_linear_gemm<Lin8Codec>(codes, x, bias, y, M, N, K, alpha, per_row, gmax, grid, m, n_normal,
                                          (flags & ANTQ_FLAG_OVP) != 0, dtype, stream);
+}
+
+// The integer-domain 4-bit linear (antq_k_linear_i8.h): y = fl32(S) * (alpha_x / I_x) * (alpha_w[n] / I_w) (+ bias) with S the
+// exact int32 sum of the operands' int8 images, 1 .. ANTQ_LINEAR4_I8_MAX_M rows of xq, F32 / BF16 / F16 outputs.  Every check
+// comes before anything touches HIP, in the neighbours' order; one workgroup per (16 MT WAVES rows of xq, 64 output rows) tile.
+extern "C" int antq_linear4_i8(const uint8_t *codes, const int8_t *xq, const void *bias, void *y, size_t M, size_t N, size_t K,
+                               const float *alpha_w, int per_row, int I_w, const int8_t *image_w, int m, int n_normal,
+                               const float *alpha_x, int I_x, unsigned flags, int dtype, void *stream)
+{
+    if (!codes || !xq || !y || !alpha_w || !image_w || !alpha_x || m < 1) return ANTQ_ERR_ARG;
+    if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_ARG;
+    if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
+    if (M == 0 || N == 0) return ANTQ_OK;
+    if (K == 0 || K % 32 != 0 || M > ANTQ_LINEAR4_I8_MAX_M) return ANTQ_ERR_UNSUPPORTED;
+    const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
+    if (!dec4_book_ok(m, n_normal, ovp)) return ANTQ_ERR_UNSUPPORTED;
+    if (N > 0x7fffffffull || K > 0x7fffffe0ull) return ANTQ_ERR_UNSUPPORTED;      // (rows and row length in 32 bits)
+    if (I_x < 1 || I_x > 127 || I_w < 1 || I_w > 127) return ANTQ_ERR_UNSUPPORTED;
+    if ((uint64_t)I_x * (uint64_t)I_w * (uint64_t)K >= (1ull << 31)) return ANTQ_ERR_UNSUPPORTED;      // (the sum could leave int32)
+    const uintptr_t esz = dtype == ANTQ_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(xq) % 16 || reinterpret_cast<uintptr_t>(codes) % 16 || reinterpret_cast<uintptr_t>(y) % esz ||
+        reinterpret_cast<uintptr_t>(bias) % esz || reinterpret_cast<uintptr_t>(alpha_w) % 4 || reinterpret_cast<uintptr_t>(alpha_x) % 4)
+        return ANTQ_ERR_ALIGN;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int waves, mt;
+    i8_shape(M, N, one_of<2, 4>(g_knob_gemm_tile, 0), waves, mt);
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return with_bool(ovp, [&](auto o) {
+            return with_value<2, 4>(waves, [&](auto wv) {
+                return with_value<4, 2>(mt, [&](auto mm) {
+                    constexpr int WAVES = decltype(wv)::value, MT = decltype(mm)::value;
+                    if constexpr (WAVES == 4 && MT == 2) return (int)ANTQ_ERR_UNSUPPORTED;      // (no such shape: i8_shape)
+                    else {
+                        constexpr size_t BM = (size_t)16 * MT * WAVES;
+                        const dim3 blocks((unsigned)((N + kGemmBN - 1) / kGemmBN), (unsigned)((M + BM - 1) / BM));
+                        launch_k(false, k_linear_i8<T, decltype(o)::value, WAVES, MT>, blocks, dim3(64u * WAVES), 0, st, codes, xq, bias, y,
+                                 (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha_w, per_row ? 1 : 0, I_w, image_w, (uint32_t)m,
+                                 ovp ? n_normal : 0, alpha_x, I_x);
+                        return launch_status();
+                    }
+                });
+            });
+        });
+    });
 }
 
 namespace antq {

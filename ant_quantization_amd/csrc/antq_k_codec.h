@@ -64,13 +64,18 @@ __device__ __forceinline__ uint32_t pack_codes(uint32_t (&c)[8])
 
 // What differs between the code widths of the element encoder (k_encode): bits per code, the pair rule's identifier, the
 // units a row may be cut into, the book a code holds, how the E codes of a unit become E * BITS / 32 words (OVP: the pair
-// rule on the outlier bits first) and how those words are stored.
+// rule on the outlier bits first) and how those words are stored; Arg / stage / map / OUT: what a trait that stores something
+// other than the code (antq_k_codec8.h: CodeI8, the code's entry in an image) brings to the workgroup and maps a code through.
 struct Code4 {
     static constexpr int BITS = 4;
     static constexpr uint32_t IDENT = 15u;
     typedef uint32_t Store;                            // the codes are 4-byte aligned (antq_encode4): an octet is one word
     static constexpr bool unit_ok(int E) { return E == 8; }
     static bool book_ok(int m, int n_normal, bool ovp) { return dec4_book_ok(m, n_normal, ovp); }
+    typedef int Arg;                                   // what the launcher hands to stage / store (here: unused)
+    static constexpr uint32_t OUT = 0u;                // the bit map() wants on an outlier's code (none: the code is stored)
+    template <bool OVP> __device__ __forceinline__ static void stage(Arg, int) {}
+    __device__ __forceinline__ static uint32_t map(uint32_t c) { return c; }
     template <bool OVP>
     __device__ __forceinline__ static void pack(uint32_t (&c)[8], uint32_t (&w)[1]) { w[0] = pack_codes<OVP>(c); }
     __device__ __forceinline__ static void store(uint32_t *codes, size_t o, const uint32_t (&w)[1], int) { codes[o] = w[0]; }
@@ -142,7 +147,7 @@ template <typename W, typename T, bool OVP, bool VEC, int E>
 __global__ void __launch_bounds__(256)
 k_encode(const void *__restrict__ x, typename W::Store *__restrict__ codes, size_t n_units, size_t row_len, size_t n_tasks,
          const float *__restrict__ alpha, int per_row, float gmax, int n_normal, int zero_code,
-         PlanArgs pa, const uint4 *__restrict__ plan_tab, int words)
+         PlanArgs pa, const uint4 *__restrict__ plan_tab, typename W::Arg words)
 {
     static_assert(W::unit_ok(E), "no such unit for this code width");
     constexpr int U = VEC ? kEncU : 1;
@@ -158,6 +163,7 @@ k_encode(const void *__restrict__ x, typename W::Store *__restrict__ codes, size
         __syncthreads();
         atab_to_codes<OVP, MASK>(pa, smem, A, n_normal);
     } else L = stage_plan(pa, plan_tab, smem, tab0);
+    W::template stage<OVP>(words, n_normal);
     __syncthreads();
     const size_t upr = row_len / E;                    // row_len % E == 0: a unit (E / 2 pairs) lies inside one row -> one scale
     const bool small = n_units <= 0xffffffffull && upr <= 0xffffffffull;
@@ -203,9 +209,9 @@ k_encode(const void *__restrict__ x, typename W::Store *__restrict__ codes, size
                     uint32_t c;
                     if (jj == ANTQ_IDX_VICTIM) c = W::IDENT;
                     else if (jj == ANTQ_IDX_NONE) c = (uint32_t)zero_code;
-                    else if (OVP && jj >= n_normal) c = (uint32_t)(jj - n_normal);
+                    else if (OVP && jj >= n_normal) c = (uint32_t)(jj - n_normal) | W::OUT;
                     else c = (uint32_t)jj;
-                    w[e * W::BITS / 32] |= (c & MASK) << (e * W::BITS % 32);
+                    w[e * W::BITS / 32] |= (W::map(c) & MASK) << (e * W::BITS % 32);
                 }
             }
             W::store(codes, o, w, words);
@@ -644,7 +650,7 @@ static inline bool codec_tasks(size_t n_units, size_t per_block, bool persistent
 template <typename W, typename T>
 static int launch_encode_units(int E, const void *x, typename W::Store *codes, size_t n_units, size_t row_len, size_t n_tasks, dim3 grid,
                                bool vec, const float *alpha, int per_row, float gmax, int n_normal, int zero_code, const PlanArgs &pa,
-                               const void *plan_dev, bool ovp, int words, hipStream_t st)
+                               const void *plan_dev, bool ovp, typename W::Arg words, hipStream_t st)
 {
     const size_t lds = lds_table(pa, true);
     return with_bool(ovp, [&](auto o) {

@@ -19,6 +19,11 @@ struct Code8 {
     typedef uint8_t Store;
     static constexpr bool unit_ok(int E) { return E == 8 || E == 4; }
     static bool book_ok(int m, int n_normal, bool ovp) { return dec8_book_ok(m, n_normal, ovp); }
+    typedef int Arg;                                   // `words`, store's choice below
+    static constexpr uint32_t OUT = 0u;
+    template <bool OVP> __device__ __forceinline__ static void stage(Arg, int) {}
+    __device__ __forceinline__ static uint32_t map(uint32_t c) { return c; }
+    static Arg arg(int words, const int8_t *, int) { return words; }
     template <bool OVP, int E>
     __device__ __forceinline__ static void pack(uint32_t (&c)[E], uint32_t (&w)[E / 4])
     {
@@ -43,11 +48,55 @@ struct Code8 {
     }
 };
 
-template <typename T>
+// The third store trait (antq_quant_i8): Code8 with every decision, the pair rule and the store as they are, but what is
+// stored for an element is the int8 entry of its code in the book's integer image -- q = image[code], a victim 0, an outlier's
+// index c the entry image[n_normal + c].  The workgroup stages the image once as a 512-byte LDS table keyed by the code with
+// the encoder's own outlier bit (kOutlierBit = bit 8) still on it: [c] = image[c] for a normal code (0 for the identifier
+// and for codes past the book), [256 + c] = image[n_normal + c]; pack / map read one byte of it per element.
+struct QuantI8Arg {
+    const int8_t *image;                               // m bytes on the device
+    int m;
+    int words;                                         // Code8's `words`
+};
+struct CodeI8 : Code8 {
+    typedef QuantI8Arg Arg;
+    static constexpr uint32_t OUT = kOutlierBit;
+    static Arg arg(int words, const int8_t *image, int m) { return Arg{image, m, words}; }
+    __device__ __forceinline__ static uint8_t *tab()
+    {
+        __shared__ uint8_t t[512];
+        return t;
+    }
+    template <bool OVP>
+    __device__ __forceinline__ static void stage(const Arg &a, int n_normal)
+    {
+        for (uint32_t i = threadIdx.x; i < 512u; i += blockDim.x) {
+            const int c = (int)(i & 255u);
+            const int j = i < 256u ? ((OVP && c >= n_normal) ? -1 : c) : (OVP ? n_normal + c : -1);
+            tab()[i] = (j >= 0 && j < a.m) ? (uint8_t)a.image[j] : (uint8_t)0;
+        }
+    }
+    __device__ __forceinline__ static uint32_t map(uint32_t c) { return tab()[c & 0x1ffu]; }
+    template <bool OVP, int E>
+    __device__ __forceinline__ static void pack(uint32_t (&c)[E], uint32_t (&w)[E / 4])
+    {
+#pragma unroll
+        for (int p = 0; p < E / 2; p++)
+            if (OVP) pair_rule(c[2 * p], c[2 * p + 1], IDENT);
+#pragma unroll
+        for (int q = 0; q < E / 4; q++) w[q] = map(c[4 * q]) | (map(c[4 * q + 1]) << 8) | (map(c[4 * q + 2]) << 16) | (map(c[4 * q + 3]) << 24);
+    }
+    template <int N>
+    __device__ __forceinline__ static void store(uint8_t *q, size_t o, const uint32_t (&w)[N], const Arg &a) { Code8::store(q, o, w, a.words); }
+};
+
+// W: Code8 (antq_encode8) or CodeI8 (antq_quant_i8: `image`, the book's integer image, m bytes on the device)
+template <typename T, typename W = Code8>
 static int launch_encode8(const void *x, uint8_t *codes, size_t rows, size_t row_len, const float *alpha, int per_row, float gmax,
-                          const PlanArgs &pa, const void *plan_host, const void *plan_dev, int n_normal, bool ovp, hipStream_t st)
+                          const PlanArgs &pa, const void *plan_host, const void *plan_dev, int n_normal, bool ovp, hipStream_t st,
+                          const int8_t *image = nullptr)
 {
-    if (codec_refuses<Code8>(row_len, 4, pa, n_normal, ovp)) return ANTQ_ERR_UNSUPPORTED;
+    if (codec_refuses<W>(row_len, 4, pa, n_normal, ovp)) return ANTQ_ERR_UNSUPPORTED;
     if (rows > (size_t)-1 / row_len) return ANTQ_ERR_UNSUPPORTED;
     if (reinterpret_cast<uintptr_t>(x) % IO<T>::ESIZE) return ANTQ_ERR_ALIGN;
     const int E = row_len % 8 == 0 ? 8 : 4;
@@ -58,8 +107,8 @@ static int launch_encode8(const void *x, uint8_t *codes, size_t rows, size_t row
     if (!codec_tasks(n_units, vec ? 256 * kEncU : 256, true, n_tasks, gd)) return ANTQ_ERR_UNSUPPORTED;
     const int zero_code = codec_zero_code(plan_host, pa, n_normal, ovp);
     const int words = reinterpret_cast<uintptr_t>(codes) % 4 == 0 ? 1 : 0;
-    return launch_encode_units<Code8, T>(E, x, codes, n_units, row_len, n_tasks, gd, vec, alpha, per_row, gmax, n_normal, zero_code, pa,
-                                         plan_dev, ovp, words, st);
+    return launch_encode_units<W, T>(E, x, codes, n_units, row_len, n_tasks, gd, vec, alpha, per_row, gmax, n_normal, zero_code, pa,
+                                     plan_dev, ovp, W::arg(words, image, (int)pa.m), st);
 }
 
 }  // namespace antq

@@ -509,6 +509,26 @@ extern "C" int antq_encode8(const void *x, uint8_t *codes, size_t rows, size_t r
     });
 }
 
+// Activations to the int8 image of their codes (antq_linear4_i8's x operand): antq_encode8's launch with the CodeI8 store
+// trait, so every decision, refusal and alignment rule is that entry point's.
+extern "C" int antq_quant_i8(const void *x, int8_t *q, size_t rows, size_t row_len, const float *alpha, int per_row, float gmax,
+                             const void *plan_host, const void *plan_dev, int n_normal, const int8_t *image, unsigned flags,
+                             int dtype, void *stream)
+{
+    if (!x || !q || !alpha || !plan_host || !plan_dev || !image) return ANTQ_ERR_ARG;
+    if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
+    if (rows == 0 || row_len == 0) return ANTQ_ERR_ARG;
+    if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_UNSUPPORTED;
+    PlanArgs pa;
+    if (!plan_args_from_host(plan_host, pa)) return ANTQ_ERR_PLAN;
+    const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return with_dtype(dtype, [&](auto tag) {
+        return launch_encode8<decltype(tag), CodeI8>(x, reinterpret_cast<uint8_t *>(q), rows, row_len, alpha, per_row ? 1 : 0, gmax, pa,
+                                                     plan_host, plan_dev, n_normal, ovp, st, image);
+    });
+}
+
 // ======================================================================================
 // ANT `outlier` mode (AQ:417-465): fused forward, exact order statistics of |x| (antq_k_outlier.h)
 // ======================================================================================

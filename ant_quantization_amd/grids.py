@@ -206,3 +206,25 @@ def olive_grid(mode, bit, signed):
     if mode == "flint":
         return olive_flint(bit, signed)
     raise RuntimeError("Unsupported mode: " + mode)
+
+
+# ------------------------------------------------------------------------------------
+# integer images (the integer-domain linear: packed.pack_model(integer_linear=True))
+# ------------------------------------------------------------------------------------
+def integer_image(values):
+    """(I, int8 array) with values[i] / max|values| = array[i] / I: I the smallest integer in 1 .. 127 for which every
+    values[i] / max|values| * I (float64) lies within 1e-5 of an integer, the array those integers in the grid's own order.
+    None when there is no such I, the book is empty or all zero, or a value is not finite.  For an OliVe book `values` is
+    cat(normal, outliers) (the normal values alone when the outlier list is empty)."""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    if v.size == 0 or not np.all(np.isfinite(v)):
+        return None
+    vmax = float(np.max(np.abs(v)))
+    if vmax == 0.0:
+        return None
+    for I in range(1, 128):
+        t = v / vmax * I
+        r = np.rint(t)
+        if np.all(np.abs(t - r) <= 1e-5):
+            return I, (r + 0.0).astype(np.int8)        # (+ 0.0: a book's -0 is 0)
+    return None

@@ -110,9 +110,25 @@ the kernels above take -- more than 8, or more than 64 when `fused_conv1d_mm` is
 weight once into LDS for 128 or 256 rows of x (`.fused_t_gemm_calls`).  A GPT-2 packed with it and `keep_images=False` computes
 its 1024-token forwards without a scratch decode.  A flag like `fused_conv1d_mm`, for the same reason.  What it costs against
 the scratch decode + `addmm` and against a kept image is in profiles/packed_linear_t_gemm.md and DESIGN.md 5p.
+
+`integer_linear=True` (needs fused_linear) is a DIFFERENT contract, not one more kernel for the image product.  Every 4-bit ANT /
+OliVe codebook but two (OliVe flint4 with its outlier list, ANT's unsigned pot4) is a set of small integers times one scale
+(`grids.integer_image`), so a layer's product is an exact int32 sum times `alpha_x / I_x * alpha_w[n] / I_w`.  A 4-bit Linear entry
+whose weight book has such an image and whose K is a multiple of 32 is integer-fusable (others: `.integer_skipped`, with the
+reason).  Its forward, float32 / bfloat16 / float16 alike and for any number of rows, hands the RAW input to
+`bank.integer_linear_call` before `quant_input` runs: `antq_quant_i8` writes the input's int8 image -- the activation quantiser's
+decisions exactly as today -- and `antq_linear4_i8` multiplies it with the codes on the int8 matrix cores and scales each output
+once (`.int_linear_calls`; include/antq.h has the formula).  The result does not depend on tile shape, sum order, M, N or the run.
+It is NOT the bits of the image product: in float32 the two agree to fp32 rounding; in bfloat16 / float16 the integer path does
+not carry the image's rounding of every factor to 8 / 11 bits (2^-9 / 2^-12), so it is the more exact of the two and differs
+from today's output by that much.  The call is served only when lookup() served the weight, the input quantiser is steady,
+enabled, per tensor, in neither `base` nor `outlier` mode, its book has an integer image, `I_x * I_w * K < 2^31` and the call
+qualifies; in every other case the forward proceeds exactly as without the option, same launches, same bits.  Conv1D entries,
+byte codes and ViT's attention wrapper are out of scope.  Measurements and verdict: profiles/int_linear4.md, DESIGN.md 5q.
 """
 from collections import namedtuple
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -137,6 +153,7 @@ _OPTIONS = (
     _Option("keep_images", True, ("fused_linear",), None),
     _Option("fused_rows", None, ("fused_linear",), ("LINEAR4_MAX_M", "LINEAR4_MM_MAX_M")),
     _Option("fused_gemm_rows", None, ("fused_linear",), ("LINEAR4_MM_MAX_M", "LINEAR4_GEMM_MAX_M")),
+    _Option("integer_linear", False, ("fused_linear",), None),
 )
 _NOTES = {("PackedBank", "keep_images"): " (nothing else computes from the codes)"}
 
@@ -201,7 +218,7 @@ def _settle(q):
 class PackedBank:
     def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True, fused_rows=None,
                  byte_codes=False, fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None,
-                 fused_conv1d=False, fused_conv1d_mm=False, fused_conv1d_gemm=False):
+                 fused_conv1d=False, fused_conv1d_mm=False, fused_conv1d_gemm=False, integer_linear=False):
         """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict);
         a layer's code width is then the one its stored size says (numel / 2 bytes: 4-bit, numel bytes: byte codes).
         Every other parameter: see the module docstring."""
@@ -220,6 +237,8 @@ class PackedBank:
         self._scratch = {}         # (device, dtype) -> the one decode buffer of the layers without an image
         self.entries = {}          # id(quantiser) -> dict
         self.skipped = []          # (layer name, reason): layers that keep their float weight and per-layer launch
+        self.integer_skipped = []  # (layer name, reason): 4-bit Linear entries integer_linear does not serve
+        self.int_linear_calls = 0  # forwards antq_quant_i8 + antq_linear4_i8 served
         self.launches = 0          # decode launches so far (one per (device, dtype, pair rule, code width) group and refresh)
         self.dirty = True
         self._batches = []
@@ -260,8 +279,16 @@ class PackedBank:
                         and w.shape[0] % 8 == 0):
                     fusable, kind = True, "conv1d"     # weight [K, N]: the codes' rows are k (antq_linear4_t)
                 image = self.keep_images or not fusable
+                integer = None             # (integer_linear) the weight book's I, when the entry is integer-fusable
+                if self.integer_linear and width == 4 and kind == "linear" and fusable:
+                    why = ("the weight's codebook has no integer image" if plan.integer_image() is None
+                           else "K = %d is not a multiple of 32" % w.shape[1] if w.shape[1] % 32 else None)
+                    if why is None:
+                        integer = plan.integer_image()[0]
+                    else:
+                        self.integer_skipped.append((name, why))
                 self.entries[id(q)] = dict(name=name, q=q, mod=mod, rows=rows, row_len=row_len, per_row=per_row, codes=c, width=width,
-                                           fusable=fusable, kind=kind, shape=tuple(w.shape), dtype=w.dtype, device=w.device,
+                                           fusable=fusable, kind=kind, shape=tuple(w.shape), dtype=w.dtype, device=w.device, integer=integer,
                                            out=torch.empty_like(w, memory_format=torch.contiguous_format) if image else None)
             if not self.entries:
                 raise _lib.AntqError("PackedBank: no weight quantiser to pack (run one forward to calibrate first): %r" % (self.skipped,))
@@ -378,6 +405,7 @@ class PackedBank:
                 # (a 16-bit model's alpha: the kernel reads a float32 copy, brought up to date in place at every refresh)
                 alpha = e["alpha32"] = alpha.to(device=w.device, dtype=torch.float32).contiguous()
             e["alpha"] = alpha
+            e["unit_stamp"] = None         # (integer_linear: the scales as antq_linear4_i8 takes them, formed at the first call)
             if e["out"] is None:           # no image: the codes are the weight (linear); one scratch per (device, dtype) stands in
                 need[(w.device, w.dtype)] = max(need.get((w.device, w.dtype), 0), e["rows"] * e["row_len"])
                 continue
@@ -465,6 +493,51 @@ class PackedBank:
                 and not (torch.is_grad_enabled() and (input.requires_grad or (bias is not None and bias.requires_grad)))
                 and (bias is None or (bias.dtype == input.dtype and bias.is_contiguous() and bias.device == input.device)))
 
+    def integer_linear_call(self, mod, input, weight):
+        """(integer_linear) The output of a LinearQuantizer from its RAW input and what quant_weight returned, in the integer
+        domain: antq_quant_i8 of the input, then antq_linear4_i8 from the codes.  None -- and nothing touched, so that the
+        forward goes on exactly as without the option -- unless lookup() served the weight (linear()'s own test; the mark is
+        popped only when the call is served here), the entry is integer-fusable, the input quantiser is steady, enabled, per
+        tensor with one alpha, in neither `base` nor `outlier` mode and its book has an integer image, I_x I_w K < 2^31 and
+        the call qualifies (_fits; no gradient wanted through the input quantiser's alpha either)."""
+        q, qi = mod.quant_weight, mod.quant_input
+        e = self.entries.get(id(q))
+        if e is None or e["integer"] is None:
+            return None
+        if e["out"] is None:
+            served = e.get("served", False) and weight is mod.weight and q._steady and q.is_enable and q.is_enable_weight
+        else:
+            served = weight is e["out"]
+        N, K = e["shape"]
+        if served and qi._steady and not qi._hm_fresh():
+            # (buffers rebound since -- a deep copy, .to(): what the quantiser's own forward would re-read, _init_quant_para)
+            qi._hm_get('bit')
+            if qi._hm_get('has_inited_quant_para') == 0:
+                return None
+        if not (served and qi._steady and qi._hm_fresh() and getattr(qi, "_pending", None) is None and qi.is_enable
+                and qi.is_enable_activation and not qi.is_perchannel and qi.mode not in ("base", "outlier") and qi.alpha.numel() == 1
+                and not (torch.is_grad_enabled() and qi.alpha.requires_grad) and self._fits(e, input, mod.bias, K)
+                and input.numel() // K <= _lib.LINEAR4_I8_MAX_M):
+            return None
+        plan_x, gmax_x, nn_x, ovp_x = _codebook(qi)
+        image_x = plan_x.integer_image()
+        if image_x is None or image_x[0] * e["integer"] * K >= 2 ** 31:
+            return None
+        e.pop("served", None)
+        plan_w, gmax_w, nn_w, ovp_w = _codebook(q)
+        dev = e["device"]
+        stamp = (qi.alpha.data_ptr(), qi.alpha._version, qi.alpha.dtype, id(plan_x), gmax_x, e["alpha"].data_ptr(), e["alpha"]._version)
+        if e["unit_stamp"] != stamp:
+            with torch.no_grad():
+                e["unit_w"] = _unit_alpha(e["alpha"], plan_w, gmax_w)
+                e["unit_x"] = _unit_alpha(qi.alpha.to(dev), plan_x, gmax_x)
+                e["alpha_x"] = qi.alpha.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+            e["unit_stamp"] = stamp
+        xq = _lib.quant_i8(input, e["alpha_x"], plan_x, gmax_x, 1, input.numel(), False, plan_x.image_dev(dev), n_normal=nn_x, ovp=ovp_x)
+        self.int_linear_calls += 1
+        return _lib.int_linear4(e["codes"], xq, e["unit_w"], plan_w.image_dev(dev), e["integer"], e["unit_x"], image_x[0], N, K,
+                                e["per_row"], e["dtype"], bias=None if mod.bias is None else mod.bias.detach(), n_normal=nn_w, ovp=ovp_w)
+
     def linear(self, mod, input, weight):
         """The output of a LinearQuantizer or Conv1dQuantizer whose weight quantiser this bank serves (fused_linear): `input`
         after quant_input, `weight` what quant_weight returned.  From the codes when the call qualifies, otherwise the layer's
@@ -496,6 +569,15 @@ class PackedBank:
         return mod._conv_forward(input, weight) if conv else F.linear(input, weight, bias)
 
 
+def _unit_alpha(alpha, plan, gmax):
+    """alpha * max|grid| / gmax as float32, formed in float64 (one rounding): the alpha whose quotient by the book's I is the
+    unit of the fake-quantised image, value = integer * alpha' / I.  gmax is max(grid) -- of the normal values for OliVe --
+    and differs from max|grid| for ANT's signed int (-8 .. 7) and for every book with an outlier list."""
+    r = float(np.max(np.abs(plan.grid.astype(np.float64)))) / float(gmax)
+    a = alpha.detach().reshape(-1)
+    return a.to(torch.float32).contiguous() if r == 1.0 else (a.to(torch.float64) * r).to(torch.float32).contiguous()
+
+
 def _is_conv1d(mod):
     """Whether `mod` is OliVe's Conv1dQuantizer (GPT-2's Conv1D: weight [in, out], y = x @ W + b)."""
     from .olive.quant_modules import Conv1dQuantizer       # (here: that module is loaded by whoever built such a layer)
@@ -522,7 +604,7 @@ def pack_model(model, release_weights=False, **options):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
     (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
     options: fused_linear, keep_images, fused_rows, byte_codes, fused_bytes, fused_byte_rows, fused_gemm_rows,
-    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm -- PackedBank's keywords with its defaults; see the module docstring."""
+    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear -- PackedBank's keywords with its defaults; see the module docstring."""
     return PackedBank(model, release_weights, None, **options)     # (codes: not an option here -- given, it is a TypeError)
 
 
@@ -551,7 +633,7 @@ def load_packed_state_dict(model, sd, release_weights=True, **options):
     any other size raises AntqError naming the layer), and the weights are materialised by the batched decode
     (release_weights=False: copied into the layers' own float weights instead of replacing them).
     options: fused_linear, keep_images, fused_rows, fused_bytes, fused_byte_rows, fused_gemm_rows, fused_byte_gemm_rows,
-    fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
+    fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
     _check_options("load_packed_state_dict", **options)        # (before the model is touched)
     suffix = "." + CODES_KEY
     codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}

@@ -888,6 +888,53 @@ int antq_linear8_mm(const uint8_t *codes_dev, const void *x_dev, const void *bia
                     unsigned flags /* 0 | ANTQ_FLAG_OVP */, int dtype /* BF16 | F16 */, void *stream);
 
 /* -------------------------------------------------------------------------
+ * The integer-domain 4-bit linear: antq_quant_i8 + antq_linear4_i8.  An OPT-IN contract of its own, not the image product of
+ * the entry points above: the scales are factored out of the sum.
+ *
+ * The integer image of a codebook is a list of m int8 values v_i and an integer I in 1 .. 127 with grid[i] / max|grid| =
+ * v_i / I; the caller builds it on the host (every 4-bit ANT / OliVe book but OliVe flint4 with outliers and ANT's unsigned
+ * pot4 has one) and keeps the m bytes on the device.
+ *
+ * antq_quant_i8: q[i] = image[code(i)], where code(i) is exactly the byte antq_encode8 stores for the same arguments -- the
+ * element encoder's decisions, the pair rule on the flat pairs (2k, 2k + 1).  A victim (255) becomes 0, an outlier's index c
+ * reads image[n_normal + c], an element outside the scan's range (ANTQ_IDX_NONE) the zero entry; an index past the m bytes
+ * reads 0.  Refusals, alignment rules and dtypes (F32 / BF16 / F16) are antq_encode8's, plus ANTQ_ERR_ARG for a null image.
+ * q_dev: rows*row_len bytes, any alignment.  One launch, no workspace, no allocation, capturable.
+ *
+ * antq_linear4_i8: with v[n, k] = image_w of the code of W[n, k] -- the pair rule applied as antq_decode4 applies it: a
+ * victim is 0, its partner's index c reads image_w[n_normal + c]; a code past the m bytes reads 0 --
+ *     S[m, n] = sum_k xq[m, k] * v[n, k]                                   exact, int32
+ *     u_x     = fl32(alpha_x / I_x),   u_w[n] = fl32(alpha_w[n] / I_w)     true fp32 divisions
+ *     y[m, n] = round_dtype( fl32( fl32( fl32( fl32(S) * u_x ) * u_w[n] ) + fl32(bias[n]) ) )
+ * The two multiplications and the addition are separate fp32 operations, each rounded once (no FMA); without a bias the
+ * addition is skipped; round_dtype is one rounding to nearest even (F32: none).  S runs on v_mfma_i32_16x16x64_i8 and has no
+ * order: the bits of y[m, n] depend on row m of xq, row n of the codes, the scales and the bias, and on nothing else -- not
+ * on M, N, the tile shape or the run.  y is the product of the operands' fake-quantised images when alpha_x / I_x and
+ * alpha_w[n] / I_w are the units of those images (the caller's business: a book whose max|grid| is not the gmax its scale
+ * is formed with passes alpha * max|grid| / gmax); in F32 the two agree to fp32 rounding, in BF16 / F16 this product does not
+ * carry the image's rounding of every factor to 8 / 11 bits.
+ *   ANTQ_ERR_ARG          a null pointer other than bias_dev; m < 1; a dtype other than F32 / BF16 / F16; a flag other than
+ *                         ANTQ_FLAG_OVP
+ *   ANTQ_OK, no launch    M == 0 or N == 0
+ *   ANTQ_ERR_UNSUPPORTED  K == 0 or K % 32 != 0; M > ANTQ_LINEAR4_I8_MAX_M; the 4-bit decoder's book refusals; N >= 2^31;
+ *                         I_x or I_w outside 1 .. 127; I_x * I_w * K >= 2^31 (the sum could leave int32)
+ *   ANTQ_ERR_ALIGN        xq_dev or codes_dev not 16-byte aligned; y_dev / bias_dev not aligned to their element; a scale
+ *                         pointer not 4-byte aligned
+ * xq values must lie in -I_x .. I_x (antq_quant_i8's do).  No atomics, no workspace, no allocation; one launch,
+ * stream-ordered, capturable.  Kernel: csrc/antq_k_linear_i8.h.  Measurements: profiles/int_linear4.md.
+ * ------------------------------------------------------------------------- */
+int antq_quant_i8(const void *x_dev, int8_t *q_dev, size_t rows, size_t row_len,
+                  const float *alpha_dev, int alpha_per_row, float gmax,
+                  const void *plan_host, const void *plan_dev, int n_normal,
+                  const int8_t *image_dev /* m bytes */, unsigned flags, int dtype, void *stream);
+#define ANTQ_LINEAR4_I8_MAX_M (1 << 20)
+int antq_linear4_i8(const uint8_t *codes_dev /* N*K/2 bytes, antq_encode4's layout */, const int8_t *xq_dev /* [M, K] */,
+                    const void *bias_dev /* N or NULL */, void *y_dev /* [M, N] */, size_t M, size_t N, size_t K,
+                    const float *alpha_w_dev, int alpha_per_row, int I_w, const int8_t *image_w_dev, int m, int n_normal,
+                    const float *alpha_x_dev /* one float */, int I_x, unsigned flags /* 0 | ANTQ_FLAG_OVP */,
+                    int dtype /* F32 | BF16 | F16: y and bias */, void *stream);
+
+/* -------------------------------------------------------------------------
  * OliVe's clip statistic on ONE read (replaces t.mean() + t.std() of olive_quantization/antquant/quant_modules.py:193-197
  * and :213-218, which read the tensor at least three times before the clip search reads it again).
  * antq_moments: sums_dev[2 r] = sum of x, sums_dev[2 r + 1] = sum of x^2 over row r (alpha_per_row) or over the whole
