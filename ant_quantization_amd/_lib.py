@@ -34,6 +34,7 @@ LINEAR8_MAX_M = 8      # include/antq.h ANTQ_LINEAR8_MAX_M: input rows antq_line
 LINEAR8_MM_MAX_M = 64  # include/antq.h ANTQ_LINEAR8_MM_MAX_M: input rows antq_linear8_mm takes
 LINEAR8_GEMM_MAX_M = 4096  # include/antq.h ANTQ_LINEAR8_GEMM_MAX_M: input rows antq_linear8_gemm takes
 LINEAR4_I8_MAX_M = 1 << 20  # include/antq.h ANTQ_LINEAR4_I8_MAX_M: rows of xq antq_linear4_i8 takes
+LINEAR4_I8_SK_MAX_M = 64  # include/antq.h ANTQ_LINEAR4_I8_SK_MAX_M: rows of xq antq_linear4_i8_sk takes
 PLAN_MAX_BYTES = 128 + 4 * MAX_GRID + 16 * 3072 + 20 * 1024 + 16 * 64
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16, torch.float64: F64}
@@ -73,7 +74,8 @@ def lib():
                              "antq_linear4", "antq_linear4_mm", "antq_encode8", "antq_decode8", "antq_decode8_batch_build",
                              "antq_decode8_batch", "antq_linear8", "antq_linear8_mm", "antq_linear4_gemm",
                              "antq_linear8_gemm", "antq_linear4_t", "antq_linear4_t_mm", "antq_linear4_t_gemm", "antq_fakequant_outlier",
-                             "antq_abs_order_stats", "antq_quant_i8", "antq_linear4_i8"):
+                             "antq_abs_order_stats", "antq_quant_i8", "antq_linear4_i8", "antq_linear4_i8_sk",
+                             "antq_linear4_i8_sk_slices"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
                 L.antq_decode4_batch_capacity.restype = ctypes.c_size_t
@@ -82,6 +84,7 @@ def lib():
                 L.antq_calibrate_workspace_bytes.restype = ctypes.c_size_t
                 L.antq_calibrate_batch_workspace_bytes.restype = ctypes.c_size_t
                 L.antq_abs_order_stats_workspace_bytes.restype = ctypes.c_size_t
+                L.antq_linear4_i8_sk_workspace_bytes.restype = ctypes.c_size_t
                 # declared signatures: plain python ints go straight through (no per-call wrapper objects)
                 vp, sz, ci, cf, cu = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_float, ctypes.c_uint
                 L.antq_fakequant.argtypes = [vp, vp, vp, sz, sz, vp, ci, cf, vp, vp, cu, ci, vp]
@@ -107,6 +110,9 @@ def lib():
                 L.antq_abs_order_stats.argtypes = [vp, sz, sz, vp, vp, ci, vp]
                 L.antq_quant_i8.argtypes = [vp, vp, sz, sz, vp, ci, cf, vp, vp, ci, vp, cu, ci, vp]
                 L.antq_linear4_i8.argtypes = [vp, vp, vp, vp, sz, sz, sz, vp, ci, ci, vp, ci, ci, vp, ci, cu, ci, vp]
+                L.antq_linear4_i8_sk.argtypes = [vp, vp, vp, vp, sz, sz, sz, vp, ci, ci, vp, ci, ci, vp, ci, vp, sz, cu, ci, vp]
+                L.antq_linear4_i8_sk_workspace_bytes.argtypes = [sz, sz, sz]
+                L.antq_linear4_i8_sk_slices.argtypes = [sz, sz, sz, ci]
                 # development: ANTQ_DEBUG_KNOBS="14=2,0=8" applies antq_debug_set(key, value) pairs to the loading thread
                 # (the knobs are thread-local; tools/fuzz_campaign.sh forces code paths with it)
                 for kv in [k for k in os.environ.get("ANTQ_DEBUG_KNOBS", "").split(",") if "=" in k]:
@@ -1225,12 +1231,8 @@ def quant_i8(x, alpha, plan, gmax, rows, row_len, per_row, image, n_normal=0, ov
     return out
 
 
-def int_linear4(codes, xq, alpha_w, image_w, I_w, alpha_x, I_x, N, K, per_row, dtype, bias=None, n_normal=0, ovp=False, out=None):
-    """y = fl32(S) * (alpha_x / I_x) * (alpha_w[n] / I_w) (+ bias) in `dtype`, S = xq . V^T the exact int32 sum of the operands'
-    int8 images on the int8 matrix cores (antq_linear4_i8): xq int8 [..., K] (quant_i8), V the image_w entries of the packed
-    4-bit codes of W [N, K] with the decoder's pair rule.  alpha_w: float32, N scales (per_row) or one; alpha_x: one float32;
-    both already the images' units times I (packed.PackedBank.integer_linear_call).  The bits of y[m, n] depend on row m of xq,
-    row n of the codes, the scales and the bias alone.  Not the image product of linear4*: see include/antq.h.  Returns [..., N]."""
+def _int_linear_args(codes, xq, alpha_w, image_w, alpha_x, N, K, per_row, dtype, bias, out):
+    """What int_linear4 and int_linear4_sk check alike.  Returns (dtype code, M, out)."""
     for t, name in ((codes, "codes"), (xq, "xq"), (alpha_w, "alpha_w"), (image_w, "image_w"), (alpha_x, "alpha_x")):
         _require_gpu(t, name)
     dt = _DTYPES.get(dtype)
@@ -1255,12 +1257,52 @@ def int_linear4(codes, xq, alpha_w, image_w, I_w, alpha_x, I_x, N, K, per_row, d
         out = torch.empty(tuple(xq.shape[:-1]) + (N,), dtype=dtype, device=xq.device)
     elif not (out.is_cuda and out.dtype == dtype and out.numel() == M * N and out.is_contiguous()):
         raise AntqError("out must be a contiguous tensor of `dtype` with M*N elements on xq's device")
+    return dt, M, out
+
+
+def int_linear4(codes, xq, alpha_w, image_w, I_w, alpha_x, I_x, N, K, per_row, dtype, bias=None, n_normal=0, ovp=False, out=None):
+    """y = fl32(S) * (alpha_x / I_x) * (alpha_w[n] / I_w) (+ bias) in `dtype`, S = xq . V^T the exact int32 sum of the operands'
+    int8 images on the int8 matrix cores (antq_linear4_i8): xq int8 [..., K] (quant_i8), V the image_w entries of the packed
+    4-bit codes of W [N, K] with the decoder's pair rule.  alpha_w: float32, N scales (per_row) or one; alpha_x: one float32;
+    both already the images' units times I (packed.PackedBank.integer_linear_call).  The bits of y[m, n] depend on row m of xq,
+    row n of the codes, the scales and the bias alone.  Not the image product of linear4*: see include/antq.h.  Returns [..., N]."""
+    dt, M, out = _int_linear_args(codes, xq, alpha_w, image_w, alpha_x, N, K, per_row, dtype, bias, out)
     with _on_device(xq.device):
         rc = lib().antq_linear4_i8(codes.data_ptr(), xq.data_ptr(), _ptr(bias), out.data_ptr(), M, N, K, alpha_w.data_ptr(),
                                    1 if per_row else 0, I_w, image_w.data_ptr(), image_w.numel(), n_normal, alpha_x.data_ptr(), I_x,
                                    FLAG_OVP if ovp else 0, dt, _stream_int(xq.device))
     if rc:
         _check(rc, "antq_linear4_i8")
+    return out
+
+
+def int_linear4_sk_workspace_bytes(M, N, K, device=None):
+    """The bytes of workspace int_linear4_sk needs for this call now, on `device` (default: the current one) and with the calling
+    thread's debug knobs (antq_linear4_i8_sk_workspace_bytes); 0 when K is not split."""
+    if device is None:
+        return int(lib().antq_linear4_i8_sk_workspace_bytes(M, N, K))
+    with _on_device(device):
+        return int(lib().antq_linear4_i8_sk_workspace_bytes(M, N, K))
+
+
+def int_linear4_sk(codes, xq, alpha_w, image_w, I_w, alpha_x, I_x, N, K, per_row, dtype, bias=None, n_normal=0, ovp=False, out=None,
+                   workspace=None):
+    """int_linear4 for at most LINEAR4_I8_SK_MAX_M rows of xq with K split across workgroups (antq_linear4_i8_sk): the same
+    arguments, the same bits.  workspace: a contiguous uint8 tensor on xq's device of at least
+    int_linear4_sk_workspace_bytes(M, N, K) bytes, 16-byte aligned -- scratch, free again when the call has finished on its
+    stream; None allocates one of that size."""
+    dt, M, out = _int_linear_args(codes, xq, alpha_w, image_w, alpha_x, N, K, per_row, dtype, bias, out)
+    if workspace is None:
+        workspace = torch.empty(int_linear4_sk_workspace_bytes(M, N, K, xq.device), dtype=torch.uint8, device=xq.device)
+    elif not (workspace.is_cuda and workspace.device == xq.device and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise AntqError("workspace must be a contiguous uint8 tensor on xq's device")
+    with _on_device(xq.device):
+        rc = lib().antq_linear4_i8_sk(codes.data_ptr(), xq.data_ptr(), _ptr(bias), out.data_ptr(), M, N, K, alpha_w.data_ptr(),
+                                      1 if per_row else 0, I_w, image_w.data_ptr(), image_w.numel(), n_normal, alpha_x.data_ptr(), I_x,
+                                      workspace.data_ptr() if workspace.numel() else None, workspace.numel(), FLAG_OVP if ovp else 0, dt,
+                                      _stream_int(xq.device))
+    if rc:
+        _check(rc, "antq_linear4_i8_sk")
     return out
 
 

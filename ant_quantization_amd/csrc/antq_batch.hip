@@ -13,7 +13,9 @@
 #include "antq_k_linear_t_mm.h"
 #include "antq_k_linear_t_gemm.h"
 #include "antq_k_linear_i8.h"
+#include "antq_k_linear_i8_sk.h"
 
+#include <atomic>
 #include <type_traits>
 
 using namespace antq;
@@ -732,6 +734,29 @@ extern "C" int antq_linear8_gemm(const uint8_t *codes, const void *x, const void
                                          (flags & ANTQ_FLAG_OVP) != 0, dtype, stream);
 }
 
+// The checks the integer-domain entries share, in the order include/antq.h states (kLinearGo: launch).  max_m: the entry's row
+// limit; workspace: antq_linear4_i8_sk's (any alignment passes when null), nullptr for antq_linear4_i8.
+static int i8_checks(const uint8_t *codes, const int8_t *xq, const void *bias, void *y, size_t M, size_t N, size_t K, const float *alpha_w,
+                     int I_w, const int8_t *image_w, int m, int n_normal, const float *alpha_x, int I_x, unsigned flags, int dtype,
+                     size_t max_m, const void *workspace)
+{
+    if (!codes || !xq || !y || !alpha_w || !image_w || !alpha_x || m < 1) return ANTQ_ERR_ARG;
+    if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_ARG;
+    if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
+    if (M == 0 || N == 0) return ANTQ_OK;
+    if (K == 0 || K % 32 != 0 || M > max_m) return ANTQ_ERR_UNSUPPORTED;
+    if (!dec4_book_ok(m, n_normal, (flags & ANTQ_FLAG_OVP) != 0)) return ANTQ_ERR_UNSUPPORTED;
+    if (N > 0x7fffffffull || K > 0x7fffffe0ull) return ANTQ_ERR_UNSUPPORTED;      // (rows and row length in 32 bits)
+    if (I_x < 1 || I_x > 127 || I_w < 1 || I_w > 127) return ANTQ_ERR_UNSUPPORTED;
+    if ((uint64_t)I_x * (uint64_t)I_w * (uint64_t)K >= (1ull << 31)) return ANTQ_ERR_UNSUPPORTED;      // (the sum could leave int32)
+    const uintptr_t esz = dtype == ANTQ_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(xq) % 16 || reinterpret_cast<uintptr_t>(codes) % 16 || reinterpret_cast<uintptr_t>(y) % esz ||
+        reinterpret_cast<uintptr_t>(bias) % esz || reinterpret_cast<uintptr_t>(alpha_w) % 4 || reinterpret_cast<uintptr_t>(alpha_x) % 4 ||
+        reinterpret_cast<uintptr_t>(workspace) % 16)
+        return ANTQ_ERR_ALIGN;
+    return kLinearGo;
+}
+
 // The integer-domain 4-bit linear (antq_k_linear_i8.h): y = fl32(S) * (alpha_x / I_x) * (alpha_w[n] / I_w) (+ bias) with S the
 // exact int32 sum of the operands' int8 images, 1 .. ANTQ_LINEAR4_I8_MAX_M rows of xq, F32 / BF16 / F16 outputs.  Every check
 // comes before anything touches HIP, in the neighbours' order; one workgroup per (16 MT WAVES rows of xq, 64 output rows) tile.
@@ -739,20 +764,10 @@ extern "C" int antq_linear4_i8(const uint8_t *codes, const int8_t *xq, const voi
                                const float *alpha_w, int per_row, int I_w, const int8_t *image_w, int m, int n_normal,
                                const float *alpha_x, int I_x, unsigned flags, int dtype, void *stream)
 {
-    if (!codes || !xq || !y || !alpha_w || !image_w || !alpha_x || m < 1) return ANTQ_ERR_ARG;
-    if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_ARG;
-    if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
-    if (M == 0 || N == 0) return ANTQ_OK;
-    if (K == 0 || K % 32 != 0 || M > ANTQ_LINEAR4_I8_MAX_M) return ANTQ_ERR_UNSUPPORTED;
+    const int rc = i8_checks(codes, xq, bias, y, M, N, K, alpha_w, I_w, image_w, m, n_normal, alpha_x, I_x, flags, dtype,
+                             ANTQ_LINEAR4_I8_MAX_M, nullptr);
+    if (rc != kLinearGo) return rc;
     const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
-    if (!dec4_book_ok(m, n_normal, ovp)) return ANTQ_ERR_UNSUPPORTED;
-    if (N > 0x7fffffffull || K > 0x7fffffe0ull) return ANTQ_ERR_UNSUPPORTED;      // (rows and row length in 32 bits)
-    if (I_x < 1 || I_x > 127 || I_w < 1 || I_w > 127) return ANTQ_ERR_UNSUPPORTED;
-    if ((uint64_t)I_x * (uint64_t)I_w * (uint64_t)K >= (1ull << 31)) return ANTQ_ERR_UNSUPPORTED;      // (the sum could leave int32)
-    const uintptr_t esz = dtype == ANTQ_F32 ? 4 : 2;
-    if (reinterpret_cast<uintptr_t>(xq) % 16 || reinterpret_cast<uintptr_t>(codes) % 16 || reinterpret_cast<uintptr_t>(y) % esz ||
-        reinterpret_cast<uintptr_t>(bias) % esz || reinterpret_cast<uintptr_t>(alpha_w) % 4 || reinterpret_cast<uintptr_t>(alpha_x) % 4)
-        return ANTQ_ERR_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int waves, mt;
     i8_shape(M, N, one_of<2, 4>(g_knob_gemm_tile, 0), waves, mt);
@@ -771,6 +786,68 @@ extern "C" int antq_linear4_i8(const uint8_t *codes, const int8_t *xq, const voi
                                  ovp ? n_normal : 0, alpha_x, I_x);
                         return launch_status();
                     }
+                });
+            });
+        });
+    });
+}
+
+// The compute units of the calling thread's device, asked once per device (256 when there is none to ask).
+static int i8_sk_cus()
+{
+    static std::atomic<int> seen[64];
+    int dev = 0, ncu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return 256; }
+    if ((ncu = seen[dev].load(std::memory_order_relaxed)) > 0) return ncu;
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1) { (void)hipGetLastError(); return 256; }
+    seen[dev].store(ncu, std::memory_order_relaxed);
+    return ncu;
+}
+
+// The slices the split-K launcher would cut K into now (i8_sk_slices with antq_debug_set key 24); cus < 1: the device's.
+extern "C" int antq_linear4_i8_sk_slices(size_t M, size_t N, size_t K, int cus)
+{
+    if (M == 0 || N == 0 || K == 0) return 0;
+    size_t per_slice;
+    return i8_sk_slices(M, N, K, cus >= 1 ? cus : i8_sk_cus(), g_knob_i8_split, per_slice);
+}
+
+extern "C" size_t antq_linear4_i8_sk_workspace_bytes(size_t M, size_t N, size_t K)
+{
+    const int S = antq_linear4_i8_sk_slices(M, N, K, 0);
+    return S <= 1 ? 0 : (((size_t)S * M * N * sizeof(int) + 15) & ~(size_t)15);
+}
+
+// antq_linear4_i8 for 1 .. ANTQ_LINEAR4_I8_SK_MAX_M rows with K split across workgroups (antq_k_linear_i8_sk.h): the same
+// checks in the same order, then the row limit, the workspace's alignment and -- the one check that asks the device, for its
+// number of compute units -- the workspace's size.  One launch when the rule says one slice, else the slices and the finish.
+extern "C" int antq_linear4_i8_sk(const uint8_t *codes, const int8_t *xq, const void *bias, void *y, size_t M, size_t N, size_t K,
+                                  const float *alpha_w, int per_row, int I_w, const int8_t *image_w, int m, int n_normal,
+                                  const float *alpha_x, int I_x, void *workspace, size_t workspace_bytes, unsigned flags, int dtype,
+                                  void *stream)
+{
+    const int rc = i8_checks(codes, xq, bias, y, M, N, K, alpha_w, I_w, image_w, m, n_normal, alpha_x, I_x, flags, dtype,
+                             ANTQ_LINEAR4_I8_SK_MAX_M, workspace);
+    if (rc != kLinearGo) return rc;
+    size_t per_slice;
+    const int S = i8_sk_slices(M, N, K, i8_sk_cus(), g_knob_i8_split, per_slice);
+    if (S > 1 && (!workspace || workspace_bytes < (size_t)S * M * N * sizeof(int))) return ANTQ_ERR_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool ovp = (flags & ANTQ_FLAG_OVP) != 0;
+    const dim3 blocks((unsigned)((N + kGemmBN - 1) / kGemmBN), (unsigned)S);
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return with_bool(ovp, [&](auto o) {
+            return with_value<1, 2, 4>(M <= 16 ? 1 : M <= 32 ? 2 : 4, [&](auto mm) {
+                return with_bool(S == 1, [&](auto direct) {
+                    launch_k(false, k_linear_i8_sk<T, decltype(o)::value, decltype(mm)::value, decltype(direct)::value>, blocks, dim3(256), 0,
+                             st, codes, xq, bias, y, static_cast<int *>(workspace), (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha_w,
+                             per_row ? 1 : 0, I_w, image_w, (uint32_t)m, ovp ? n_normal : 0, alpha_x, I_x, (uint32_t)per_slice);
+                    if constexpr (!decltype(direct)::value)
+                        launch_k(false, k_i8_sk_finish<T>, dim3((unsigned)((M * N + 255) / 256)), dim3(256), 0, st,
+                                 static_cast<const int *>(workspace), bias, y, (uint32_t)M, (uint32_t)N, (uint32_t)S, alpha_w,
+                                 per_row ? 1 : 0, I_w, alpha_x, I_x);
+                    return launch_status();
                 });
             });
         });

@@ -75,6 +75,26 @@ static inline void i8_shape(size_t M, size_t N, int forced_waves, int &waves, in
     mt = 4;
 }
 
+// The slices of K of the split-K form (antq_k_linear_i8_sk.h, M <= 64) on a part of `cus` compute units.  tiles = ceil(N / 64)
+// workgroups exist per slice, a slice is a whole number of 128-k stages:
+//   S = the smallest of 1, 2, 4, 8, 16 with tiles S >= 2 cus (16 when none has)      two workgroups per CU
+//   S <= K / (16 M)                           above it the 8 S M N bytes of partial traffic exceed the N K / 2 bytes of codes
+//   S <= stages; forced (antq_debug_set key 24, 1 .. 16) replaces the rule and is clamped to stages alone
+//   per_slice = ceil(stages / S) stages, and S becomes the number of non-empty slices, ceil(stages / per_slice)
+// The sum is exact, so no result depends on S: the rule is for time alone.
+static inline int i8_sk_slices(size_t M, size_t N, size_t K, int cus, int forced, size_t &per_slice)
+{
+    const size_t tiles = (N + 63) / 64, stages = (K + 127) / 128;
+    size_t S = 16;
+    for (size_t s = 1; s <= 16; s *= 2)
+        if (tiles * s >= 2 * (size_t)std::max(cus, 1)) { S = s; break; }
+    S = std::min(S, std::max<size_t>(K / (16 * M), 1));
+    if (forced >= 1) S = (size_t)std::min(forced, 16);
+    S = std::max<size_t>(std::min(S, stages), 1);
+    per_slice = (stages + S - 1) / S;
+    return (int)((stages + per_slice - 1) / per_slice);
+}
+
 // 8 nibbles (one code word: 8 consecutive k) -> their int8 image entries in k order, for a book of at most 16 values whose
 // image is the 16 bytes T[0] .. T[3]
 __device__ __forceinline__ void i8_decode_word(uint32_t w, const uint32_t (&T)[4], uint32_t &o0, uint32_t &o1)
@@ -86,6 +106,16 @@ __device__ __forceinline__ void i8_decode_word(uint32_t w, const uint32_t (&T)[4
     const uint32_t od = __builtin_amdgcn_perm(__builtin_amdgcn_perm(T[3], T[2], o7), __builtin_amdgcn_perm(T[1], T[0], o7), so);
     o0 = __builtin_amdgcn_perm(od, ev, 0x05010400u);
     o1 = __builtin_amdgcn_perm(od, ev, 0x07030602u);
+}
+
+// the int8 pair of code byte b under the decoder's pair rule (dec_pair): identifier 15 in one nibble -- that element is the
+// victim (0), its partner an outlier; g: the image, zero beyond m
+__device__ __forceinline__ uint16_t i8_pair_entry(uint32_t b, const uint8_t *g, uint32_t n_normal)
+{
+    const uint32_t c0 = b & 15u, c1 = b >> 4;
+    const uint32_t v0 = (c0 == 15u) ? 0u : g[(c1 == 15u) ? n_normal + c0 : c0];
+    const uint32_t v1 = (c1 == 15u) ? 0u : g[(c0 == 15u) ? n_normal + c1 : c1];
+    return (uint16_t)(v0 | (v1 << 8));
 }
 
 template <typename T, bool OVP, int WAVES, int MT>
@@ -167,13 +197,7 @@ k_linear_i8(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq, co
     sync();
     uint32_t img[4] = {0u, 0u, 0u, 0u};
     if constexpr (OVP) {
-        // the decoder's pair rule (dec_pair): identifier 15 in one nibble -- that element is the victim (0), its partner an outlier
-        for (uint32_t b = tid; b < 256u; b += (uint32_t)NTH) {
-            const uint32_t c0 = b & 15u, c1 = b >> 4;
-            const uint32_t v0 = (c0 == 15u) ? 0u : lds.g[(c1 == 15u) ? (uint32_t)n_normal + c0 : c0];
-            const uint32_t v1 = (c1 == 15u) ? 0u : lds.g[(c0 == 15u) ? (uint32_t)n_normal + c1 : c1];
-            lds.pair[b] = (uint16_t)(v0 | (v1 << 8));
-        }
+        for (uint32_t b = tid; b < 256u; b += (uint32_t)NTH) lds.pair[b] = i8_pair_entry(b, lds.g, (uint32_t)n_normal);
         sync();
     } else {
         const u32x4_t t = *reinterpret_cast<const u32x4_t *>(lds.g);

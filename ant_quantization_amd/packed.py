@@ -125,6 +125,14 @@ from today's output by that much.  The call is served only when lookup() served 
 enabled, per tensor, in neither `base` nor `outlier` mode, its book has an integer image, `I_x * I_w * K < 2^31` and the call
 qualifies; in every other case the forward proceeds exactly as without the option, same launches, same bits.  Conv1D entries,
 byte codes and ViT's attention wrapper are out of scope.  Measurements and verdict: profiles/int_linear4.md, DESIGN.md 5q.
+
+`integer_split_k=True` (needs fused_linear and integer_linear) sends the integer calls of at most `_lib.LINEAR4_I8_SK_MAX_M` = 64
+rows -- token generation, batched and speculative decode -- to `antq_linear4_i8_sk`, which cuts K across workgroups
+(`.int_linear_sk_calls`; they still count in `.int_linear_calls`).  The sum is an exact integer, so the bits are those of
+`antq_linear4_i8`: the flag changes launches and time, never a result.  The partial sums go through ONE workspace per device
+owned by the bank, grown on demand and, like the decode scratch, valid only until the next such call on the same stream.  A flag,
+not a rows option, for the reason `fused_conv1d_mm` is one.  Calls of more rows run `antq_linear4_i8` as before.  Measurements:
+profiles/int_linear4_sk.md, DESIGN.md 5r.
 """
 from collections import namedtuple
 
@@ -154,6 +162,7 @@ _OPTIONS = (
     _Option("fused_rows", None, ("fused_linear",), ("LINEAR4_MAX_M", "LINEAR4_MM_MAX_M")),
     _Option("fused_gemm_rows", None, ("fused_linear",), ("LINEAR4_MM_MAX_M", "LINEAR4_GEMM_MAX_M")),
     _Option("integer_linear", False, ("fused_linear",), None),
+    _Option("integer_split_k", False, ("fused_linear", "integer_linear"), None),
 )
 _NOTES = {("PackedBank", "keep_images"): " (nothing else computes from the codes)"}
 
@@ -218,7 +227,8 @@ def _settle(q):
 class PackedBank:
     def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True, fused_rows=None,
                  byte_codes=False, fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None,
-                 fused_conv1d=False, fused_conv1d_mm=False, fused_conv1d_gemm=False, integer_linear=False):
+                 fused_conv1d=False, fused_conv1d_mm=False, fused_conv1d_gemm=False, integer_linear=False,
+                 integer_split_k=False):
         """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict);
         a layer's code width is then the one its stored size says (numel / 2 bytes: 4-bit, numel bytes: byte codes).
         Every other parameter: see the module docstring."""
@@ -238,7 +248,9 @@ class PackedBank:
         self.entries = {}          # id(quantiser) -> dict
         self.skipped = []          # (layer name, reason): layers that keep their float weight and per-layer launch
         self.integer_skipped = []  # (layer name, reason): 4-bit Linear entries integer_linear does not serve
-        self.int_linear_calls = 0  # forwards antq_quant_i8 + antq_linear4_i8 served
+        self.int_linear_calls = 0  # forwards antq_quant_i8 + antq_linear4_i8 (or _sk) served
+        self.int_linear_sk_calls = 0  # ... of them through antq_linear4_i8_sk (integer_split_k)
+        self._sk_workspace = {}    # device -> the one workspace of antq_linear4_i8_sk, grown on demand
         self.launches = 0          # decode launches so far (one per (device, dtype, pair rule, code width) group and refresh)
         self.dirty = True
         self._batches = []
@@ -535,8 +547,19 @@ class PackedBank:
             e["unit_stamp"] = stamp
         xq = _lib.quant_i8(input, e["alpha_x"], plan_x, gmax_x, 1, input.numel(), False, plan_x.image_dev(dev), n_normal=nn_x, ovp=ovp_x)
         self.int_linear_calls += 1
-        return _lib.int_linear4(e["codes"], xq, e["unit_w"], plan_w.image_dev(dev), e["integer"], e["unit_x"], image_x[0], N, K,
-                                e["per_row"], e["dtype"], bias=None if mod.bias is None else mod.bias.detach(), n_normal=nn_w, ovp=ovp_w)
+        args = (e["codes"], xq, e["unit_w"], plan_w.image_dev(dev), e["integer"], e["unit_x"], image_x[0], N, K, e["per_row"], e["dtype"])
+        kw = dict(bias=None if mod.bias is None else mod.bias.detach(), n_normal=nn_w, ovp=ovp_w)
+        M = input.numel() // K
+        if getattr(self, "integer_split_k", False) and M <= _lib.LINEAR4_I8_SK_MAX_M:
+            # K split across workgroups: the same bits.  The bank's one workspace per device, like the decode scratch valid
+            # until the next such call on the same stream
+            need = _lib.int_linear4_sk_workspace_bytes(M, N, K, dev)
+            ws = self._sk_workspace.get(dev)
+            if ws is None or ws.numel() < need:
+                ws = self._sk_workspace[dev] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+            self.int_linear_sk_calls += 1
+            return _lib.int_linear4_sk(*args, workspace=ws, **kw)
+        return _lib.int_linear4(*args, **kw)
 
     def linear(self, mod, input, weight):
         """The output of a LinearQuantizer or Conv1dQuantizer whose weight quantiser this bank serves (fused_linear): `input`
@@ -604,7 +627,7 @@ def pack_model(model, release_weights=False, **options):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
     (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
     options: fused_linear, keep_images, fused_rows, byte_codes, fused_bytes, fused_byte_rows, fused_gemm_rows,
-    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear -- PackedBank's keywords with its defaults; see the module docstring."""
+    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k -- PackedBank's keywords with its defaults; see the module docstring."""
     return PackedBank(model, release_weights, None, **options)     # (codes: not an option here -- given, it is a TypeError)
 
 
@@ -633,7 +656,7 @@ def load_packed_state_dict(model, sd, release_weights=True, **options):
     any other size raises AntqError naming the layer), and the weights are materialised by the batched decode
     (release_weights=False: copied into the layers' own float weights instead of replacing them).
     options: fused_linear, keep_images, fused_rows, fused_bytes, fused_byte_rows, fused_gemm_rows, fused_byte_gemm_rows,
-    fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
+    fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
     _check_options("load_packed_state_dict", **options)        # (before the model is touched)
     suffix = "." + CODES_KEY
     codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}

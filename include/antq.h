@@ -935,6 +935,37 @@ int antq_linear4_i8(const uint8_t *codes_dev /* N*K/2 bytes, antq_encode4's layo
                     int dtype /* F32 | BF16 | F16: y and bias */, void *stream);
 
 /* -------------------------------------------------------------------------
+ * antq_linear4_i8_sk: antq_linear4_i8 for 1 .. ANTQ_LINEAR4_I8_SK_MAX_M rows of xq -- token generation, batched and
+ * speculative decode -- with K split across workgroups.  The formula, the operands and their rules are antq_linear4_i8's,
+ * and so are the bits: y equals what antq_linear4_i8 writes for the same arguments.  S is an exact int32 sum and has no
+ * order, so it does not depend on how K is cut: the launcher cuts K into 1 .. 16 slices of whole 128-k stages by the output
+ * rows, K, M and the device's number of compute units (csrc/antq_k_linear_i8.h: i8_sk_slices), every slice's workgroups
+ * write their int32 partial sums to the workspace, and a second small launch adds them as integers and applies the
+ * scales.  With one slice there is one launch and no workspace.  No atomics, no order between workgroups.
+ *
+ * antq_linear4_i8_sk_workspace_bytes: the bytes the launcher would use NOW for this call on the calling thread (its device,
+ * its antq_debug_set state): 0 with one slice, else 4 * slices * M * N rounded up to 16.  antq_linear4_i8_sk_slices: that
+ * number of slices; cus >= 1 answers for a part of that many compute units instead of the device's (0 for an empty call).
+ * The workspace's previous contents are never read; the call writes its first 4 * slices * M * N bytes and nothing beyond;
+ * they are scratch, free again when the call has finished on its stream.
+ *
+ * Refusals: antq_linear4_i8's, in its order, with the row limit M > ANTQ_LINEAR4_I8_SK_MAX_M among the ANTQ_ERR_UNSUPPORTED
+ * ones and a non-null workspace_dev that is not 16-byte aligned among the ANTQ_ERR_ALIGN ones; then, last,
+ *   ANTQ_ERR_ARG          the call needs a workspace and workspace_dev is null or workspace_bytes too small
+ * Every check but the last comes before anything touches HIP; the last asks the device for its number of compute units
+ * (once per device; 256 when there is none) and nothing else.  A refused call launches and writes nothing.  One or two
+ * launches, stream-ordered, capturable; no allocation.  Kernels: csrc/antq_k_linear_i8_sk.h.  Measurements:
+ * profiles/int_linear4_sk.md.
+ * ------------------------------------------------------------------------- */
+#define ANTQ_LINEAR4_I8_SK_MAX_M 64
+int antq_linear4_i8_sk_slices(size_t M, size_t N, size_t K, int cus);
+size_t antq_linear4_i8_sk_workspace_bytes(size_t M, size_t N, size_t K);
+int antq_linear4_i8_sk(const uint8_t *codes_dev, const int8_t *xq_dev, const void *bias_dev, void *y_dev, size_t M, size_t N, size_t K,
+                       const float *alpha_w_dev, int alpha_per_row, int I_w, const int8_t *image_w_dev, int m, int n_normal,
+                       const float *alpha_x_dev, int I_x, void *workspace_dev, size_t workspace_bytes,
+                       unsigned flags /* 0 | ANTQ_FLAG_OVP */, int dtype /* F32 | BF16 | F16: y and bias */, void *stream);
+
+/* -------------------------------------------------------------------------
  * OliVe's clip statistic on ONE read (replaces t.mean() + t.std() of olive_quantization/antquant/quant_modules.py:193-197
  * and :213-218, which read the tensor at least three times before the clip search reads it again).
  * antq_moments: sums_dev[2 r] = sum of x, sums_dev[2 r + 1] = sum of x^2 over row r (alpha_per_row) or over the whole

@@ -9,11 +9,14 @@ repetition; the median and the spread (max - min) / median are reported.
        (M <= 4096, 16-bit); float32 beyond 8 rows has none
     C  antq_fakequant + antq_decode4 into one scratch buffer + F.linear      (keep_images=False, a call no kernel serves)
     A  antq_fakequant + F.linear on the kept image
+    K  (--split-k) antq_quant_i8 + antq_linear4_i8_sk: K split across workgroups, at most 64 rows.  The rows are then 1, 8, 16, 64,
+       the tables compare K with every other arm, and --force 1,2,4,8,16 adds one arm per forced number of slices (knob 24)
 
 Layers [N, K]: 4096 x 4096, 16384 x 4096, 4096 x 16384, 3072 x 768, 768 x 3072; float32 and bfloat16; ANT flint-4 (signed) and OliVe
 int-4 with its outlier list, the same book on both operands, one scale per output row, one per input tensor, bias.
 
     python tools/probe_int_linear4.py [--quick] [--out profiles/int_linear4]      (writes .json and .md)
+    python tools/probe_int_linear4.py --split-k [--force 1,2,4,8,16] [--quick] --out profiles/int_linear4_sk
 """
 import argparse
 import json
@@ -30,6 +33,7 @@ from probe_linear4_t import ROTATE_BYTES, capture, alternate  # noqa: E402
 
 SHAPES = ((4096, 4096), (16384, 4096), (4096, 16384), (3072, 768), (768, 3072))
 MS = (1, 8, 64, 512, 4096)
+MS_SK = (1, 8, 16, 64)
 
 
 def books():
@@ -84,8 +88,53 @@ def write_md(rows, path, args):
         f.write("\n".join(out))
 
 
+def write_md_sk(rows, path, args):
+    """the --split-k form: K against I, R, C and A (times of K over the other arm's: below 1, K is faster)"""
+    others = ("i", "r", "c", "a")
+    out = ["# antq_quant_i8 + antq_linear4_i8_sk (K split across workgroups) at 1 ... 64 rows", "",
+           "Written by `tools/probe_int_linear4.py --split-k%s%s`: the protocol of profiles/int_linear4.md (one MI355X, one process, every "
+           "arm from the RAW input, rotating weight buffers, %d repetitions of one graph-replayed batch of calls per arm, the arms "
+           "alternated inside a repetition; medians in us per call, `spread` = the largest (max - min) / median of the point's arms)." % (
+               " --quick" if args.quick else "", " --force " + args.force if args.force else "", args.reps), "",
+           "K = antq_quant_i8 + antq_linear4_i8_sk with S slices by the launcher's rule; I, R, C, A as in profiles/int_linear4.md.  "
+           "K / X are TIMES: below 1, K is faster.  `won` counts the points where K is faster by more than the point's spread, "
+           "`lost` those where it is slower by more than it.", ""]
+    for dt in sorted({r["dtype"] for r in rows}):
+        rs = [r for r in rows if r["dtype"] == dt]
+        out += ["## Verdict in counts, %s" % dt, "", "| against | points | won | lost | K / X |", "|---|---|---|---|---|"]
+        for o in others:
+            rr = [r for r in rs if r.get("k_over_" + o) is not None]
+            if rr:
+                out.append("| %s | %d | %d | %d | %s |" % (o.upper(), len(rr), sum(r["k_over_" + o] < 1 - r["spread"] for r in rr),
+                                                         sum(r["k_over_" + o] > 1 + r["spread"] for r in rr), _range([r["k_over_" + o] for r in rr])))
+        out += ["", "Per M, K / I: " + "; ".join("M = %d: %s" % (M, _range([r["k_over_i"] for r in rs if r["M"] == M]))
+                                                  for M in MS_SK if any(r["M"] == M for r in rs)) + ".", ""]
+    forced = sorted({int(k[5:]) for r in rows for k in r if k.startswith("us_k_")})
+    keys = []
+    for r in rows:
+        if (r["dtype"], r["book"]) not in keys:
+            keys.append((r["dtype"], r["book"]))
+    for dt, book in keys:
+        out += ["## %s, %s" % (dt, book), "",
+                "| layer [N, K] | M | S | K | I | R | C | A | K / I | K / R | K / C | K / A |%s spread |" % "".join(" S = %d |" % f for f in forced),
+                "|---|---|---|---|---|---|---|---|---|---|---|---|%s---|" % ("---|" * len(forced))]
+        for r in rows:
+            if (r["dtype"], r["book"]) == (dt, book):
+                out.append("| [%d, %d] | %d | %d | %.1f | %.1f | %s | %.1f | %.1f | %.2f | %s | %.2f | %.2f |%s %.1f %% |" % (
+                    r["N"], r["K"], r["M"], r["slices"], r["us_k"], r["us_i"], "" if r["us_r"] is None else "%.1f" % r["us_r"], r["us_c"],
+                    r["us_a"], r["k_over_i"], "" if r["us_r"] is None else "%.2f" % r["k_over_r"], r["k_over_c"], r["k_over_a"],
+                    "".join(" %.1f |" % r["us_k_%d" % f] for f in forced), 100 * r["spread"]))
+        out.append("")
+    if args.notes and os.path.exists(args.notes):
+        out += [open(args.notes).read()]
+    with open(path, "w") as f:
+        f.write("\n".join(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--split-k", action="store_true", help="add arm K (antq_linear4_i8_sk) at 1, 8, 16, 64 rows; K's tables")
+    ap.add_argument("--force", default="", help="(--split-k) numbers of slices to force as arms of their own, e.g. 1,2,4,8,16")
     ap.add_argument("--quick", action="store_true", help="bfloat16, ANT flint-4, the first and the fourth layer only")
     ap.add_argument("--flop", type=float, default=3e11, help="operations per graph, about")
     ap.add_argument("--min-iters", type=int, default=4)
@@ -95,8 +144,10 @@ def main():
     ap.add_argument("--rewrite", default=None, help="a .json of an earlier run: write its .md again (no GPU needed) and stop")
     ap.add_argument("--out", default=None, help="path without extension: .json and .md are written (and rewritten after every layer)")
     a = ap.parse_args()
+    md = write_md_sk if a.split_k else write_md
+    forced = [int(v) for v in a.force.split(",") if v]
     if a.rewrite:
-        write_md(json.load(open(a.rewrite)), (a.out or os.path.splitext(a.rewrite)[0]) + ".md", a)
+        md(json.load(open(a.rewrite)), (a.out or os.path.splitext(a.rewrite)[0]) + ".md", a)
         return
     if not torch.cuda.is_available():
         raise SystemExit("probe_int_linear4: no GPU -- nothing is measured without one")
@@ -119,7 +170,7 @@ def main():
                 unit_w = packed._unit_alpha(alpha, plan, gmax)
                 scratch = torch.empty(N * K, dtype=dt, device=dev)
                 bias = torch.randn(N, device=dev).to(dt)
-                for M in MS:
+                for M in (MS_SK if a.split_k else MS):
                     iters = int(min(a.max_iters, max(a.min_iters, a.flop / (2.0 * M * N * K))))
                     n_img = int(min(iters, max(2, -(-ROTATE_BYTES // (K * N * esz)))))
                     n_cod = int(min(iters, max(2, -(-ROTATE_BYTES // (K * N // 2)))))
@@ -154,9 +205,23 @@ def main():
                         fq()
                         return F.linear(xf, images[i], bias)
 
+                    def arm_k(i, S=0):
+                        _lib.quant_i8(x, ax, plan, gmax, 1, M * K, False, img, n_normal=nn, ovp=ovp, out=xq)
+                        _lib.lib().antq_debug_set(24, S)
+                        try:
+                            return _lib.int_linear4_sk(codes[i], xq, unit_w, img, I, unit_x, I, N, K, True, dt, bias=bias, n_normal=nn, ovp=ovp,
+                                                       out=y, workspace=ws)
+                        finally:
+                            _lib.lib().antq_debug_set(24, 0)
+
                     graphs = {"I": capture(arm_i, n_cod, iters, 3), "C": capture(arm_c, n_cod, iters, 3), "A": capture(arm_a, n_img, iters, 3)}
                     if route:
                         graphs["R"] = capture(arm_r, n_cod, iters, 3)
+                    if a.split_k:
+                        ws = torch.empty(16 * 4 * M * N, dtype=torch.uint8, device=dev)
+                        graphs["K"] = capture(arm_k, n_cod, iters, 3)
+                        for S in forced:
+                            graphs["K%d" % S] = capture(lambda i, S=S: arm_k(i, S), n_cod, iters, 3)
                     t = alternate(graphs, iters, a.reps)
                     us = {k: v[0] for k, v in t.items()}
                     r = dict(dtype=str(dt).split(".")[1], book=bname, N=N, K=K, M=M, calls=iters, image_buffers=n_img, code_buffers=n_cod,
@@ -164,6 +229,10 @@ def main():
                              us_a=round(us["A"], 2), i_over_r=round(us["I"] / us["R"], 3) if route else None,
                              i_over_c=round(us["I"] / us["C"], 3), i_over_a=round(us["I"] / us["A"], 3),
                              tops=round(2.0 * M * N * K / (us["I"] * 1e-6) / 1e12, 1), spread=round(max(v[1] for v in t.values()), 4))
+                    if a.split_k:
+                        r.update(slices=_lib.lib().antq_linear4_i8_sk_slices(M, N, K, 0), us_k=round(us["K"], 2),
+                                 **{"k_over_" + o.lower(): round(us["K"] / us[o], 3) if o in us else None for o in "IRCA"},
+                                 **{"us_k_%d" % S: round(us["K%d" % S], 2) for S in forced})
                     rows.append(r)
                     print(json.dumps(r), flush=True)
                     del graphs, images, codes
@@ -173,7 +242,7 @@ def main():
                     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
                     with open(a.out + ".json", "w") as f:
                         json.dump(rows, f, indent=1)
-                    write_md(rows, a.out + ".md", a)
+                    md(rows, a.out + ".md", a)
 
 
 if __name__ == "__main__":
