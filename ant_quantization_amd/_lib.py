@@ -35,6 +35,8 @@ LINEAR8_MM_MAX_M = 64  # include/antq.h ANTQ_LINEAR8_MM_MAX_M: input rows antq_l
 LINEAR8_GEMM_MAX_M = 4096  # include/antq.h ANTQ_LINEAR8_GEMM_MAX_M: input rows antq_linear8_gemm takes
 LINEAR4_I8_MAX_M = 1 << 20  # include/antq.h ANTQ_LINEAR4_I8_MAX_M: rows of xq antq_linear4_i8 takes
 LINEAR4_I8_SK_MAX_M = 64  # include/antq.h ANTQ_LINEAR4_I8_SK_MAX_M: rows of xq antq_linear4_i8_sk takes
+LINEAR8_I8_MAX_M = 1 << 20  # include/antq.h ANTQ_LINEAR8_I8_MAX_M: rows of xq antq_linear8_i8 takes
+LINEAR8_I8_SK_MAX_M = 64  # include/antq.h ANTQ_LINEAR8_I8_SK_MAX_M: rows of xq antq_linear8_i8_sk takes
 PLAN_MAX_BYTES = 128 + 4 * MAX_GRID + 16 * 3072 + 20 * 1024 + 16 * 64
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16, torch.float64: F64}
@@ -75,7 +77,7 @@ def lib():
                              "antq_decode8_batch", "antq_linear8", "antq_linear8_mm", "antq_linear4_gemm",
                              "antq_linear8_gemm", "antq_linear4_t", "antq_linear4_t_mm", "antq_linear4_t_gemm", "antq_fakequant_outlier",
                              "antq_abs_order_stats", "antq_quant_i8", "antq_linear4_i8", "antq_linear4_i8_sk",
-                             "antq_linear4_i8_sk_slices"):
+                             "antq_linear4_i8_sk_slices", "antq_linear8_i8", "antq_linear8_i8_sk", "antq_linear8_i8_sk_slices"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
                 L.antq_decode4_batch_capacity.restype = ctypes.c_size_t
@@ -85,6 +87,7 @@ def lib():
                 L.antq_calibrate_batch_workspace_bytes.restype = ctypes.c_size_t
                 L.antq_abs_order_stats_workspace_bytes.restype = ctypes.c_size_t
                 L.antq_linear4_i8_sk_workspace_bytes.restype = ctypes.c_size_t
+                L.antq_linear8_i8_sk_workspace_bytes.restype = ctypes.c_size_t
                 # declared signatures: plain python ints go straight through (no per-call wrapper objects)
                 vp, sz, ci, cf, cu = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_float, ctypes.c_uint
                 L.antq_fakequant.argtypes = [vp, vp, vp, sz, sz, vp, ci, cf, vp, vp, cu, ci, vp]
@@ -113,6 +116,10 @@ def lib():
                 L.antq_linear4_i8_sk.argtypes = [vp, vp, vp, vp, sz, sz, sz, vp, ci, ci, vp, ci, ci, vp, ci, vp, sz, cu, ci, vp]
                 L.antq_linear4_i8_sk_workspace_bytes.argtypes = [sz, sz, sz]
                 L.antq_linear4_i8_sk_slices.argtypes = [sz, sz, sz, ci]
+                L.antq_linear8_i8.argtypes = [vp, vp, vp, vp, sz, sz, sz, vp, ci, ci, vp, vp, ci, vp, ci, cu, ci, vp]
+                L.antq_linear8_i8_sk.argtypes = [vp, vp, vp, vp, sz, sz, sz, vp, ci, ci, vp, vp, ci, vp, ci, vp, sz, cu, ci, vp]
+                L.antq_linear8_i8_sk_workspace_bytes.argtypes = [sz, sz, sz]
+                L.antq_linear8_i8_sk_slices.argtypes = [sz, sz, sz, ci]
                 # development: ANTQ_DEBUG_KNOBS="14=2,0=8" applies antq_debug_set(key, value) pairs to the loading thread
                 # (the knobs are thread-local; tools/fuzz_campaign.sh forces code paths with it)
                 for kv in [k for k in os.environ.get("ANTQ_DEBUG_KNOBS", "").split(",") if "=" in k]:
@@ -338,12 +345,23 @@ class Plan:
             self._image = grids.integer_image(self.grid)
         return self._image
 
-    def image_dev(self, device):
-        """The integer image's m bytes (int8) on `device`, next to grid_dev; the grid must have one."""
-        key = ("image", device.index if device.index is not None else torch.cuda.current_device())
+    def integer_image8(self):
+        """integer_image with I up to 128 (grids.integer_image(limit=128)): what the byte-code integer linear takes.  ANT's
+        signed 8-bit int book has one -- I = 128, the int8 values -128 .. 127 -- and none under the 127 limit; a book that has an
+        image under that limit has the same one here.  Found once."""
+        if not hasattr(self, "_image8"):
+            from . import grids
+            self._image8 = grids.integer_image(self.grid, limit=128)
+        return self._image8
+
+    def image_dev(self, device, limit=127):
+        """The integer image's m bytes (int8) on `device`, next to grid_dev; the grid must have one.  limit=128: the image of
+        integer_image8, under a key of its own."""
+        wide = limit == 128
+        key = ("image8" if wide else "image", device.index if device.index is not None else torch.cuda.current_device())
         t = self._dev.get(key)
         if t is None:
-            t = self._dev[key] = torch.from_numpy(self.integer_image()[1]).to(device)
+            t = self._dev[key] = torch.from_numpy((self.integer_image8() if wide else self.integer_image())[1]).to(device)
         return t
 
     def eval_host(self, d):
@@ -1231,8 +1249,9 @@ def quant_i8(x, alpha, plan, gmax, rows, row_len, per_row, image, n_normal=0, ov
     return out
 
 
-def _int_linear_args(codes, xq, alpha_w, image_w, alpha_x, N, K, per_row, dtype, bias, out):
-    """What int_linear4 and int_linear4_sk check alike.  Returns (dtype code, M, out)."""
+def _int_linear_args(codes, xq, alpha_w, image_w, alpha_x, N, K, per_row, dtype, bias, out, width=4):
+    """What int_linear4, int_linear4_sk, int_linear8 and int_linear8_sk check alike (width: bits per code).  Returns (dtype code,
+    M, out)."""
     for t, name in ((codes, "codes"), (xq, "xq"), (alpha_w, "alpha_w"), (image_w, "image_w"), (alpha_x, "alpha_x")):
         _require_gpu(t, name)
     dt = _DTYPES.get(dtype)
@@ -1241,8 +1260,8 @@ def _int_linear_args(codes, xq, alpha_w, image_w, alpha_x, N, K, per_row, dtype,
     if xq.dtype != torch.int8 or K <= 0 or xq.numel() % K != 0 or (xq.dim() and xq.shape[-1] != K) or not xq.is_contiguous():
         raise AntqError("xq must be a contiguous int8 tensor [..., K]")
     M = xq.numel() // K
-    if codes.dtype != torch.uint8 or codes.numel() * 2 != N * K:
-        raise AntqError("codes must be uint8 of N*K/2 bytes")
+    if codes.dtype != torch.uint8 or codes.numel() * 8 != N * K * width:
+        raise AntqError("codes must be uint8 of N*K%s bytes" % ("/2" if width == 4 else ""))
     if (alpha_w.dtype != torch.float32 or alpha_w.numel() < (N if per_row else 1) or alpha_x.dtype != torch.float32 or alpha_x.numel() < 1
             or image_w.dtype != torch.int8):
         raise AntqError("alpha_w must be float32, one per row (per_row) or one; alpha_x one float32; image_w int8")
@@ -1252,7 +1271,7 @@ def _int_linear_args(codes, xq, alpha_w, image_w, alpha_x, N, K, per_row, dtype,
             raise AntqError("bias must hold N elements of `dtype`")
     for t in (codes, alpha_w, image_w, alpha_x, bias, out):
         if t is not None and t.device != xq.device:
-            raise AntqError("every tensor of int_linear4 must live on one device")
+            raise AntqError("every tensor of int_linear%d must live on one device" % width)
     if out is None:
         out = torch.empty(tuple(xq.shape[:-1]) + (N,), dtype=dtype, device=xq.device)
     elif not (out.is_cuda and out.dtype == dtype and out.numel() == M * N and out.is_contiguous()):
@@ -1303,6 +1322,58 @@ def int_linear4_sk(codes, xq, alpha_w, image_w, I_w, alpha_x, I_x, N, K, per_row
                                       _stream_int(xq.device))
     if rc:
         _check(rc, "antq_linear4_i8_sk")
+    return out
+
+
+def _image_host(image_host, image_w):
+    """the host copy of a byte book's image as antq_linear8_i8 reads it: contiguous int8, as many bytes as the device copy"""
+    h = np.ascontiguousarray(image_host, dtype=np.int8).reshape(-1)
+    if h.size != image_w.numel():
+        raise AntqError("image_host must hold the %d bytes of image_w" % image_w.numel())
+    return h
+
+
+def int_linear8(codes, xq, alpha_w, image_w, image_host, I_w, alpha_x, I_x, N, K, per_row, dtype, bias=None, out=None):
+    """int_linear4's product from BYTE codes (antq_linear8_i8): codes uint8 [N, K] in encode8's layout, V[n, k] =
+    image_w[code] (a code past the image reads 0), plain books only.  image_w: the book's int8 image on the device
+    (Plan.image_dev(device, 128)); image_host: the same bytes as a numpy int8 array (Plan.integer_image8()[1]), read before the
+    launch to choose the decode -- one XOR per four weights for ANT's signed int8 book, an LDS table otherwise; the bits do not
+    depend on it.  I_w, I_x in 1 .. 128; xq may hold -128.  Everything else as int_linear4.  Returns [..., N]."""
+    dt, M, out = _int_linear_args(codes, xq, alpha_w, image_w, alpha_x, N, K, per_row, dtype, bias, out, width=8)
+    h = _image_host(image_host, image_w)
+    with _on_device(xq.device):
+        rc = lib().antq_linear8_i8(codes.data_ptr(), xq.data_ptr(), _ptr(bias), out.data_ptr(), M, N, K, alpha_w.data_ptr(),
+                                   1 if per_row else 0, I_w, h.ctypes.data, image_w.data_ptr(), h.size, alpha_x.data_ptr(), I_x, 0, dt,
+                                   _stream_int(xq.device))
+    if rc:
+        _check(rc, "antq_linear8_i8")
+    return out
+
+
+def int_linear8_sk_workspace_bytes(M, N, K, device=None):
+    """int_linear4_sk_workspace_bytes for int_linear8_sk (antq_linear8_i8_sk_workspace_bytes)."""
+    if device is None:
+        return int(lib().antq_linear8_i8_sk_workspace_bytes(M, N, K))
+    with _on_device(device):
+        return int(lib().antq_linear8_i8_sk_workspace_bytes(M, N, K))
+
+
+def int_linear8_sk(codes, xq, alpha_w, image_w, image_host, I_w, alpha_x, I_x, N, K, per_row, dtype, bias=None, out=None, workspace=None):
+    """int_linear8 for at most LINEAR8_I8_SK_MAX_M rows of xq with K split across workgroups (antq_linear8_i8_sk): the same
+    arguments, the same bits.  workspace: as for int_linear4_sk, of int_linear8_sk_workspace_bytes(M, N, K) bytes."""
+    dt, M, out = _int_linear_args(codes, xq, alpha_w, image_w, alpha_x, N, K, per_row, dtype, bias, out, width=8)
+    h = _image_host(image_host, image_w)
+    if workspace is None:
+        workspace = torch.empty(int_linear8_sk_workspace_bytes(M, N, K, xq.device), dtype=torch.uint8, device=xq.device)
+    elif not (workspace.is_cuda and workspace.device == xq.device and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise AntqError("workspace must be a contiguous uint8 tensor on xq's device")
+    with _on_device(xq.device):
+        rc = lib().antq_linear8_i8_sk(codes.data_ptr(), xq.data_ptr(), _ptr(bias), out.data_ptr(), M, N, K, alpha_w.data_ptr(),
+                                      1 if per_row else 0, I_w, h.ctypes.data, image_w.data_ptr(), h.size, alpha_x.data_ptr(), I_x,
+                                      workspace.data_ptr() if workspace.numel() else None, workspace.numel(), 0, dt,
+                                      _stream_int(xq.device))
+    if rc:
+        _check(rc, "antq_linear8_i8_sk")
     return out
 
 

@@ -14,6 +14,7 @@
 #include "antq_k_linear_t_gemm.h"
 #include "antq_k_linear_i8.h"
 #include "antq_k_linear_i8_sk.h"
+#include "antq_k_linear8_i8.h"
 
 #include <atomic>
 #include <type_traits>
@@ -843,6 +844,112 @@ extern "C" int antq_linear4_i8_sk(const uint8_t *codes, const int8_t *xq, const 
                     launch_k(false, k_linear_i8_sk<T, decltype(o)::value, decltype(mm)::value, decltype(direct)::value>, blocks, dim3(256), 0,
                              st, codes, xq, bias, y, static_cast<int *>(workspace), (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha_w,
                              per_row ? 1 : 0, I_w, image_w, (uint32_t)m, ovp ? n_normal : 0, alpha_x, I_x, (uint32_t)per_slice);
+                    if constexpr (!decltype(direct)::value)
+                        launch_k(false, k_i8_sk_finish<T>, dim3((unsigned)((M * N + 255) / 256)), dim3(256), 0, st,
+                                 static_cast<const int *>(workspace), bias, y, (uint32_t)M, (uint32_t)N, (uint32_t)S, alpha_w,
+                                 per_row ? 1 : 0, I_w, alpha_x, I_x);
+                    return launch_status();
+                });
+            });
+        });
+    });
+}
+
+// The checks the integer-domain byte-code entries share: i8_checks' order and codes with bytes in place of nibbles -- the
+// host copy of the image is required, the pair rule is refused (no pair-rule byte book has an int8 image), m <= 256 and
+// I <= 128 (kLinearGo: launch).
+static int i8b_checks(const uint8_t *codes, const int8_t *xq, const void *bias, void *y, size_t M, size_t N, size_t K, const float *alpha_w,
+                      int I_w, const int8_t *image_w_host, const int8_t *image_w, int m, const float *alpha_x, int I_x, unsigned flags,
+                      int dtype, size_t max_m, const void *workspace)
+{
+    if (!codes || !xq || !y || !alpha_w || !image_w_host || !image_w || !alpha_x || m < 1) return ANTQ_ERR_ARG;
+    if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_ARG;
+    if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
+    if (M == 0 || N == 0) return ANTQ_OK;
+    if (K == 0 || K % 32 != 0 || M > max_m) return ANTQ_ERR_UNSUPPORTED;
+    if ((flags & ANTQ_FLAG_OVP) || m > 256) return ANTQ_ERR_UNSUPPORTED;
+    if (N > 0x7fffffffull || K > 0x7fffffe0ull) return ANTQ_ERR_UNSUPPORTED;      // (rows and row length in 32 bits)
+    if (I_x < 1 || I_x > 128 || I_w < 1 || I_w > 128) return ANTQ_ERR_UNSUPPORTED;
+    if ((uint64_t)I_x * (uint64_t)I_w * (uint64_t)K >= (1ull << 31)) return ANTQ_ERR_UNSUPPORTED;      // (the sum could leave int32)
+    const uintptr_t esz = dtype == ANTQ_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(xq) % 16 || reinterpret_cast<uintptr_t>(codes) % 16 || reinterpret_cast<uintptr_t>(y) % esz ||
+        reinterpret_cast<uintptr_t>(bias) % esz || reinterpret_cast<uintptr_t>(alpha_w) % 4 || reinterpret_cast<uintptr_t>(alpha_x) % 4 ||
+        reinterpret_cast<uintptr_t>(workspace) % 16)
+        return ANTQ_ERR_ALIGN;
+    return kLinearGo;
+}
+
+// The integer-domain byte-code linear (antq_k_linear8_i8.h): antq_linear4_i8's formula on byte codes.  The decode kind comes
+// from the host copy of the image, read here before the launch; tile shape and knob 23 as for antq_linear4_i8.
+extern "C" int antq_linear8_i8(const uint8_t *codes, const int8_t *xq, const void *bias, void *y, size_t M, size_t N, size_t K,
+                               const float *alpha_w, int per_row, int I_w, const int8_t *image_w_host, const int8_t *image_w, int m,
+                               const float *alpha_x, int I_x, unsigned flags, int dtype, void *stream)
+{
+    const int rc = i8b_checks(codes, xq, bias, y, M, N, K, alpha_w, I_w, image_w_host, image_w, m, alpha_x, I_x, flags, dtype,
+                              ANTQ_LINEAR8_I8_MAX_M, nullptr);
+    if (rc != kLinearGo) return rc;
+    const bool table = !i8b_image_is_xor(image_w_host, m);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int waves, mt;
+    i8_shape(M, N, one_of<2, 4>(g_knob_gemm_tile, 0), waves, mt);
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return with_bool(table, [&](auto tb) {
+            return with_value<2, 4>(waves, [&](auto wv) {
+                return with_value<4, 2>(mt, [&](auto mm) {
+                    constexpr int WAVES = decltype(wv)::value, MT = decltype(mm)::value;
+                    if constexpr (WAVES == 4 && MT == 2) return (int)ANTQ_ERR_UNSUPPORTED;      // (no such shape: i8_shape)
+                    else {
+                        constexpr size_t BM = (size_t)16 * MT * WAVES;
+                        const dim3 blocks((unsigned)((N + kGemmBN - 1) / kGemmBN), (unsigned)((M + BM - 1) / BM));
+                        launch_k(false, k_linear8_i8<T, decltype(tb)::value, WAVES, MT>, blocks, dim3(64u * WAVES), 0, st, codes, xq, bias,
+                                 y, (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha_w, per_row ? 1 : 0, I_w, image_w, (uint32_t)m, alpha_x, I_x);
+                        return launch_status();
+                    }
+                });
+            });
+        });
+    });
+}
+
+// The slices antq_linear8_i8_sk would cut K into now (i8b_sk_slices with antq_debug_set key 24); cus < 1: the device's.
+extern "C" int antq_linear8_i8_sk_slices(size_t M, size_t N, size_t K, int cus)
+{
+    if (M == 0 || N == 0 || K == 0) return 0;
+    size_t per_slice;
+    return i8b_sk_slices(M, N, K, cus >= 1 ? cus : i8_sk_cus(), g_knob_i8_split, per_slice);
+}
+
+extern "C" size_t antq_linear8_i8_sk_workspace_bytes(size_t M, size_t N, size_t K)
+{
+    const int S = antq_linear8_i8_sk_slices(M, N, K, 0);
+    return S <= 1 ? 0 : (((size_t)S * M * N * sizeof(int) + 15) & ~(size_t)15);
+}
+
+// antq_linear8_i8 for 1 .. ANTQ_LINEAR8_I8_SK_MAX_M rows with K split across workgroups (antq_k_linear8_i8.h): the same
+// checks, the workspace's alignment among them, then -- the one check that asks the device -- the workspace's size.
+extern "C" int antq_linear8_i8_sk(const uint8_t *codes, const int8_t *xq, const void *bias, void *y, size_t M, size_t N, size_t K,
+                                  const float *alpha_w, int per_row, int I_w, const int8_t *image_w_host, const int8_t *image_w, int m,
+                                  const float *alpha_x, int I_x, void *workspace, size_t workspace_bytes, unsigned flags, int dtype,
+                                  void *stream)
+{
+    const int rc = i8b_checks(codes, xq, bias, y, M, N, K, alpha_w, I_w, image_w_host, image_w, m, alpha_x, I_x, flags, dtype,
+                              ANTQ_LINEAR8_I8_SK_MAX_M, workspace);
+    if (rc != kLinearGo) return rc;
+    const bool table = !i8b_image_is_xor(image_w_host, m);
+    size_t per_slice;
+    const int S = i8b_sk_slices(M, N, K, i8_sk_cus(), g_knob_i8_split, per_slice);
+    if (S > 1 && (!workspace || workspace_bytes < (size_t)S * M * N * sizeof(int))) return ANTQ_ERR_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 blocks((unsigned)((N + kGemmBN - 1) / kGemmBN), (unsigned)S);
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return with_bool(table, [&](auto tb) {
+            return with_value<1, 2, 4>(M <= 16 ? 1 : M <= 32 ? 2 : 4, [&](auto mm) {
+                return with_bool(S == 1, [&](auto direct) {
+                    launch_k(false, k_linear8_i8_sk<T, decltype(tb)::value, decltype(mm)::value, decltype(direct)::value>, blocks, dim3(256),
+                             0, st, codes, xq, bias, y, static_cast<int *>(workspace), (uint32_t)M, (uint32_t)N, (uint32_t)K, alpha_w,
+                             per_row ? 1 : 0, I_w, image_w, (uint32_t)m, alpha_x, I_x, (uint32_t)per_slice);
                     if constexpr (!decltype(direct)::value)
                         launch_k(false, k_i8_sk_finish<T>, dim3((unsigned)((M * N + 255) / 256)), dim3(256), 0, st,
                                  static_cast<const int *>(workspace), bias, y, (uint32_t)M, (uint32_t)N, (uint32_t)S, alpha_w,

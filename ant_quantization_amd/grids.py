@@ -211,20 +211,24 @@ def olive_grid(mode, bit, signed):
 # ------------------------------------------------------------------------------------
 # integer images (the integer-domain linear: packed.pack_model(integer_linear=True))
 # ------------------------------------------------------------------------------------
-def integer_image(values):
-    """(I, int8 array) with values[i] / max|values| = array[i] / I: I the smallest integer in 1 .. 127 for which every
+def integer_image(values, limit=127):
+    """(I, int8 array) with values[i] / max|values| = array[i] / I: I the smallest integer in 1 .. limit for which every
     values[i] / max|values| * I (float64) lies within 1e-5 of an integer, the array those integers in the grid's own order.
     None when there is no such I, the book is empty or all zero, or a value is not finite.  For an OliVe book `values` is
-    cat(normal, outliers) (the normal values alone when the outlier list is empty)."""
+    cat(normal, outliers) (the normal values alone when the outlier list is empty).  limit: 127, or 128 for the byte-code
+    integer linear (packed.pack_model(integer_bytes=True)) -- I = 128 is taken only when no value is +128, as for ANT's signed
+    8-bit int book, whose image is -128 .. 127."""
+    if not 1 <= limit <= 128:
+        raise ValueError("integer_image: limit must lie in 1 .. 128")
     v = np.asarray(values, dtype=np.float64).reshape(-1)
     if v.size == 0 or not np.all(np.isfinite(v)):
         return None
     vmax = float(np.max(np.abs(v)))
     if vmax == 0.0:
         return None
-    for I in range(1, 128):
+    for I in range(1, limit + 1):
         t = v / vmax * I
         r = np.rint(t)
-        if np.all(np.abs(t - r) <= 1e-5):
+        if np.all(np.abs(t - r) <= 1e-5) and r.max() <= 127:
             return I, (r + 0.0).astype(np.int8)        # (+ 0.0: a book's -0 is 0)
     return None

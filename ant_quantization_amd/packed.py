@@ -133,6 +133,19 @@ rows -- token generation, batched and speculative decode -- to `antq_linear4_i8_
 owned by the bank, grown on demand and, like the decode scratch, valid only until the next such call on the same stream.  A flag,
 not a rows option, for the reason `fused_conv1d_mm` is one.  Calls of more rows run `antq_linear4_i8` as before.  Measurements:
 profiles/int_linear4_sk.md, DESIGN.md 5r.
+
+`integer_bytes=True` (needs fused_linear, fused_bytes and integer_linear) extends the integer contract to the byte-coded Linear
+entries -- the 8-bit layers of ANT's mixed-precision recipe (`set_8_bit_layer_n` / `_l`): W8A8 on the int8 matrix cores.  Such an
+entry is integer-fusable when it is fusable, K is a multiple of 32, its book is plain and has an int8 image with I up to 128
+(`Plan.integer_image8`: ANT int 5 to 8 bit signed, 5 to 7 bit unsigned, signed flint5; not unsigned int8, whose 255 levels need
+a row-sum correction, nor flint6 and wider, pot / float books of 5 bits or more, or OliVe's byte books); every other byte-coded
+entry is listed in `.integer_skipped` with its reason, and so is one whose calibrated input quantiser has no such image.  Its
+forward quantises the raw input with the input book's 128-limit image (an 8-bit signed `int` activation quantiser qualifies:
+xq may hold -128) and runs `antq_linear8_i8` -- for ANT's signed int8 book the code is the weight plus 128, one XOR per four
+weights in front of the MFMA; other books go through an LDS table -- or, with `integer_split_k` and at most 64 rows,
+`antq_linear8_i8_sk` on the bank's workspace (`.int_linear_byte_calls`, `.int_linear_byte_sk_calls`; both also count in
+`.int_linear_calls` / `.int_linear_sk_calls`).  With the option off every path takes today's launches and gives today's bits.
+Measurements and verdict: profiles/int_linear8.md, DESIGN.md 5s.
 """
 from collections import namedtuple
 
@@ -163,6 +176,7 @@ _OPTIONS = (
     _Option("fused_gemm_rows", None, ("fused_linear",), ("LINEAR4_MM_MAX_M", "LINEAR4_GEMM_MAX_M")),
     _Option("integer_linear", False, ("fused_linear",), None),
     _Option("integer_split_k", False, ("fused_linear", "integer_linear"), None),
+    _Option("integer_bytes", False, ("fused_linear", "fused_bytes", "integer_linear"), None),
 )
 _NOTES = {("PackedBank", "keep_images"): " (nothing else computes from the codes)"}
 
@@ -228,7 +242,7 @@ class PackedBank:
     def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True, fused_rows=None,
                  byte_codes=False, fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None,
                  fused_conv1d=False, fused_conv1d_mm=False, fused_conv1d_gemm=False, integer_linear=False,
-                 integer_split_k=False):
+                 integer_split_k=False, integer_bytes=False):
         """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict);
         a layer's code width is then the one its stored size says (numel / 2 bytes: 4-bit, numel bytes: byte codes).
         Every other parameter: see the module docstring."""
@@ -247,10 +261,12 @@ class PackedBank:
         self._scratch = {}         # (device, dtype) -> the one decode buffer of the layers without an image
         self.entries = {}          # id(quantiser) -> dict
         self.skipped = []          # (layer name, reason): layers that keep their float weight and per-layer launch
-        self.integer_skipped = []  # (layer name, reason): 4-bit Linear entries integer_linear does not serve
+        self.integer_skipped = []  # (layer name, reason): 4-bit Linear entries integer_linear does not serve (integer_bytes: and byte-coded entries)
         self.int_linear_calls = 0  # forwards antq_quant_i8 + antq_linear4_i8 (or _sk) served
         self.int_linear_sk_calls = 0  # ... of them through antq_linear4_i8_sk (integer_split_k)
-        self._sk_workspace = {}    # device -> the one workspace of antq_linear4_i8_sk, grown on demand
+        self.int_linear_byte_calls = 0  # ... of int_linear_calls, those from byte codes: antq_linear8_i8 (or _sk) (integer_bytes)
+        self.int_linear_byte_sk_calls = 0  # ... of them through antq_linear8_i8_sk
+        self._sk_workspace = {}    # device -> the one workspace of antq_linear4_i8_sk / antq_linear8_i8_sk, grown on demand
         self.launches = 0          # decode launches so far (one per (device, dtype, pair rule, code width) group and refresh)
         self.dirty = True
         self._batches = []
@@ -299,6 +315,12 @@ class PackedBank:
                         integer = plan.integer_image()[0]
                     else:
                         self.integer_skipped.append((name, why))
+                elif self.integer_linear and self.integer_bytes and width == 8:
+                    why = self._byte_integer_refusal(mod, w, plan, ovp, kind == "linear" and fusable)
+                    if why is None:
+                        integer = plan.integer_image8()[0]
+                    else:
+                        self.integer_skipped.append((name, why))
                 self.entries[id(q)] = dict(name=name, q=q, mod=mod, rows=rows, row_len=row_len, per_row=per_row, codes=c, width=width,
                                            fusable=fusable, kind=kind, shape=tuple(w.shape), dtype=w.dtype, device=w.device, integer=integer,
                                            out=torch.empty_like(w, memory_format=torch.contiguous_format) if image else None)
@@ -320,6 +342,25 @@ class PackedBank:
 
     def __reduce__(self):
         return (type(None), ())
+
+    @staticmethod
+    def _byte_integer_refusal(mod, w, plan, ovp, fusable):
+        """(integer_bytes) Why a byte-coded entry is not integer-fusable (None: it is).  The input quantiser is looked at as
+        well when it is calibrated already -- integer_linear_call asks again at every call."""
+        if not fusable:
+            return "not a fusable Linear layer"
+        if w.shape[1] % 32:
+            return "K = %d is not a multiple of 32" % w.shape[1]
+        if ovp:
+            return "a pair-rule byte book has no integer image"
+        if plan.integer_image8() is None:
+            return "the weight's codebook has no integer image"
+        qi = getattr(mod, "quant_input", None)
+        if qi is not None and getattr(qi, "_steady", False) and qi.mode not in ("base", "outlier"):
+            plan_x, _, _, ovp_x = _codebook(qi)
+            if ovp_x or plan_x.integer_image8() is None:
+                return "the input's codebook has no integer image"
+        return None
 
     @staticmethod
     def _unsuitable(q, w, byte_codes=False):
@@ -532,8 +573,9 @@ class PackedBank:
                 and input.numel() // K <= _lib.LINEAR4_I8_MAX_M):
             return None
         plan_x, gmax_x, nn_x, ovp_x = _codebook(qi)
-        image_x = plan_x.integer_image()
-        if image_x is None or image_x[0] * e["integer"] * K >= 2 ** 31:
+        wide = e["width"] == 8             # (integer_bytes) byte codes: images with I up to 128, plain books on both sides
+        image_x = plan_x.integer_image8() if wide else plan_x.integer_image()
+        if image_x is None or image_x[0] * e["integer"] * K >= 2 ** 31 or (wide and ovp_x):
             return None
         e.pop("served", None)
         plan_w, gmax_w, nn_w, ovp_w = _codebook(q)
@@ -545,8 +587,11 @@ class PackedBank:
                 e["unit_x"] = _unit_alpha(qi.alpha.to(dev), plan_x, gmax_x)
                 e["alpha_x"] = qi.alpha.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
             e["unit_stamp"] = stamp
-        xq = _lib.quant_i8(input, e["alpha_x"], plan_x, gmax_x, 1, input.numel(), False, plan_x.image_dev(dev), n_normal=nn_x, ovp=ovp_x)
+        xq = _lib.quant_i8(input, e["alpha_x"], plan_x, gmax_x, 1, input.numel(), False, plan_x.image_dev(dev, 128 if wide else 127),
+                           n_normal=nn_x, ovp=ovp_x)
         self.int_linear_calls += 1
+        if wide:
+            return self._integer_byte_call(e, mod, xq, plan_w, image_x[0], input.numel() // K)
         args = (e["codes"], xq, e["unit_w"], plan_w.image_dev(dev), e["integer"], e["unit_x"], image_x[0], N, K, e["per_row"], e["dtype"])
         kw = dict(bias=None if mod.bias is None else mod.bias.detach(), n_normal=nn_w, ovp=ovp_w)
         M = input.numel() // K
@@ -560,6 +605,24 @@ class PackedBank:
             self.int_linear_sk_calls += 1
             return _lib.int_linear4_sk(*args, workspace=ws, **kw)
         return _lib.int_linear4(*args, **kw)
+
+    def _integer_byte_call(self, e, mod, xq, plan_w, I_x, M):
+        """(integer_bytes) integer_linear_call's product for a byte-coded entry: antq_linear8_i8, or its split-K form."""
+        N, K = e["shape"]
+        dev = e["device"]
+        args = (e["codes"], xq, e["unit_w"], plan_w.image_dev(dev, 128), plan_w.integer_image8()[1], e["integer"], e["unit_x"], I_x,
+                N, K, e["per_row"], e["dtype"])
+        bias = None if mod.bias is None else mod.bias.detach()
+        self.int_linear_byte_calls += 1
+        if getattr(self, "integer_split_k", False) and M <= _lib.LINEAR8_I8_SK_MAX_M:
+            need = _lib.int_linear8_sk_workspace_bytes(M, N, K, dev)
+            ws = self._sk_workspace.get(dev)
+            if ws is None or ws.numel() < need:
+                ws = self._sk_workspace[dev] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+            self.int_linear_sk_calls += 1
+            self.int_linear_byte_sk_calls += 1
+            return _lib.int_linear8_sk(*args, bias=bias, workspace=ws)
+        return _lib.int_linear8(*args, bias=bias)
 
     def linear(self, mod, input, weight):
         """The output of a LinearQuantizer or Conv1dQuantizer whose weight quantiser this bank serves (fused_linear): `input`
@@ -627,7 +690,7 @@ def pack_model(model, release_weights=False, **options):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
     (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
     options: fused_linear, keep_images, fused_rows, byte_codes, fused_bytes, fused_byte_rows, fused_gemm_rows,
-    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k -- PackedBank's keywords with its defaults; see the module docstring."""
+    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes -- PackedBank's keywords with its defaults; see the module docstring."""
     return PackedBank(model, release_weights, None, **options)     # (codes: not an option here -- given, it is a TypeError)
 
 
@@ -656,7 +719,7 @@ def load_packed_state_dict(model, sd, release_weights=True, **options):
     any other size raises AntqError naming the layer), and the weights are materialised by the batched decode
     (release_weights=False: copied into the layers' own float weights instead of replacing them).
     options: fused_linear, keep_images, fused_rows, fused_bytes, fused_byte_rows, fused_gemm_rows, fused_byte_gemm_rows,
-    fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
+    fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
     _check_options("load_packed_state_dict", **options)        # (before the model is touched)
     suffix = "." + CODES_KEY
     codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}

@@ -966,6 +966,41 @@ int antq_linear4_i8_sk(const uint8_t *codes_dev, const int8_t *xq_dev, const voi
                        unsigned flags /* 0 | ANTQ_FLAG_OVP */, int dtype /* F32 | BF16 | F16: y and bias */, void *stream);
 
 /* -------------------------------------------------------------------------
+ * The integer-domain BYTE-code linear: antq_linear8_i8 and its split-K form antq_linear8_i8_sk.  antq_linear4_i8's contract
+ * with bytes in place of nibbles, for the 5- to 8-bit layers of a mixed-precision model (W8A8 on the int8 matrix cores):
+ *     v[n, k] = image_w[code[n, k]], a code >= m reads 0;  S, u_x, u_w[n] and y[m, n] exactly as stated at antq_linear4_i8.
+ * The image of a byte book may use I up to 128: ANT's signed 8-bit `int` book is the int8 values -128 .. 127 in code order
+ * with I = 128, and xq may hold -128.  Plain books only: no pair-rule byte book has an int8 image.
+ * image_w_host: the same m bytes on the host, read before the launch to choose the decode kind -- XOR when m == 256 and
+ * image[c] == c - 128 for every c (four weights per v_xor_b32), else a 256-byte LDS table with one look-up per weight.  The
+ * result does not depend on the kind.
+ * Refusals: antq_linear4_i8's, in its order, with these differences:
+ *   ANTQ_ERR_ARG          image_w_host null as well
+ *   ANTQ_ERR_UNSUPPORTED  in place of the 4-bit decoder's book refusals: ANTQ_FLAG_OVP, m > 256;
+ *                         I_x or I_w outside 1 .. 128; I_x * I_w * K >= 2^31
+ * (K % 32 != 0, the row limits ANTQ_LINEAR8_I8_MAX_M / ANTQ_LINEAR8_I8_SK_MAX_M, the 16-byte alignment of xq_dev and codes_dev
+ * and everything else as there.)  antq_linear8_i8_sk, _sk_slices and _sk_workspace_bytes are to antq_linear8_i8 what
+ * antq_linear4_i8_sk and its two helpers are to antq_linear4_i8: the same bits, 1 .. 16 slices of K, a caller-owned workspace
+ * of 4 * slices * M * N bytes (rounded up to 16) whose size is the one check after the device is asked.  The slice rule is
+ * antq_linear4_i8_sk's with the cap K / (8 M): byte codes are N K bytes of traffic, not N K / 2.  antq_debug_set keys 23
+ * (tile) and 24 (slices) act on these entries as on the 4-bit ones.  One or two launches, stream-ordered, capturable; no
+ * atomics, no allocation.  Kernels: csrc/antq_k_linear8_i8.h.  Measurements: profiles/int_linear8.md.
+ * ------------------------------------------------------------------------- */
+#define ANTQ_LINEAR8_I8_MAX_M (1 << 20)
+#define ANTQ_LINEAR8_I8_SK_MAX_M 64
+int antq_linear8_i8(const uint8_t *codes_dev /* N*K bytes, antq_encode8's layout */, const int8_t *xq_dev /* [M, K] */,
+                    const void *bias_dev /* N or NULL */, void *y_dev /* [M, N] */, size_t M, size_t N, size_t K,
+                    const float *alpha_w_dev, int alpha_per_row, int I_w, const int8_t *image_w_host /* m bytes */,
+                    const int8_t *image_w_dev /* the same m bytes */, int m, const float *alpha_x_dev /* one float */, int I_x,
+                    unsigned flags /* 0 */, int dtype /* F32 | BF16 | F16: y and bias */, void *stream);
+int antq_linear8_i8_sk_slices(size_t M, size_t N, size_t K, int cus);
+size_t antq_linear8_i8_sk_workspace_bytes(size_t M, size_t N, size_t K);
+int antq_linear8_i8_sk(const uint8_t *codes_dev, const int8_t *xq_dev, const void *bias_dev, void *y_dev, size_t M, size_t N, size_t K,
+                       const float *alpha_w_dev, int alpha_per_row, int I_w, const int8_t *image_w_host, const int8_t *image_w_dev,
+                       int m, const float *alpha_x_dev, int I_x, void *workspace_dev, size_t workspace_bytes,
+                       unsigned flags /* 0 */, int dtype /* F32 | BF16 | F16: y and bias */, void *stream);
+
+/* -------------------------------------------------------------------------
  * OliVe's clip statistic on ONE read (replaces t.mean() + t.std() of olive_quantization/antquant/quant_modules.py:193-197
  * and :213-218, which read the tensor at least three times before the clip search reads it again).
  * antq_moments: sums_dev[2 r] = sum of x, sums_dev[2 r + 1] = sum of x^2 over row r (alpha_per_row) or over the whole
