@@ -36,6 +36,9 @@ LINEAR8_GEMM_MAX_M = 4096  # include/antq.h ANTQ_LINEAR8_GEMM_MAX_M: input rows 
 LINEAR4_I8_MAX_M = 1 << 20  # include/antq.h ANTQ_LINEAR4_I8_MAX_M: rows of xq antq_linear4_i8 takes
 LINEAR4_I8_SK_MAX_M = 64  # include/antq.h ANTQ_LINEAR4_I8_SK_MAX_M: rows of xq antq_linear4_i8_sk takes
 LINEAR8_I8_MAX_M = 1 << 20  # include/antq.h ANTQ_LINEAR8_I8_MAX_M: rows of xq antq_linear8_i8 takes
+CONV2D4_I8_MAX_DIM = 8191   # include/antq.h ANTQ_CONV2D4_I8_MAX_DIM: H, W, R, S, strides, paddings, dilations of antq_conv2d4_i8
+CONV2D4_I8_MAX_M = 1 << 22  # include/antq.h ANTQ_CONV2D4_I8_MAX_M: output positions B * Ho * Wo
+CONV2D4_I8_MAX_XQ_BYTES = 0x7fffffff  # include/antq.h ANTQ_CONV2D4_I8_MAX_XQ_BYTES: bytes of xq
 LINEAR8_I8_SK_MAX_M = 64  # include/antq.h ANTQ_LINEAR8_I8_SK_MAX_M: rows of xq antq_linear8_i8_sk takes
 PLAN_MAX_BYTES = 128 + 4 * MAX_GRID + 16 * 3072 + 20 * 1024 + 16 * 64
 
@@ -77,7 +80,8 @@ def lib():
                              "antq_decode8_batch", "antq_linear8", "antq_linear8_mm", "antq_linear4_gemm",
                              "antq_linear8_gemm", "antq_linear4_t", "antq_linear4_t_mm", "antq_linear4_t_gemm", "antq_fakequant_outlier",
                              "antq_abs_order_stats", "antq_quant_i8", "antq_linear4_i8", "antq_linear4_i8_sk",
-                             "antq_linear4_i8_sk_slices", "antq_linear8_i8", "antq_linear8_i8_sk", "antq_linear8_i8_sk_slices"):
+                             "antq_linear4_i8_sk_slices", "antq_linear8_i8", "antq_linear8_i8_sk", "antq_linear8_i8_sk_slices",
+                             "antq_conv2d4_i8"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
                 L.antq_decode4_batch_capacity.restype = ctypes.c_size_t
@@ -120,6 +124,7 @@ def lib():
                 L.antq_linear8_i8_sk.argtypes = [vp, vp, vp, vp, sz, sz, sz, vp, ci, ci, vp, vp, ci, vp, ci, vp, sz, cu, ci, vp]
                 L.antq_linear8_i8_sk_workspace_bytes.argtypes = [sz, sz, sz]
                 L.antq_linear8_i8_sk_slices.argtypes = [sz, sz, sz, ci]
+                L.antq_conv2d4_i8.argtypes = [vp, vp, vp, vp, sz, sz, sz, sz, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, ci, ci, vp, ci, vp, ci, cu, ci, vp]
                 # development: ANTQ_DEBUG_KNOBS="14=2,0=8" applies antq_debug_set(key, value) pairs to the loading thread
                 # (the knobs are thread-local; tools/fuzz_campaign.sh forces code paths with it)
                 for kv in [k for k in os.environ.get("ANTQ_DEBUG_KNOBS", "").split(",") if "=" in k]:
@@ -1292,6 +1297,57 @@ def int_linear4(codes, xq, alpha_w, image_w, I_w, alpha_x, I_x, N, K, per_row, d
                                    FLAG_OVP if ovp else 0, dt, _stream_int(xq.device))
     if rc:
         _check(rc, "antq_linear4_i8")
+    return out
+
+
+def _pair(v):
+    """an int or a pair of ints -> (int, int)"""
+    a, b = (v, v) if isinstance(v, int) else tuple(v)
+    return int(a), int(b)
+
+
+def int_conv2d4(codes, xq, alpha_w, image_w, I_w, alpha_x, I_x, N, kernel_size, stride, padding, dilation, per_row, dtype, bias=None,
+                out=None):
+    """conv2d (groups = 1) in the integer domain as an implicit GEMM from 4-bit codes (antq_conv2d4_i8): int_linear4's formula
+    with S summed over the receptive field, taps outside the image contributing 0.  xq: contiguous int8 [B, H, W, C] -- quant_i8
+    of a channels-last input seen as NHWC; codes: the weight's codes viewed as [N][R][S][C] (tap-major: PackedBank's
+    `conv_codes`), N*R*S*C/2 bytes; plain books only, C % 32 == 0.  kernel_size, stride, padding, dilation: an int or a pair.
+    alpha_w, alpha_x, I_w, I_x, image_w, bias: as int_linear4.  out: a [B, N, Ho, Wo] tensor of `dtype` in channels-last memory.
+    Returns such a tensor (logical [B, N, Ho, Wo], stored NHWC)."""
+    for t, name in ((codes, "codes"), (xq, "xq"), (alpha_w, "alpha_w"), (image_w, "image_w"), (alpha_x, "alpha_x")):
+        _require_gpu(t, name)
+    dt = _DTYPES.get(dtype)
+    if dt is None or dt == F64:
+        raise AntqError("unsupported dtype %s" % dtype)
+    if xq.dtype != torch.int8 or xq.dim() != 4 or not xq.is_contiguous():
+        raise AntqError("xq must be a contiguous int8 tensor [B, H, W, C]")
+    (R, S), (sh, sw), (ph, pw), (dh, dw) = _pair(kernel_size), _pair(stride), _pair(padding), _pair(dilation)
+    B, H, W, C = xq.shape
+    if codes.dtype != torch.uint8 or codes.numel() * 2 != N * R * S * C:
+        raise AntqError("codes must be uint8 of N*R*S*C/2 bytes")
+    if (alpha_w.dtype != torch.float32 or alpha_w.numel() < (N if per_row else 1) or alpha_x.dtype != torch.float32 or alpha_x.numel() < 1
+            or image_w.dtype != torch.int8):
+        raise AntqError("alpha_w must be float32, one per row (per_row) or one; alpha_x one float32; image_w int8")
+    if bias is not None:
+        _require_gpu(bias, "bias")
+        if bias.dtype != dtype or bias.numel() != N:
+            raise AntqError("bias must hold N elements of `dtype`")
+    for t in (codes, alpha_w, image_w, alpha_x, bias, out):
+        if t is not None and t.device != xq.device:
+            raise AntqError("every tensor of int_conv2d4 must live on one device")
+    # (sizes the library refuses -- an empty output among them -- give an empty `out` here and its code there)
+    Ho = max((H + 2 * ph - dh * (R - 1) - 1) // sh + 1, 0) if sh >= 1 else 0
+    Wo = max((W + 2 * pw - dw * (S - 1) - 1) // sw + 1, 0) if sw >= 1 else 0
+    if out is None:
+        out = torch.empty((B, Ho, Wo, N), dtype=dtype, device=xq.device).permute(0, 3, 1, 2)
+    elif not (out.is_cuda and out.dtype == dtype and tuple(out.shape) == (B, N, Ho, Wo) and out.permute(0, 2, 3, 1).is_contiguous()):
+        raise AntqError("out must be a [B, N, Ho, Wo] tensor of `dtype` in channels-last memory on xq's device")
+    with _on_device(xq.device):
+        rc = lib().antq_conv2d4_i8(codes.data_ptr(), xq.data_ptr(), _ptr(bias), out.data_ptr(), B, H, W, C, N, R, S, sh, sw, ph, pw, dh, dw,
+                                   alpha_w.data_ptr(), 1 if per_row else 0, I_w, image_w.data_ptr(), image_w.numel(), alpha_x.data_ptr(),
+                                   I_x, 0, dt, _stream_int(xq.device))
+    if rc:
+        _check(rc, "antq_conv2d4_i8")
     return out
 
 

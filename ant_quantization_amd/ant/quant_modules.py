@@ -594,6 +594,11 @@ class Conv2dQuantizer(nn.Module):
         if not self.quant_input._steady:
             self.quant_input.prefetch_sign(input)          # (first call: its sign is on its way while the weight calibrates)
         weight = self.quant_weight(self.weight, input)     # re-quantised on every forward, like the reference
+        bank = self.quant_weight._bank
+        if bank is not None and getattr(bank, "integer_conv", False):       # packed.pack_model(integer_conv=True): the raw input
+            out = bank.integer_conv_call(self, input, weight)
+            if out is not None:
+                return out
         input = self.quant_input(input, self.weight)
         return self._conv_forward(input, weight)
 

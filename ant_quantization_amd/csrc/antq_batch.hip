@@ -15,6 +15,7 @@
 #include "antq_k_linear_i8.h"
 #include "antq_k_linear_i8_sk.h"
 #include "antq_k_linear8_i8.h"
+#include "antq_k_conv_i8.h"
 
 #include <atomic>
 #include <type_traits>
@@ -788,6 +789,61 @@ extern "C" int antq_linear4_i8(const uint8_t *codes, const int8_t *xq, const voi
                         return launch_status();
                     }
                 });
+            });
+        });
+    });
+}
+
+// The integer-domain conv2d from 4-bit codes (antq_k_conv_i8.h): an implicit GEMM of M = B Ho Wo rows by K = R S C, the
+// formula, the epilogue and the tile rule antq_linear4_i8's.  Every check comes before anything touches HIP, in the order
+// include/antq.h states; the limits are what the kernel's 32-bit offsets and packed 16-bit row origins need.
+extern "C" int antq_conv2d4_i8(const uint8_t *codes, const int8_t *xq, const void *bias, void *y, size_t B, size_t H, size_t W, size_t C,
+                               size_t N, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                               const float *alpha_w, int per_row, int I_w, const int8_t *image_w, int m, const float *alpha_x, int I_x,
+                               unsigned flags, int dtype, void *stream)
+{
+    if (!codes || !xq || !y || !alpha_w || !image_w || !alpha_x || m < 1) return ANTQ_ERR_ARG;
+    if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_ARG;
+    if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
+    if (B == 0 || N == 0) return ANTQ_OK;
+    constexpr long long D = ANTQ_CONV2D4_I8_MAX_DIM;
+    if ((flags & ANTQ_FLAG_OVP) || !dec4_book_ok(m, 0, false)) return ANTQ_ERR_UNSUPPORTED;
+    if (C == 0 || C % 32 != 0 || H < 1 || W < 1 || R < 1 || S < 1 || stride_h < 1 || stride_w < 1 || dil_h < 1 || dil_w < 1 || pad_h < 0 ||
+        pad_w < 0)
+        return ANTQ_ERR_UNSUPPORTED;
+    if (H > (size_t)D || W > (size_t)D || R > D || S > D || stride_h > D || stride_w > D || dil_h > D || dil_w > D || pad_h > D || pad_w > D)
+        return ANTQ_ERR_UNSUPPORTED;
+    const long long eh = (long long)H + 2 * pad_h - (long long)dil_h * (R - 1) - 1, ew = (long long)W + 2 * pad_w - (long long)dil_w * (S - 1) - 1;
+    if (eh < 0 || ew < 0) return ANTQ_ERR_UNSUPPORTED;                                  // (an empty output)
+    const size_t Ho = (size_t)(eh / stride_h) + 1, Wo = (size_t)(ew / stride_w) + 1;
+    // (H, W, R, S, Ho, Wo < 2^15; B and C are bounded first: no product below leaves 64 bits)
+    if (B > ANTQ_CONV2D4_I8_MAX_M || C > ANTQ_CONV2D4_I8_MAX_XQ_BYTES || N > 0x7fffffffull) return ANTQ_ERR_UNSUPPORTED;
+    const size_t M = B * Ho * Wo, K = (size_t)R * (size_t)S * C;
+    if (M > ANTQ_CONV2D4_I8_MAX_M || B * H * W > ANTQ_CONV2D4_I8_MAX_XQ_BYTES / C) return ANTQ_ERR_UNSUPPORTED;
+    if (I_x < 1 || I_x > 127 || I_w < 1 || I_w > 127) return ANTQ_ERR_UNSUPPORTED;
+    if ((uint64_t)I_x * (uint64_t)I_w * (uint64_t)K >= (1ull << 31)) return ANTQ_ERR_UNSUPPORTED;      // (the sum could leave int32)
+    const uintptr_t esz = dtype == ANTQ_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(xq) % 16 || reinterpret_cast<uintptr_t>(codes) % 16 || reinterpret_cast<uintptr_t>(y) % esz ||
+        reinterpret_cast<uintptr_t>(bias) % esz || reinterpret_cast<uintptr_t>(alpha_w) % 4 || reinterpret_cast<uintptr_t>(alpha_x) % 4)
+        return ANTQ_ERR_ALIGN;
+    const ConvGeom g{(uint32_t)H, (uint32_t)W, (uint32_t)C, (uint32_t)R, (uint32_t)S, (uint32_t)Wo, (uint32_t)(Ho * Wo),
+                     (uint32_t)stride_h, (uint32_t)stride_w, (uint32_t)dil_h, (uint32_t)dil_w, pad_h, pad_w};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int waves, mt;
+    i8_shape(M, N, one_of<2, 4>(g_knob_gemm_tile, 0), waves, mt);
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return with_value<2, 4>(waves, [&](auto wv) {
+            return with_value<4, 2>(mt, [&](auto mm) {
+                constexpr int WAVES = decltype(wv)::value, MT = decltype(mm)::value;
+                if constexpr (WAVES == 4 && MT == 2) return (int)ANTQ_ERR_UNSUPPORTED;      // (no such shape: i8_shape)
+                else {
+                    constexpr size_t BM = (size_t)16 * MT * WAVES;
+                    const dim3 blocks((unsigned)((N + kGemmBN - 1) / kGemmBN), (unsigned)((M + BM - 1) / BM));
+                    launch_k(false, k_conv2d_i8<T, WAVES, MT>, blocks, dim3(64u * WAVES), 0, st, codes, xq, bias, y, (uint32_t)M, (uint32_t)N,
+                             (uint32_t)K, g, alpha_w, per_row ? 1 : 0, I_w, image_w, (uint32_t)m, alpha_x, I_x);
+                    return launch_status();
+                }
             });
         });
     });

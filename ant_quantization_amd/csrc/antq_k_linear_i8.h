@@ -2,7 +2,8 @@
 // the kernel of antq_linear4_i8 (fp32, bf16 and f16 outputs).  xq is the int8 image of the activations (antq_quant_i8), V[n, k] the
 // int8 image of the weight's code; the sum over k is an exact int32 sum on v_mfma_i32_16x16x64_i8, the scales are applied once per
 // output.  This is NOT the image product of the other packed linears: the scale is factored out of the sum (include/antq.h).
-// Part of libantq's batched translation unit (antq_batch.hip includes it); gfx950 only.
+// Part of libantq's batched translation unit (antq_batch.hip includes it); gfx950 only.  Everything below but the source of the
+// A operand lives in i8_tile, which antq_k_conv_i8.h shares: k_linear_i8 is i8_tile with the matrix A side (I8Matrix).
 //
 //   ownership  a workgroup of WAVES = 2 / 4 wavefronts owns one tile of BM = 16 MT WAVES rows of xq by BN = 64 output rows n
 //              (grid: x = tiles of n, y = tiles of m).  Wavefront w owns rows 16 MT w .. + 16 MT - 1 of the tile for all 64 n:
@@ -118,18 +119,32 @@ __device__ __forceinline__ uint16_t i8_pair_entry(uint32_t b, const uint8_t *g, 
     return (uint16_t)(v0 | (v1 << 8));
 }
 
-template <typename T, bool OVP, int WAVES, int MT>
-__global__ void __launch_bounds__(64 * WAVES) ANTQ_I8_KERNEL
-k_linear_i8(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq, const void *__restrict__ bias, void *__restrict__ y,
-            uint32_t M, uint32_t N, uint32_t K, const float *__restrict__ alpha_w, int per_row, int I_w,
-            const int8_t *__restrict__ image_w, uint32_t m, int n_normal, const float *__restrict__ alpha_x, int I_x)
+// The constants of a (WAVES, MT) tile that the kernels and their A sides share
+template <int WAVES, int MT>
+struct I8Tile {
+    static constexpr int WR = 16 * MT;                 // rows of xq per wavefront
+    static constexpr int BM = WR * WAVES, NTH = 64 * WAVES;
+    static constexpr int PIECES = kGemmBK / 16;        // 16-byte pieces of a row of xq per stage
+    static constexpr int XL = BM * PIECES / NTH;       // pieces of xq a thread stages per stage
+    static constexpr int RSTEP = NTH / PIECES;         // rows between a thread's pieces
+};
+
+// The A side of k_linear_i8 itself: xq is a row-major [M, K] matrix, read by i8_tile's own load_x.  Any other A side is a
+// type with load(xq, xn), called once per stage in order, which fills the thread's XL pieces of that stage (antq_k_conv_i8.h).
+struct I8Matrix {};
+
+// One tile of S = A . V^T and its epilogue, as the header states it: everything of k_linear_i8 but where a piece of the A
+// operand comes from: a row-major matrix xq [M, K] (XS = I8Matrix), or whatever xs.load(xq, xn) gathers for the next stage
+// (antq_k_conv_i8.h: im2col).  y is [M, N] row-major.
+template <typename T, bool OVP, int WAVES, int MT, typename XS>
+__device__ __forceinline__ ANTQ_I8_KERNEL void
+i8_tile(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq, const void *__restrict__ bias, void *__restrict__ y,
+        uint32_t M, uint32_t N, uint32_t K, const float *__restrict__ alpha_w, int per_row, int I_w, const int8_t *__restrict__ image_w, uint32_t m, int n_normal,
+        const float *__restrict__ alpha_x, int I_x, XS &xs)
 {
+    using TL = I8Tile<WAVES, MT>;
     constexpr int NT = kGemmBN / 16;                   // a wavefront's tiles of 16 output rows
-    constexpr int WR = 16 * MT;                        // rows of xq per wavefront
-    constexpr int BM = WR * WAVES, NTH = 64 * WAVES;
-    constexpr int PIECES = kGemmBK / 16;               // 16-byte pieces of a row of xq per stage
-    constexpr int XL = BM * PIECES / NTH;              // pieces of xq a thread stages per stage
-    constexpr int RSTEP = NTH / PIECES;                // rows between a thread's pieces
+    constexpr int WR = TL::WR, BM = TL::BM, NTH = TL::NTH, PIECES = TL::PIECES, XL = TL::XL, RSTEP = TL::RSTEP;
     constexpr int CL = 256 / NTH;                      // pieces of codes a thread decodes per stage
     constexpr uint32_t BSLOTS = 2u * NT * 64u;         // 16-byte slots of one B image
     static_assert((WAVES == 2 || WAVES == 4) && (MT == 2 || MT == 4) && PIECES == 8 && XL == 2 * MT && kGemmBK == 64 * 2 && NT == 4,
@@ -153,16 +168,18 @@ k_linear_i8(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq, co
     const uint32_t xp = tid & 7u, xr0 = tid >> 3;
     u32x4_t xn[XL];
     auto load_x = [&](uint32_t c) __attribute__((always_inline)) {
-        const uint32_t k0 = c * (uint32_t)kGemmBK + 16u * xp;
-        const bool kok = k0 < K;
-        const size_t koff = (size_t)min(k0, K - 16u);
+        if constexpr (std::is_same<XS, I8Matrix>::value) {
+            const uint32_t k0 = c * (uint32_t)kGemmBK + 16u * xp;
+            const bool kok = k0 < K;
+            const size_t koff = (size_t)min(k0, K - 16u);
 #pragma unroll
-        for (int i = 0; i < XL; i++) {
-            const uint32_t r = m0 + xr0 + (uint32_t)(RSTEP * i);
-            u32x4_t v = *(const ANTQ_GLOBAL u32x4_t *)(reinterpret_cast<const char *>(xq) + (size_t)min(r, M - 1u) * K + koff);
-            if (!(kok && r < M)) v = u32x4_t{0u, 0u, 0u, 0u};
-            xn[i] = v;
-        }
+            for (int i = 0; i < XL; i++) {
+                const uint32_t r = m0 + xr0 + (uint32_t)(RSTEP * i);
+                u32x4_t v = *(const ANTQ_GLOBAL u32x4_t *)(reinterpret_cast<const char *>(xq) + (size_t)min(r, M - 1u) * K + koff);
+                if (!(kok && r < M)) v = u32x4_t{0u, 0u, 0u, 0u};
+                xn[i] = v;
+            }
+        } else xs.load(xq, xn);
     };
     auto write_x = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -299,6 +316,16 @@ k_linear_i8(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq, co
                 }
             }
     }
+}
+
+template <typename T, bool OVP, int WAVES, int MT>
+__global__ void __launch_bounds__(64 * WAVES) ANTQ_I8_KERNEL
+k_linear_i8(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq, const void *__restrict__ bias, void *__restrict__ y,
+            uint32_t M, uint32_t N, uint32_t K, const float *__restrict__ alpha_w, int per_row, int I_w,
+            const int8_t *__restrict__ image_w, uint32_t m, int n_normal, const float *__restrict__ alpha_x, int I_x)
+{
+    I8Matrix xs;
+    i8_tile<T, OVP, WAVES, MT>(codes, xq, bias, y, M, N, K, alpha_w, per_row, I_w, image_w, m, n_normal, alpha_x, I_x, xs);
 }
 
 }  // namespace antq

@@ -146,6 +146,22 @@ weights in front of the MFMA; other books go through an LDS table -- or, with `i
 `antq_linear8_i8_sk` on the bank's workspace (`.int_linear_byte_calls`, `.int_linear_byte_sk_calls`; both also count in
 `.int_linear_calls` / `.int_linear_sk_calls`).  With the option off every path takes today's launches and gives today's bits.
 Measurements and verdict: profiles/int_linear8.md, DESIGN.md 5s.
+
+`integer_conv=True` (needs fused_linear and integer_linear) carries the integer contract over to convolutions: conv2d as an implicit
+GEMM from the 4-bit codes on the int8 matrix cores (`antq_conv2d4_i8`; include/antq.h has the formula -- int_linear4's with the sum
+over the receptive field; zero padding is exact because the image of 0 is 0).  A 4-bit `Conv2dQuantizer` entry of the ant tree is
+integer-conv-fusable when groups == 1, C = in_channels is a multiple of 32, its padding is a tuple of integers with
+`padding_mode == "zeros"`, and its weight book is plain and has an integer image; every other conv entry is listed in
+`.integer_skipped` with its reason (conv1 with C = 3, for one).  A fusable entry gets `conv_codes`: its codes re-ordered nibble-wise
+from (c, r, s) to (r, s, c) per output channel, built with torch ops at pack time from fresh or loaded codes alike and not written
+to checkpoints -- N K / 2 extra bytes per served layer; the decoded image stays, because every call that is not served needs it.
+`Conv2dQuantizer.forward` hands the RAW input to `bank.integer_conv_call` before `quant_input` runs; the call is served under
+integer_linear_call's conditions on the weight and the input quantiser, for a 4-D input, when `I_x * I_w * C R S < 2^31`
+(`.int_conv_calls`).  The kernel reads NHWC: a channels-last-contiguous input is used as it is, any other is copied once with
+`contiguous(memory_format=torch.channels_last)` (`.int_conv_relayouts`); the output has the logical shape [B, N, Ho, Wo] in
+channels-last memory, so a chain of served layers pays no relayout after the first.  OliVe's wrapper, byte-coded conv layers and
+groups are out of scope.  With the option off every launch and every bit is today's.  Measurements and verdict:
+profiles/int_conv4.md, DESIGN.md 5t.
 """
 from collections import namedtuple
 
@@ -177,6 +193,7 @@ _OPTIONS = (
     _Option("integer_linear", False, ("fused_linear",), None),
     _Option("integer_split_k", False, ("fused_linear", "integer_linear"), None),
     _Option("integer_bytes", False, ("fused_linear", "fused_bytes", "integer_linear"), None),
+    _Option("integer_conv", False, ("fused_linear", "integer_linear"), None),
 )
 _NOTES = {("PackedBank", "keep_images"): " (nothing else computes from the codes)"}
 
@@ -242,7 +259,7 @@ class PackedBank:
     def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True, fused_rows=None,
                  byte_codes=False, fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None,
                  fused_conv1d=False, fused_conv1d_mm=False, fused_conv1d_gemm=False, integer_linear=False,
-                 integer_split_k=False, integer_bytes=False):
+                 integer_split_k=False, integer_bytes=False, integer_conv=False):
         """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict);
         a layer's code width is then the one its stored size says (numel / 2 bytes: 4-bit, numel bytes: byte codes).
         Every other parameter: see the module docstring."""
@@ -261,11 +278,13 @@ class PackedBank:
         self._scratch = {}         # (device, dtype) -> the one decode buffer of the layers without an image
         self.entries = {}          # id(quantiser) -> dict
         self.skipped = []          # (layer name, reason): layers that keep their float weight and per-layer launch
-        self.integer_skipped = []  # (layer name, reason): 4-bit Linear entries integer_linear does not serve (integer_bytes: and byte-coded entries)
+        self.integer_skipped = []  # (layer name, reason): 4-bit Linear entries integer_linear does not serve (integer_bytes: and byte-coded entries; integer_conv: and conv entries)
         self.int_linear_calls = 0  # forwards antq_quant_i8 + antq_linear4_i8 (or _sk) served
         self.int_linear_sk_calls = 0  # ... of them through antq_linear4_i8_sk (integer_split_k)
         self.int_linear_byte_calls = 0  # ... of int_linear_calls, those from byte codes: antq_linear8_i8 (or _sk) (integer_bytes)
         self.int_linear_byte_sk_calls = 0  # ... of them through antq_linear8_i8_sk
+        self.int_conv_calls = 0    # forwards antq_quant_i8 + antq_conv2d4_i8 served (integer_conv)
+        self.int_conv_relayouts = 0  # ... of them whose input was copied to channels-last memory first
         self._sk_workspace = {}    # device -> the one workspace of antq_linear4_i8_sk / antq_linear8_i8_sk, grown on demand
         self.launches = 0          # decode launches so far (one per (device, dtype, pair rule, code width) group and refresh)
         self.dirty = True
@@ -288,6 +307,9 @@ class PackedBank:
                     if codes is not None and name in codes:
                         raise _lib.AntqError("PackedBank: stored codes for layer %s, which cannot be packed (%s)" % (name, reason))
                     self.skipped.append((name, reason))
+                    if self.integer_conv and w.dim() == 4:       # (a conv layer that is not even packed: conv1, C = 3, K = 27)
+                        self.integer_skipped.append((name, "C = %d is not a multiple of 32" % w.shape[1] if w.shape[1] % 32
+                                                     else "not packed: %s" % reason))
                     continue
                 per_row = bool(q.is_perchannel)
                 rows, row_len = (w.shape[0], w.numel() // w.shape[0]) if per_row else (1, w.numel())
@@ -321,7 +343,15 @@ class PackedBank:
                         integer = plan.integer_image8()[0]
                     else:
                         self.integer_skipped.append((name, why))
-                self.entries[id(q)] = dict(name=name, q=q, mod=mod, rows=rows, row_len=row_len, per_row=per_row, codes=c, width=width,
+                conv_codes = None          # (integer_conv) the codes in tap-major order, when the entry is integer-conv-fusable
+                if self.integer_conv and w.dim() == 4 and not (self.integer_bytes and width == 8):      # (those are listed above)
+                    why = ("not a Conv2dQuantizer of the ant tree" if not _is_ant_conv2d(mod)
+                           else self._conv_integer_refusal(mod, tuple(w.shape), plan, ovp, width))
+                    if why is None:
+                        integer, conv_codes = plan.integer_image()[0], _tap_major(c, tuple(w.shape))
+                    else:
+                        self.integer_skipped.append((name, why))
+                self.entries[id(q)] = dict(name=name, q=q, mod=mod, rows=rows, row_len=row_len, per_row=per_row, codes=c, width=width, conv_codes=conv_codes,
                                            fusable=fusable, kind=kind, shape=tuple(w.shape), dtype=w.dtype, device=w.device, integer=integer,
                                            out=torch.empty_like(w, memory_format=torch.contiguous_format) if image else None)
             if not self.entries:
@@ -360,6 +390,26 @@ class PackedBank:
             plan_x, _, _, ovp_x = _codebook(qi)
             if ovp_x or plan_x.integer_image8() is None:
                 return "the input's codebook has no integer image"
+        return None
+
+    @staticmethod
+    def _conv_integer_refusal(mod, shape, plan, ovp, width):
+        """(integer_conv) Why the entry of an ANT Conv2dQuantizer `mod` with weight [N, C, R, S] is not integer-conv-fusable
+        (None: it is)."""
+        if width != 4:
+            return "byte codes"
+        if mod.groups != 1:
+            return "groups = %d" % mod.groups
+        if shape[1] % 32:
+            return "C = %d is not a multiple of 32" % shape[1]
+        pad = mod.padding
+        if (isinstance(pad, str) or getattr(mod, "padding_mode", "zeros") != "zeros"
+                or not all(isinstance(p, int) and p >= 0 for p in (pad if isinstance(pad, (tuple, list)) else (pad,)))):
+            return "padding %r (%s) is not zero padding by integers" % (pad, getattr(mod, "padding_mode", "zeros"))
+        if ovp:
+            return "a pair-rule book does not survive the tap-major order"
+        if plan.integer_image() is None:
+            return "the weight's codebook has no integer image"
         return None
 
     @staticmethod
@@ -426,7 +476,7 @@ class PackedBank:
 
     def nbytes(self):
         """(bytes of codes, bytes of decoded images and of the scratch buffers that stand in for dropped ones)"""
-        return (sum(e["codes"].numel() for e in self.entries.values()),
+        return (sum(e["codes"].numel() + (0 if e.get("conv_codes") is None else e["conv_codes"].numel()) for e in self.entries.values()),
                 sum(t.numel() * t.element_size() for t in [e["out"] for e in self.entries.values() if e["out"] is not None]
                     + list(self._scratch.values())))
 
@@ -450,6 +500,8 @@ class PackedBank:
                 if e["out"] is not None:
                     e["out"] = torch.empty(e["shape"], dtype=w.dtype, device=w.device)
                 e["codes"] = e["codes"].to(w.device)
+                if e.get("conv_codes") is not None:
+                    e["conv_codes"] = e["conv_codes"].to(w.device)
                 e["dtype"], e["device"] = w.dtype, w.device
             plan, gmax, n_normal, ovp = _codebook(q)
             alpha = q.alpha.detach().reshape(-1)
@@ -562,15 +614,7 @@ class PackedBank:
         else:
             served = weight is e["out"]
         N, K = e["shape"]
-        if served and qi._steady and not qi._hm_fresh():
-            # (buffers rebound since -- a deep copy, .to(): what the quantiser's own forward would re-read, _init_quant_para)
-            qi._hm_get('bit')
-            if qi._hm_get('has_inited_quant_para') == 0:
-                return None
-        if not (served and qi._steady and qi._hm_fresh() and getattr(qi, "_pending", None) is None and qi.is_enable
-                and qi.is_enable_activation and not qi.is_perchannel and qi.mode not in ("base", "outlier") and qi.alpha.numel() == 1
-                and not (torch.is_grad_enabled() and qi.alpha.requires_grad) and self._fits(e, input, mod.bias, K)
-                and input.numel() // K <= _lib.LINEAR4_I8_MAX_M):
+        if not (served and self._input_serves(qi) and self._fits(e, input, mod.bias, K) and input.numel() // K <= _lib.LINEAR4_I8_MAX_M):
             return None
         plan_x, gmax_x, nn_x, ovp_x = _codebook(qi)
         wide = e["width"] == 8             # (integer_bytes) byte codes: images with I up to 128, plain books on both sides
@@ -580,13 +624,7 @@ class PackedBank:
         e.pop("served", None)
         plan_w, gmax_w, nn_w, ovp_w = _codebook(q)
         dev = e["device"]
-        stamp = (qi.alpha.data_ptr(), qi.alpha._version, qi.alpha.dtype, id(plan_x), gmax_x, e["alpha"].data_ptr(), e["alpha"]._version)
-        if e["unit_stamp"] != stamp:
-            with torch.no_grad():
-                e["unit_w"] = _unit_alpha(e["alpha"], plan_w, gmax_w)
-                e["unit_x"] = _unit_alpha(qi.alpha.to(dev), plan_x, gmax_x)
-                e["alpha_x"] = qi.alpha.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
-            e["unit_stamp"] = stamp
+        self._integer_units(e, qi, plan_w, gmax_w, plan_x, gmax_x)
         xq = _lib.quant_i8(input, e["alpha_x"], plan_x, gmax_x, 1, input.numel(), False, plan_x.image_dev(dev, 128 if wide else 127),
                            n_normal=nn_x, ovp=ovp_x)
         self.int_linear_calls += 1
@@ -605,6 +643,74 @@ class PackedBank:
             self.int_linear_sk_calls += 1
             return _lib.int_linear4_sk(*args, workspace=ws, **kw)
         return _lib.int_linear4(*args, **kw)
+
+    @staticmethod
+    def _input_serves(qi):
+        """Whether an input quantiser is one the integer calls take: steady, enabled, per tensor with one alpha, in neither
+        `base` nor `outlier` mode, nothing pending, no gradient wanted through its alpha."""
+        if qi._steady and not qi._hm_fresh():
+            # (buffers rebound since -- a deep copy, .to(): what the quantiser's own forward would re-read, _init_quant_para)
+            qi._hm_get('bit')
+            if qi._hm_get('has_inited_quant_para') == 0:
+                return False
+        return (qi._steady and qi._hm_fresh() and getattr(qi, "_pending", None) is None and qi.is_enable
+                and qi.is_enable_activation and not qi.is_perchannel and qi.mode not in ("base", "outlier") and qi.alpha.numel() == 1
+                and not (torch.is_grad_enabled() and qi.alpha.requires_grad))
+
+    @staticmethod
+    def _integer_units(e, qi, plan_w, gmax_w, plan_x, gmax_x):
+        """The scales as the integer entries take them (e["unit_w"], e["unit_x"], e["alpha_x"]), formed again only when an alpha
+        or the input's book changed."""
+        dev = e["device"]
+        stamp = (qi.alpha.data_ptr(), qi.alpha._version, qi.alpha.dtype, id(plan_x), gmax_x, e["alpha"].data_ptr(), e["alpha"]._version)
+        if e["unit_stamp"] != stamp:
+            with torch.no_grad():
+                e["unit_w"] = _unit_alpha(e["alpha"], plan_w, gmax_w)
+                e["unit_x"] = _unit_alpha(qi.alpha.to(dev), plan_x, gmax_x)
+                e["alpha_x"] = qi.alpha.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+            e["unit_stamp"] = stamp
+
+    def integer_conv_call(self, mod, input, weight):
+        """(integer_conv) The output of a Conv2dQuantizer from its RAW input and what quant_weight returned, in the integer
+        domain: antq_quant_i8 of the input in channels-last memory, then antq_conv2d4_i8 from the tap-major codes.  None -- and
+        nothing touched -- unless lookup() served the weight, the entry is integer-conv-fusable, the input quantiser is one
+        integer_linear_call takes and its book is plain with an integer image, I_x I_w C R S < 2^31, and the input is a 4-D
+        no-grad GPU tensor [B, C, H, W] of the layer's dtype on its device whose sizes the library takes.  An input that is not
+        channels-last contiguous is copied once (`.int_conv_relayouts`).  Returns [B, N, Ho, Wo] in channels-last memory."""
+        q, qi = mod.quant_weight, mod.quant_input
+        e = self.entries.get(id(q))
+        if e is None or e.get("conv_codes") is None or weight is not e["out"]:
+            return None
+        N, C, R, S = e["shape"]
+        bias = mod.bias
+        if not (self._input_serves(qi) and input.dim() == 4 and input.is_cuda and input.dtype == e["dtype"] and input.device == e["device"]
+                and input.shape[1] == C and input.numel() > 0
+                and not (torch.is_grad_enabled() and (input.requires_grad or (bias is not None and bias.requires_grad)))
+                and (bias is None or (bias.dtype == input.dtype and bias.is_contiguous() and bias.device == input.device))):
+            return None
+        plan_x, gmax_x, nn_x, ovp_x = _codebook(qi)
+        image_x = plan_x.integer_image()
+        if image_x is None or ovp_x or image_x[0] * e["integer"] * C * R * S >= 2 ** 31:
+            return None
+        B, _, H, W = input.shape
+        (sh, sw), (ph, pw), (dh, dw) = _lib._pair(mod.stride), _lib._pair(mod.padding), _lib._pair(mod.dilation)
+        Ho, Wo = (H + 2 * ph - dh * (R - 1) - 1) // sh + 1, (W + 2 * pw - dw * (S - 1) - 1) // sw + 1
+        if (Ho < 1 or Wo < 1 or max(H, W, R, S, sh, sw, ph, pw, dh, dw) > _lib.CONV2D4_I8_MAX_DIM or B * Ho * Wo > _lib.CONV2D4_I8_MAX_M
+                or input.numel() > _lib.CONV2D4_I8_MAX_XQ_BYTES):
+            return None
+        last = input.is_contiguous(memory_format=torch.channels_last)
+        if last and input.data_ptr() % 16:
+            return None
+        if not last:
+            input = input.contiguous(memory_format=torch.channels_last)
+            self.int_conv_relayouts += 1
+        plan_w, gmax_w, _, _ = _codebook(q)
+        dev = e["device"]
+        self._integer_units(e, qi, plan_w, gmax_w, plan_x, gmax_x)
+        xq = _lib.quant_i8(input.permute(0, 2, 3, 1), e["alpha_x"], plan_x, gmax_x, 1, input.numel(), False, plan_x.image_dev(dev))
+        self.int_conv_calls += 1
+        return _lib.int_conv2d4(e["conv_codes"], xq, e["unit_w"], plan_w.image_dev(dev), e["integer"], e["unit_x"], image_x[0], N, (R, S),
+                                (sh, sw), (ph, pw), (dh, dw), e["per_row"], e["dtype"], bias=None if bias is None else bias.detach())
 
     def _integer_byte_call(self, e, mod, xq, plan_w, I_x, M):
         """(integer_bytes) integer_linear_call's product for a byte-coded entry: antq_linear8_i8, or its split-K form."""
@@ -664,6 +770,21 @@ def _unit_alpha(alpha, plan, gmax):
     return a.to(torch.float32).contiguous() if r == 1.0 else (a.to(torch.float64) * r).to(torch.float32).contiguous()
 
 
+def _tap_major(codes, shape):
+    """The 4-bit codes of a conv weight [N, C, R, S] (encode4's layout: element 2 i in the low nibble of byte i) re-ordered
+    nibble-wise to [N, R, S, C], as antq_conv2d4_i8 reads them."""
+    N, C, R, S = shape
+    c = codes.reshape(-1)
+    nib = torch.stack((c & 15, c >> 4), dim=1).reshape(N, C, R, S).permute(0, 2, 3, 1).reshape(-1, 2)
+    return (nib[:, 0] | (nib[:, 1] << 4)).contiguous()
+
+
+def _is_ant_conv2d(mod):
+    """Whether `mod` is the ant tree's Conv2dQuantizer (OliVe's wrapper is out of integer_conv's scope)."""
+    from .ant.quant_modules import Conv2dQuantizer
+    return isinstance(mod, Conv2dQuantizer)
+
+
 def _is_conv1d(mod):
     """Whether `mod` is OliVe's Conv1dQuantizer (GPT-2's Conv1D: weight [in, out], y = x @ W + b)."""
     from .olive.quant_modules import Conv1dQuantizer       # (here: that module is loaded by whoever built such a layer)
@@ -690,7 +811,7 @@ def pack_model(model, release_weights=False, **options):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
     (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
     options: fused_linear, keep_images, fused_rows, byte_codes, fused_bytes, fused_byte_rows, fused_gemm_rows,
-    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes -- PackedBank's keywords with its defaults; see the module docstring."""
+    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes, integer_conv -- PackedBank's keywords with its defaults; see the module docstring."""
     return PackedBank(model, release_weights, None, **options)     # (codes: not an option here -- given, it is a TypeError)
 
 
@@ -719,7 +840,7 @@ def load_packed_state_dict(model, sd, release_weights=True, **options):
     any other size raises AntqError naming the layer), and the weights are materialised by the batched decode
     (release_weights=False: copied into the layers' own float weights instead of replacing them).
     options: fused_linear, keep_images, fused_rows, fused_bytes, fused_byte_rows, fused_gemm_rows, fused_byte_gemm_rows,
-    fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
+    fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes, integer_conv, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
     _check_options("load_packed_state_dict", **options)        # (before the model is touched)
     suffix = "." + CODES_KEY
     codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}

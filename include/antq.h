@@ -1001,6 +1001,45 @@ int antq_linear8_i8_sk(const uint8_t *codes_dev, const int8_t *xq_dev, const voi
                        unsigned flags /* 0 */, int dtype /* F32 | BF16 | F16: y and bias */, void *stream);
 
 /* -------------------------------------------------------------------------
+ * antq_conv2d4_i8: the integer-domain conv2d (groups = 1) as an implicit GEMM from 4-bit codes -- antq_linear4_i8's contract
+ * carried over to convolutions.  xq_dev: int8 [B, H, W, C] (NHWC), what antq_quant_i8 writes for a channels-last-contiguous
+ * input with one scale per tensor (the element encoder does not look at the layout of a plain book).  codes_dev: 4-bit codes
+ * in antq_encode4's layout of the weight viewed as [N = Cout][R][S][C] (tap-major), K = R S C.  y_dev: [B, Ho, Wo, N] (NHWC)
+ * with Ho = (H + 2 pad_h - dil_h (R - 1) - 1) / stride_h + 1 and Wo alike.  With v = image_w[code] (a code past the m bytes
+ * reads 0)
+ *     S[(b, ho, wo), n] = sum over r, s, c of xq[b, ho stride_h - pad_h + r dil_h, wo stride_w - pad_w + s dil_w, c] * v[n, r, s, c]
+ * where a tap outside the image contributes 0 (the image of 0 is 0: zero padding is exact); S is an exact int32 sum and has
+ * no order.  u_x, u_w[n] and the epilogue are antq_linear4_i8's, word for word:
+ *     y[b, ho, wo, n] = round_dtype( fl32( fl32( fl32( fl32(S) * u_x ) * u_w[n] ) + fl32(bias[n]) ) )
+ * The bits of an output depend on its receptive field, row n of the codes, the scales and the bias, and on nothing else --
+ * not on the tile shape, B, N or the run; a 1 x 1 / stride 1 / pad 0 call gives antq_linear4_i8's bits for the same operands.
+ * Plain books only (m <= 16): the pair rule ties flat neighbours and does not survive the tap-major order of the weight or
+ * the NHWC order of the activation.  Groups other than 1 cannot be expressed.
+ *   ANTQ_ERR_ARG          a null pointer other than bias_dev; m < 1; a dtype other than F32 / BF16 / F16; a flag other than
+ *                         ANTQ_FLAG_OVP
+ *   ANTQ_OK, no launch    B == 0 or N == 0
+ *   ANTQ_ERR_UNSUPPORTED  ANTQ_FLAG_OVP; m > 16; C == 0 or C % 32 != 0; H, W, R or S below 1; a stride or dilation below 1; a
+ *                         negative padding; any of H, W, R, S, the strides, dilations and paddings above
+ *                         ANTQ_CONV2D4_I8_MAX_DIM; an empty output (Ho or Wo below 1); B Ho Wo > ANTQ_CONV2D4_I8_MAX_M;
+ *                         B H W C > ANTQ_CONV2D4_I8_MAX_XQ_BYTES (the kernel's 32-bit offsets); N >= 2^31; I_x or I_w
+ *                         outside 1 .. 127; I_x * I_w * K >= 2^31 (the sum could leave int32)
+ *   ANTQ_ERR_ALIGN        xq_dev or codes_dev not 16-byte aligned; y_dev / bias_dev not aligned to their element; a scale
+ *                         pointer not 4-byte aligned
+ * Every check comes before anything touches HIP; a refused call launches and writes nothing.  antq_debug_set key 23 forces
+ * the tile as for antq_linear4_i8 (no result changes).  No atomics, no workspace, no allocation; one launch, stream-ordered,
+ * capturable.  Kernel: csrc/antq_k_conv_i8.h.  Measurements: profiles/int_conv4.md.
+ * ------------------------------------------------------------------------- */
+#define ANTQ_CONV2D4_I8_MAX_DIM 8191
+#define ANTQ_CONV2D4_I8_MAX_M (1 << 22)
+#define ANTQ_CONV2D4_I8_MAX_XQ_BYTES 0x7fffffff
+int antq_conv2d4_i8(const uint8_t *codes_dev /* N*R*S*C/2 bytes */, const int8_t *xq_dev /* [B, H, W, C] */,
+                    const void *bias_dev /* N or NULL */, void *y_dev /* [B, Ho, Wo, N] */, size_t B, size_t H, size_t W, size_t C,
+                    size_t N, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                    const float *alpha_w_dev, int alpha_per_row, int I_w, const int8_t *image_w_dev, int m,
+                    const float *alpha_x_dev /* one float */, int I_x, unsigned flags /* 0 */,
+                    int dtype /* F32 | BF16 | F16: y and bias */, void *stream);
+
+/* -------------------------------------------------------------------------
  * OliVe's clip statistic on ONE read (replaces t.mean() + t.std() of olive_quantization/antquant/quant_modules.py:193-197
  * and :213-218, which read the tensor at least three times before the clip search reads it again).
  * antq_moments: sums_dev[2 r] = sum of x, sums_dev[2 r + 1] = sum of x^2 over row r (alpha_per_row) or over the whole

@@ -1,0 +1,162 @@
+#!/usr/bin/env python3
+"""A/B of a packed 4-bit Conv2d layer's whole forward from a RAW input -- activation quantiser and convolution -- on ResNet-50's
+distinct conv shapes with C % 32 == 0 (224 x 224 images), at batch 1, 8 and 64, float32 and bfloat16; the protocol of
+profiles/int_linear4.md: same process, each arm rotating over distinct weight buffers, per point `--reps` measurements of one
+captured graph of calls per arm, the arms ALTERNATED inside every repetition; the median and the spread (max - min) / median.
+
+    I   antq_quant_i8 + antq_conv2d4_i8 on the tap-major codes, the input channels-last   (pack_model(integer_conv=True))
+    IN  the same from an NCHW-contiguous input: the copy to channels-last memory is paid
+    A   antq_fakequant + F.conv2d on the kept image; measured with the NCHW-contiguous and with the channels-last input, the
+        faster of the two per point is A (`a_layout` says which)
+
+Signed flint-4 weights with one scale per output channel, unsigned int-4 activations (post-ReLU) with one scale, bias.
+
+    python tools/probe_int_conv4.py [--quick] [--out profiles/int_conv4]      (writes .json and .md)
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from ant_quantization_amd import _lib, grids, packed  # noqa: E402
+from probe_linear4_t import ROTATE_BYTES, capture, alternate  # noqa: E402
+
+# (C, N, kernel, stride, padding, H = W of the input): torchvision's ResNet-50 (stride on the 3 x 3), conv1 (C = 3) left out
+SHAPES = ((64, 64, 1, 1, 0, 56), (64, 64, 3, 1, 1, 56), (64, 256, 1, 1, 0, 56), (256, 64, 1, 1, 0, 56), (256, 128, 1, 1, 0, 56),
+          (128, 128, 3, 2, 1, 56), (128, 512, 1, 1, 0, 28), (256, 512, 1, 2, 0, 56), (512, 128, 1, 1, 0, 28), (128, 128, 3, 1, 1, 28),
+          (512, 256, 1, 1, 0, 28), (256, 256, 3, 2, 1, 28), (256, 1024, 1, 1, 0, 14), (512, 1024, 1, 2, 0, 28), (1024, 256, 1, 1, 0, 14),
+          (256, 256, 3, 1, 1, 14), (1024, 512, 1, 1, 0, 14), (512, 512, 3, 2, 1, 14), (512, 2048, 1, 1, 0, 7), (1024, 2048, 1, 2, 0, 14),
+          (2048, 512, 1, 1, 0, 7), (512, 512, 3, 1, 1, 7))
+BATCHES = (1, 8, 64)
+
+
+def _range(v):
+    return "%.2f ... %.2f" % (min(v), max(v))
+
+
+def write_md(rows, path, args):
+    out = ["# antq_quant_i8 + antq_conv2d4_i8 against today's forward of a packed 4-bit Conv2d layer", "",
+           "Written by `tools/probe_int_conv4.py%s`: one MI355X, one process, one run; every arm starts from the RAW input and rotates "
+           "over distinct weight buffers; per point %d repetitions of one graph-replayed batch of calls per arm, the arms alternated "
+           "inside a repetition; medians in us per call, `spread` = the largest (max - min) / median of the point's arms." % (
+               " --quick" if args.quick else "", args.reps), "",
+           "I = antq_quant_i8 + antq_conv2d4_i8 from a channels-last input, IN = the same from an NCHW input (relayout paid), A = "
+           "antq_fakequant + F.conv2d on the kept image with the faster of the two input layouts (`A in`).  I / A and IN / A are TIMES: "
+           "below 1, the integer path is faster.  `won` / `lost`: faster / slower than A by more than the point's spread.  TOP/s = "
+           "2 M N K over I's time (quantiser included).", ""]
+    for dt in sorted({r["dtype"] for r in rows}):
+        rs = [r for r in rows if r["dtype"] == dt]
+        out += ["## Verdict in counts, %s" % dt, "", "| arm | points | won | lost | arm / A |", "|---|---|---|---|---|"]
+        for arm in ("i", "in"):
+            k = arm + "_over_a"
+            out.append("| %s | %d | %d | %d | %s |" % (arm.upper(), len(rs), sum(r[k] < 1 - r["spread"] for r in rs),
+                                                     sum(r[k] > 1 + r["spread"] for r in rs), _range([r[k] for r in rs])))
+        out += ["", "Per batch, I / A: " + "; ".join("B = %d: %s" % (B, _range([r["i_over_a"] for r in rs if r["B"] == B]))
+                                                     for B in BATCHES if any(r["B"] == B for r in rs)) + ".",
+                "I reaches %s TOP/s.  The largest spread of a point is %.1f %%." % (_range([r["tops"] for r in rs]), 100 * max(r["spread"] for r in rs)), "",
+                "| C -> N, k / stride, input | B | M | K | calls | I | IN | A | A in | I / A | IN / A | TOP/s | spread |",
+                "|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+        for r in rs:
+            out.append("| %d -> %d, %d / %d, %d x %d | %d | %d | %d | %d | %.1f | %.1f | %.1f | %s | %.2f | %.2f | %.0f | %.1f %% |" % (
+                r["C"], r["N"], r["k"], r["stride"], r["H"], r["H"], r["B"], r["M"], r["K"], r["calls"], r["us_i"], r["us_in"], r["us_a"],
+                r["a_layout"], r["i_over_a"], r["in_over_a"], r["tops"], 100 * r["spread"]))
+        out.append("")
+    if args.notes and os.path.exists(args.notes):
+        out += [open(args.notes).read()]
+    with open(path, "w") as f:
+        f.write("\n".join(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--quick", action="store_true", help="bfloat16, batch 8, every fourth shape")
+    ap.add_argument("--dtype", default=None, help="float32 or bfloat16 alone (a run split in two; merge with --rewrite)")
+    ap.add_argument("--flop", type=float, default=1e11, help="operations per graph, about")
+    ap.add_argument("--min-iters", type=int, default=4)
+    ap.add_argument("--max-iters", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--notes", default=None, help="a markdown file appended to the .md: what the run does not say")
+    ap.add_argument("--rewrite", default=None, help="the .json of an earlier run, or several with commas: write the .md (and the merged .json) again (no GPU needed) and stop")
+    ap.add_argument("--out", default=None, help="path without extension: .json and .md are written (and rewritten after every shape)")
+    a = ap.parse_args()
+    if a.rewrite:
+        rows = [r for f in a.rewrite.split(",") for r in json.load(open(f))]          # (several files: the parts of a split run)
+        if a.out:
+            with open(a.out + ".json", "w") as f:
+                json.dump(rows, f, indent=1)
+        write_md(rows, (a.out or os.path.splitext(a.rewrite)[0]) + ".md", a)
+        return
+    if not torch.cuda.is_available():
+        raise SystemExit("probe_int_conv4: no GPU -- nothing is measured without one")
+    dev = torch.device("cuda:0")
+    gw, gx = grids.ant_flint(4, True), grids.ant_grid("int", 4, False)
+    plan_w, plan_x = _lib.plan_for(gw), _lib.plan_for(gx)
+    gmax_w, gmax_x = float(gw.max()), float(gx.max())
+    (I_w, _), (I_x, _) = plan_w.integer_image(), plan_x.integer_image()
+    img_w, img_x = plan_w.image_dev(dev), plan_x.image_dev(dev)
+    rows = []
+    for dt in ((getattr(torch, a.dtype),) if a.dtype else (torch.bfloat16,) if a.quick else (torch.float32, torch.bfloat16)):
+        esz = torch.empty(0, dtype=dt).element_size()
+        for C, N, k, stride, pad, H in (SHAPES[::4] if a.quick else SHAPES):
+            K = C * k * k
+            w = (torch.randn(N, C, k, k, device=dev) * 0.05).to(dt)
+            alpha = (w.float().abs().amax((1, 2, 3)) * 0.9).contiguous()
+            codes0 = _lib.encode4(w, alpha, plan_w, gmax_w, N, K, True)
+            image0 = _lib.decode4(codes0, alpha, plan_w, gmax_w, N, K, True, dt).view(N, C, k, k)
+            taps0 = packed._tap_major(codes0, (N, C, k, k))
+            unit_w = packed._unit_alpha(alpha, plan_w, gmax_w)
+            bias = torch.randn(N, device=dev).to(dt)
+            del w
+            for B in ((8,) if a.quick else BATCHES):
+                Ho = (H + 2 * pad - k) // stride + 1
+                M = B * Ho * Ho
+                iters = int(min(a.max_iters, max(a.min_iters, a.flop / (2.0 * M * N * K))))
+                n_buf = int(min(iters, max(2, -(-ROTATE_BYTES // (K * N * esz)))))
+                images, taps = [image0.clone() for _ in range(n_buf)], [taps0.clone() for _ in range(n_buf)]
+                x = torch.rand(B, C, H, H, device=dev).to(dt)                      # post-ReLU: no negative value
+                x_cl = x.contiguous(memory_format=torch.channels_last)
+                ax = (x.float().max() * 0.9).reshape(1).contiguous()
+                unit_x = packed._unit_alpha(ax, plan_x, gmax_x)
+                xq = torch.empty(B, H, H, C, dtype=torch.int8, device=dev)
+                xf, xf_cl = torch.empty_like(x), torch.empty_like(x_cl)
+                y = torch.empty(B, Ho, Ho, N, dtype=dt, device=dev).permute(0, 3, 1, 2)
+
+                def integer(src, i):
+                    _lib.quant_i8(src.permute(0, 2, 3, 1), ax, plan_x, gmax_x, 1, src.numel(), False, img_x, out=xq)
+                    return _lib.int_conv2d4(taps[i], xq, unit_w, img_w, I_w, unit_x, I_x, N, k, stride, pad, 1, True, dt, bias=bias, out=y)
+
+                def image(src, dst, i):
+                    last = not src.is_contiguous()            # (the quantiser takes the memory as it lies: NHWC views of both)
+                    _lib.fakequant(src.permute(0, 2, 3, 1) if last else src, ax, plan_x, gmax_x, 1, src.numel(), False,
+                                   out=dst.permute(0, 2, 3, 1) if last else dst)
+                    return F.conv2d(dst, images[i], bias, stride, pad)
+
+                graphs = {"I": capture(lambda i: integer(x_cl, i), n_buf, iters, 3),
+                          "IN": capture(lambda i: integer(x.contiguous(memory_format=torch.channels_last), i), n_buf, iters, 3),
+                          "A": capture(lambda i: image(x, xf, i), n_buf, iters, 3),
+                          "ACL": capture(lambda i: image(x_cl, xf_cl, i), n_buf, iters, 3)}
+                t = alternate(graphs, iters, a.reps)
+                us = {key: v[0] for key, v in t.items()}
+                best = "ACL" if us["ACL"] < us["A"] else "A"
+                r = dict(dtype=str(dt).split(".")[1], C=C, N=N, k=k, stride=stride, H=H, B=B, M=M, K=K, calls=iters, buffers=n_buf,
+                         us_i=round(us["I"], 2), us_in=round(us["IN"], 2), us_a_nchw=round(us["A"], 2), us_a_cl=round(us["ACL"], 2),
+                         us_a=round(us[best], 2), a_layout="NCHW" if best == "A" else "channels-last",
+                         i_over_a=round(us["I"] / us[best], 3), in_over_a=round(us["IN"] / us[best], 3),
+                         tops=round(2.0 * M * N * K / (us["I"] * 1e-6) / 1e12, 1), spread=round(max(v[1] for v in t.values()), 4))
+                rows.append(r)
+                print(json.dumps(r), flush=True)
+                del graphs, images, taps
+            torch.cuda.empty_cache()
+            if a.out:
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                with open(a.out + ".json", "w") as f:
+                    json.dump(rows, f, indent=1)
+                write_md(rows, a.out + ".md", a)
+
+
+if __name__ == "__main__":
+    main()
