@@ -39,6 +39,7 @@ LINEAR8_I8_MAX_M = 1 << 20  # include/antq.h ANTQ_LINEAR8_I8_MAX_M: rows of xq a
 CONV2D4_I8_MAX_DIM = 8191   # include/antq.h ANTQ_CONV2D4_I8_MAX_DIM: H, W, R, S, strides, paddings, dilations of antq_conv2d4_i8
 CONV2D4_I8_MAX_M = 1 << 22  # include/antq.h ANTQ_CONV2D4_I8_MAX_M: output positions B * Ho * Wo
 CONV2D4_I8_MAX_XQ_BYTES = 0x7fffffff  # include/antq.h ANTQ_CONV2D4_I8_MAX_XQ_BYTES: bytes of xq
+CONV2D4_I8_SK_MAX_M = 1024  # include/antq.h ANTQ_CONV2D4_I8_SK_MAX_M: output positions B * Ho * Wo antq_conv2d4_i8_sk takes
 LINEAR8_I8_SK_MAX_M = 64  # include/antq.h ANTQ_LINEAR8_I8_SK_MAX_M: rows of xq antq_linear8_i8_sk takes
 PLAN_MAX_BYTES = 128 + 4 * MAX_GRID + 16 * 3072 + 20 * 1024 + 16 * 64
 
@@ -81,7 +82,7 @@ def lib():
                              "antq_linear8_gemm", "antq_linear4_t", "antq_linear4_t_mm", "antq_linear4_t_gemm", "antq_fakequant_outlier",
                              "antq_abs_order_stats", "antq_quant_i8", "antq_linear4_i8", "antq_linear4_i8_sk",
                              "antq_linear4_i8_sk_slices", "antq_linear8_i8", "antq_linear8_i8_sk", "antq_linear8_i8_sk_slices",
-                             "antq_conv2d4_i8"):
+                             "antq_conv2d4_i8", "antq_conv2d4_i8_sk", "antq_conv2d4_i8_sk_slices"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
                 L.antq_decode4_batch_capacity.restype = ctypes.c_size_t
@@ -92,6 +93,7 @@ def lib():
                 L.antq_abs_order_stats_workspace_bytes.restype = ctypes.c_size_t
                 L.antq_linear4_i8_sk_workspace_bytes.restype = ctypes.c_size_t
                 L.antq_linear8_i8_sk_workspace_bytes.restype = ctypes.c_size_t
+                L.antq_conv2d4_i8_sk_workspace_bytes.restype = ctypes.c_size_t
                 # declared signatures: plain python ints go straight through (no per-call wrapper objects)
                 vp, sz, ci, cf, cu = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_float, ctypes.c_uint
                 L.antq_fakequant.argtypes = [vp, vp, vp, sz, sz, vp, ci, cf, vp, vp, cu, ci, vp]
@@ -125,6 +127,9 @@ def lib():
                 L.antq_linear8_i8_sk_workspace_bytes.argtypes = [sz, sz, sz]
                 L.antq_linear8_i8_sk_slices.argtypes = [sz, sz, sz, ci]
                 L.antq_conv2d4_i8.argtypes = [vp, vp, vp, vp, sz, sz, sz, sz, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, ci, ci, vp, ci, vp, ci, cu, ci, vp]
+                L.antq_conv2d4_i8_sk.argtypes = L.antq_conv2d4_i8.argtypes[:24] + [vp, sz] + L.antq_conv2d4_i8.argtypes[24:]
+                L.antq_conv2d4_i8_sk_workspace_bytes.argtypes = [sz, sz, sz]
+                L.antq_conv2d4_i8_sk_slices.argtypes = [sz, sz, sz, ci]
                 # development: ANTQ_DEBUG_KNOBS="14=2,0=8" applies antq_debug_set(key, value) pairs to the loading thread
                 # (the knobs are thread-local; tools/fuzz_campaign.sh forces code paths with it)
                 for kv in [k for k in os.environ.get("ANTQ_DEBUG_KNOBS", "").split(",") if "=" in k]:
@@ -1306,14 +1311,9 @@ def _pair(v):
     return int(a), int(b)
 
 
-def int_conv2d4(codes, xq, alpha_w, image_w, I_w, alpha_x, I_x, N, kernel_size, stride, padding, dilation, per_row, dtype, bias=None,
-                out=None):
-    """conv2d (groups = 1) in the integer domain as an implicit GEMM from 4-bit codes (antq_conv2d4_i8): int_linear4's formula
-    with S summed over the receptive field, taps outside the image contributing 0.  xq: contiguous int8 [B, H, W, C] -- quant_i8
-    of a channels-last input seen as NHWC; codes: the weight's codes viewed as [N][R][S][C] (tap-major: PackedBank's
-    `conv_codes`), N*R*S*C/2 bytes; plain books only, C % 32 == 0.  kernel_size, stride, padding, dilation: an int or a pair.
-    alpha_w, alpha_x, I_w, I_x, image_w, bias: as int_linear4.  out: a [B, N, Ho, Wo] tensor of `dtype` in channels-last memory.
-    Returns such a tensor (logical [B, N, Ho, Wo], stored NHWC)."""
+def _int_conv_args(codes, xq, alpha_w, image_w, alpha_x, N, kernel_size, stride, padding, dilation, per_row, dtype, bias, out):
+    """What int_conv2d4 and int_conv2d4_sk check alike.  Returns (dtype code, the geometry as antq_conv2d4_i8 takes it -- B, H,
+    W, C, N, R, S, sh, sw, ph, pw, dh, dw --, M = B Ho Wo, out)."""
     for t, name in ((codes, "codes"), (xq, "xq"), (alpha_w, "alpha_w"), (image_w, "image_w"), (alpha_x, "alpha_x")):
         _require_gpu(t, name)
     dt = _DTYPES.get(dtype)
@@ -1342,12 +1342,57 @@ def int_conv2d4(codes, xq, alpha_w, image_w, I_w, alpha_x, I_x, N, kernel_size, 
         out = torch.empty((B, Ho, Wo, N), dtype=dtype, device=xq.device).permute(0, 3, 1, 2)
     elif not (out.is_cuda and out.dtype == dtype and tuple(out.shape) == (B, N, Ho, Wo) and out.permute(0, 2, 3, 1).is_contiguous()):
         raise AntqError("out must be a [B, N, Ho, Wo] tensor of `dtype` in channels-last memory on xq's device")
+    return dt, (B, H, W, C, N, R, S, sh, sw, ph, pw, dh, dw), B * Ho * Wo, out
+
+
+def int_conv2d4(codes, xq, alpha_w, image_w, I_w, alpha_x, I_x, N, kernel_size, stride, padding, dilation, per_row, dtype, bias=None,
+                out=None):
+    """conv2d (groups = 1) in the integer domain as an implicit GEMM from 4-bit codes (antq_conv2d4_i8): int_linear4's formula
+    with S summed over the receptive field, taps outside the image contributing 0.  xq: contiguous int8 [B, H, W, C] -- quant_i8
+    of a channels-last input seen as NHWC; codes: the weight's codes viewed as [N][R][S][C] (tap-major: PackedBank's
+    `conv_codes`), N*R*S*C/2 bytes; plain books only, C % 32 == 0.  kernel_size, stride, padding, dilation: an int or a pair.
+    alpha_w, alpha_x, I_w, I_x, image_w, bias: as int_linear4.  out: a [B, N, Ho, Wo] tensor of `dtype` in channels-last memory.
+    Returns such a tensor (logical [B, N, Ho, Wo], stored NHWC)."""
+    dt, geom, _, out = _int_conv_args(codes, xq, alpha_w, image_w, alpha_x, N, kernel_size, stride, padding, dilation, per_row, dtype, bias,
+                                      out)
     with _on_device(xq.device):
-        rc = lib().antq_conv2d4_i8(codes.data_ptr(), xq.data_ptr(), _ptr(bias), out.data_ptr(), B, H, W, C, N, R, S, sh, sw, ph, pw, dh, dw,
-                                   alpha_w.data_ptr(), 1 if per_row else 0, I_w, image_w.data_ptr(), image_w.numel(), alpha_x.data_ptr(),
-                                   I_x, 0, dt, _stream_int(xq.device))
+        rc = lib().antq_conv2d4_i8(codes.data_ptr(), xq.data_ptr(), _ptr(bias), out.data_ptr(), *geom, alpha_w.data_ptr(),
+                                   1 if per_row else 0, I_w, image_w.data_ptr(), image_w.numel(), alpha_x.data_ptr(), I_x, 0, dt,
+                                   _stream_int(xq.device))
     if rc:
         _check(rc, "antq_conv2d4_i8")
+    return out
+
+
+def int_conv2d4_sk_workspace_bytes(M, N, K, device=None):
+    """The bytes of workspace int_conv2d4_sk needs now for an output of M = B Ho Wo rows by N channels with K = R S C, on
+    `device` (default: the current one) and with the calling thread's debug knobs (antq_conv2d4_i8_sk_workspace_bytes); 0 when K
+    is not split."""
+    if device is None:
+        return int(lib().antq_conv2d4_i8_sk_workspace_bytes(M, N, K))
+    with _on_device(device):
+        return int(lib().antq_conv2d4_i8_sk_workspace_bytes(M, N, K))
+
+
+def int_conv2d4_sk(codes, xq, alpha_w, image_w, I_w, alpha_x, I_x, N, kernel_size, stride, padding, dilation, per_row, dtype, bias=None,
+                   out=None, workspace=None):
+    """int_conv2d4 for outputs of at most CONV2D4_I8_SK_MAX_M rows (B Ho Wo) with K = R S C split across workgroups
+    (antq_conv2d4_i8_sk): the same arguments, the same bits.  workspace: as for int_linear4_sk, of
+    int_conv2d4_sk_workspace_bytes(B Ho Wo, N, R S C) bytes; None allocates one of that size."""
+    dt, geom, M, out = _int_conv_args(codes, xq, alpha_w, image_w, alpha_x, N, kernel_size, stride, padding, dilation, per_row, dtype, bias,
+                                      out)
+    if workspace is None:
+        workspace = torch.empty(int_conv2d4_sk_workspace_bytes(M, N, geom[3] * geom[5] * geom[6], xq.device), dtype=torch.uint8,
+                                device=xq.device)
+    elif not (workspace.is_cuda and workspace.device == xq.device and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise AntqError("workspace must be a contiguous uint8 tensor on xq's device")
+    with _on_device(xq.device):
+        rc = lib().antq_conv2d4_i8_sk(codes.data_ptr(), xq.data_ptr(), _ptr(bias), out.data_ptr(), *geom, alpha_w.data_ptr(),
+                                      1 if per_row else 0, I_w, image_w.data_ptr(), image_w.numel(), alpha_x.data_ptr(), I_x,
+                                      workspace.data_ptr() if workspace.numel() else None, workspace.numel(), 0, dt,
+                                      _stream_int(xq.device))
+    if rc:
+        _check(rc, "antq_conv2d4_i8_sk")
     return out
 
 

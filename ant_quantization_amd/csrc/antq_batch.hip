@@ -16,6 +16,7 @@
 #include "antq_k_linear_i8_sk.h"
 #include "antq_k_linear8_i8.h"
 #include "antq_k_conv_i8.h"
+#include "antq_k_conv_i8_sk.h"
 
 #include <atomic>
 #include <type_traits>
@@ -794,13 +795,13 @@ extern "C" int antq_linear4_i8(const uint8_t *codes, const int8_t *xq, const voi
     });
 }
 
-// The integer-domain conv2d from 4-bit codes (antq_k_conv_i8.h): an implicit GEMM of M = B Ho Wo rows by K = R S C, the
-// formula, the epilogue and the tile rule antq_linear4_i8's.  Every check comes before anything touches HIP, in the order
-// include/antq.h states; the limits are what the kernel's 32-bit offsets and packed 16-bit row origins need.
-extern "C" int antq_conv2d4_i8(const uint8_t *codes, const int8_t *xq, const void *bias, void *y, size_t B, size_t H, size_t W, size_t C,
-                               size_t N, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
-                               const float *alpha_w, int per_row, int I_w, const int8_t *image_w, int m, const float *alpha_x, int I_x,
-                               unsigned flags, int dtype, void *stream)
+// The checks antq_conv2d4_i8 and antq_conv2d4_i8_sk share, in the order include/antq.h states (kLinearGo: launch, with the
+// call's M = B Ho Wo, K = R S C and geometry); the limits are what the kernels' 32-bit offsets and packed 16-bit row origins
+// need.  Nothing here touches HIP.
+static int conv_i8_checks(const uint8_t *codes, const int8_t *xq, const void *bias, void *y, size_t B, size_t H, size_t W, size_t C, size_t N,
+                          int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, const float *alpha_w,
+                          int I_w, const int8_t *image_w, int m, const float *alpha_x, int I_x, unsigned flags, int dtype, size_t &M,
+                          size_t &K, ConvGeom &g)
 {
     if (!codes || !xq || !y || !alpha_w || !image_w || !alpha_x || m < 1) return ANTQ_ERR_ARG;
     if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_ARG;
@@ -818,7 +819,8 @@ extern "C" int antq_conv2d4_i8(const uint8_t *codes, const int8_t *xq, const voi
     const size_t Ho = (size_t)(eh / stride_h) + 1, Wo = (size_t)(ew / stride_w) + 1;
     // (H, W, R, S, Ho, Wo < 2^15; B and C are bounded first: no product below leaves 64 bits)
     if (B > ANTQ_CONV2D4_I8_MAX_M || C > ANTQ_CONV2D4_I8_MAX_XQ_BYTES || N > 0x7fffffffull) return ANTQ_ERR_UNSUPPORTED;
-    const size_t M = B * Ho * Wo, K = (size_t)R * (size_t)S * C;
+    M = B * Ho * Wo;
+    K = (size_t)R * (size_t)S * C;
     if (M > ANTQ_CONV2D4_I8_MAX_M || B * H * W > ANTQ_CONV2D4_I8_MAX_XQ_BYTES / C) return ANTQ_ERR_UNSUPPORTED;
     if (I_x < 1 || I_x > 127 || I_w < 1 || I_w > 127) return ANTQ_ERR_UNSUPPORTED;
     if ((uint64_t)I_x * (uint64_t)I_w * (uint64_t)K >= (1ull << 31)) return ANTQ_ERR_UNSUPPORTED;      // (the sum could leave int32)
@@ -826,8 +828,23 @@ extern "C" int antq_conv2d4_i8(const uint8_t *codes, const int8_t *xq, const voi
     if (reinterpret_cast<uintptr_t>(xq) % 16 || reinterpret_cast<uintptr_t>(codes) % 16 || reinterpret_cast<uintptr_t>(y) % esz ||
         reinterpret_cast<uintptr_t>(bias) % esz || reinterpret_cast<uintptr_t>(alpha_w) % 4 || reinterpret_cast<uintptr_t>(alpha_x) % 4)
         return ANTQ_ERR_ALIGN;
-    const ConvGeom g{(uint32_t)H, (uint32_t)W, (uint32_t)C, (uint32_t)R, (uint32_t)S, (uint32_t)Wo, (uint32_t)(Ho * Wo),
-                     (uint32_t)stride_h, (uint32_t)stride_w, (uint32_t)dil_h, (uint32_t)dil_w, pad_h, pad_w};
+    g = ConvGeom{(uint32_t)H, (uint32_t)W, (uint32_t)C, (uint32_t)R, (uint32_t)S, (uint32_t)Wo, (uint32_t)(Ho * Wo),
+                 (uint32_t)stride_h, (uint32_t)stride_w, (uint32_t)dil_h, (uint32_t)dil_w, pad_h, pad_w};
+    return kLinearGo;
+}
+
+// The integer-domain conv2d from 4-bit codes (antq_k_conv_i8.h): an implicit GEMM of M = B Ho Wo rows by K = R S C, the
+// formula, the epilogue and the tile rule antq_linear4_i8's.  Every check comes before anything touches HIP.
+extern "C" int antq_conv2d4_i8(const uint8_t *codes, const int8_t *xq, const void *bias, void *y, size_t B, size_t H, size_t W, size_t C,
+                               size_t N, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                               const float *alpha_w, int per_row, int I_w, const int8_t *image_w, int m, const float *alpha_x, int I_x,
+                               unsigned flags, int dtype, void *stream)
+{
+    size_t M, K;
+    ConvGeom g;
+    const int rc = conv_i8_checks(codes, xq, bias, y, B, H, W, C, N, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, alpha_w, I_w,
+                                  image_w, m, alpha_x, I_x, flags, dtype, M, K, g);
+    if (rc != kLinearGo) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int waves, mt;
     i8_shape(M, N, one_of<2, 4>(g_knob_gemm_tile, 0), waves, mt);
@@ -906,6 +923,60 @@ extern "C" int antq_linear4_i8_sk(const uint8_t *codes, const int8_t *xq, const 
                                  per_row ? 1 : 0, I_w, alpha_x, I_x);
                     return launch_status();
                 });
+            });
+        });
+    });
+}
+
+// The slices antq_conv2d4_i8_sk would cut K = R S C into now for M = B Ho Wo output rows: i8_sk_slices, whose tiles count the
+// ceil(M / 64) row tiles and whose traffic cap is per row tile (antq_debug_set key 24 forces it); cus < 1: the device's.
+extern "C" int antq_conv2d4_i8_sk_slices(size_t M, size_t N, size_t K, int cus)
+{
+    if (M == 0 || N == 0 || K == 0) return 0;
+    size_t per_slice;
+    return i8_sk_slices(M, N, K, cus >= 1 ? cus : i8_sk_cus(), g_knob_i8_split, per_slice);
+}
+
+extern "C" size_t antq_conv2d4_i8_sk_workspace_bytes(size_t M, size_t N, size_t K)
+{
+    const int S = antq_conv2d4_i8_sk_slices(M, N, K, 0);
+    return S <= 1 ? 0 : (((size_t)S * M * N * sizeof(int) + 15) & ~(size_t)15);
+}
+
+// antq_conv2d4_i8 for outputs of 1 .. ANTQ_CONV2D4_I8_SK_MAX_M rows with K split across workgroups (antq_k_conv_i8_sk.h): the
+// same checks in the same order, then the row limit (and the finish's grid), the workspace's alignment and -- the one check
+// that asks the device, for its number of compute units -- the workspace's size.  One launch when the rule says one slice,
+// else the slices and the finish.
+extern "C" int antq_conv2d4_i8_sk(const uint8_t *codes, const int8_t *xq, const void *bias, void *y, size_t B, size_t H, size_t W, size_t C,
+                                  size_t N, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                                  const float *alpha_w, int per_row, int I_w, const int8_t *image_w, int m, const float *alpha_x, int I_x,
+                                  void *workspace, size_t workspace_bytes, unsigned flags, int dtype, void *stream)
+{
+    size_t M, K;
+    ConvGeom g;
+    const int rc = conv_i8_checks(codes, xq, bias, y, B, H, W, C, N, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, alpha_w, I_w,
+                                  image_w, m, alpha_x, I_x, flags, dtype, M, K, g);
+    if (rc != kLinearGo) return rc;
+    // (M N / 256 workgroups of k_i8_sk_finish in one grid dimension)
+    if (M > ANTQ_CONV2D4_I8_SK_MAX_M || M * N > 0x7fffffffull * 256) return ANTQ_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(workspace) % 16) return ANTQ_ERR_ALIGN;
+    size_t per_slice;
+    const int slices = i8_sk_slices(M, N, K, i8_sk_cus(), g_knob_i8_split, per_slice);
+    if (slices > 1 && (!workspace || workspace_bytes < (size_t)slices * M * N * sizeof(int))) return ANTQ_ERR_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 blocks((unsigned)((N + kGemmBN - 1) / kGemmBN), (unsigned)slices, (unsigned)((M + kConvSkBM - 1) / kConvSkBM));
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return with_value<1, 2, 4>(M <= 16 ? 1 : M <= 32 ? 2 : 4, [&](auto mm) {
+            return with_bool(slices == 1, [&](auto direct) {
+                launch_k(false, k_conv2d_i8_sk<T, decltype(mm)::value, decltype(direct)::value>, blocks, dim3(256), 0, st, codes, xq, bias, y,
+                         static_cast<int *>(workspace), (uint32_t)M, (uint32_t)N, (uint32_t)K, g, alpha_w, per_row ? 1 : 0, I_w, image_w,
+                         (uint32_t)m, alpha_x, I_x, (uint32_t)per_slice);
+                if constexpr (!decltype(direct)::value)
+                    launch_k(false, k_i8_sk_finish<T>, dim3((unsigned)((M * N + 255) / 256)), dim3(256), 0, st,
+                             static_cast<const int *>(workspace), bias, y, (uint32_t)M, (uint32_t)N, (uint32_t)slices, alpha_w,
+                             per_row ? 1 : 0, I_w, alpha_x, I_x);
+                return launch_status();
             });
         });
     });

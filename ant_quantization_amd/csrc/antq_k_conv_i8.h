@@ -27,7 +27,8 @@
 //   bounds     a piece that counts has 0 <= hi < H, 0 <= wi < W, c0 + 16 <= C, b < B: its 16 bytes lie inside the B H W C
 //              bytes of xq; the stand-in at c0 <= C - 16 does too.  The launcher keeps B H W C below 2^31.
 // Rows run over the flattened B Ho Wo: a tile may cross image and batch boundaries.  xq is read once per tap it takes part
-// in (no LDS halo tile), K is not split.  One launch, no workspace, no atomics; capturable.
+// in (no LDS halo tile), K is not split.  One launch, no workspace, no atomics; capturable.  The split-K form for outputs of
+// up to 1024 rows, which starts the same walker at a slice's first stage: antq_k_conv_i8_sk.h.
 #ifndef ANTQ_K_CONV_I8_H
 #define ANTQ_K_CONV_I8_H
 
@@ -42,27 +43,37 @@ struct ConvGeom {
     int32_t ph, pw;                        // paddings (top, left)
 };
 
-template <int WAVES, int MT>
+// XL: the pieces a thread stages per stage, RSTEP: the rows between them (k_conv2d_i8: I8Tile's; antq_k_conv_i8_sk.h: 1 or 2
+// pieces, 32 rows apart).
+template <int XL, int RSTEP>
 struct I8ConvX {
-    using TL = I8Tile<WAVES, MT>;
     ConvGeom g;
-    uint32_t origin[TL::XL];               // byte offset of xq[b, hi0, wi0, 0] (mod 2^32)
-    uint32_t hw0[TL::XL];                  // hi0 in the low, wi0 in the high 16 bits (int16 each)
+    uint32_t origin[XL];                   // byte offset of xq[b, hi0, wi0, 0] (mod 2^32)
+    uint32_t hw0[XL];                      // hi0 in the low, wi0 in the high 16 bits (int16 each)
     uint32_t r, s, c0;                     // the tap and channel of k = 128 stage + 16 p
     uint32_t ar, as, ac;                   // 128 k as tap rows, taps and channels
 
-    __device__ __forceinline__ ANTQ_I8_KERNEL void init(uint32_t M, uint32_t m0, uint32_t xp, uint32_t xr0)
+    // the walker at piece xp of `stage`: k = 128 stage + 16 xp as (r, s, c0), by division -- once, at entry (a stage past
+    // the last one gives r >= R, which never counts)
+    __device__ __forceinline__ ANTQ_I8_KERNEL void seek(uint32_t stage, uint32_t xp)
     {
-        const uint32_t at = (uint32_t)kGemmBK / g.C, t0 = 16u * xp / g.C;
+        const uint32_t k = stage * (uint32_t)kGemmBK + 16u * xp, t0 = k / g.C;
+        c0 = k % g.C;
+        r = t0 / g.S;
+        s = t0 % g.S;
+    }
+
+    // stage: the first one load() will be asked for (k_conv2d_i8: 0; a slice of K: its first)
+    __device__ __forceinline__ ANTQ_I8_KERNEL void init(uint32_t M, uint32_t m0, uint32_t xp, uint32_t xr0, uint32_t stage = 0u)
+    {
+        const uint32_t at = (uint32_t)kGemmBK / g.C;
         ac = (uint32_t)kGemmBK % g.C;
         ar = at / g.S;
         as = at % g.S;
-        c0 = 16u * xp % g.C;
-        r = t0 / g.S;
-        s = t0 % g.S;
+        seek(stage, xp);
 #pragma unroll
-        for (int i = 0; i < TL::XL; i++) {
-            const uint32_t row = m0 + xr0 + (uint32_t)(TL::RSTEP * i);
+        for (int i = 0; i < XL; i++) {
+            const uint32_t row = m0 + xr0 + (uint32_t)(RSTEP * i);
             const uint32_t rc = min(row, M - 1u);
             const uint32_t b = rc / g.HoWo, rem = rc % g.HoWo, ho = rem / g.Wo, wo = rem % g.Wo;
             const int32_t hi0 = (int32_t)(ho * g.sh) - g.ph, wi0 = (int32_t)(wo * g.sw) - g.pw;
@@ -71,19 +82,23 @@ struct I8ConvX {
         }
     }
 
-    // the next stage's pieces (the stages are asked for in order, 0, 1, 2, ...: the walker moves on after each)
-    __device__ __forceinline__ ANTQ_I8_KERNEL void load(const int8_t *__restrict__ xq, u32x4_t (&xn)[TL::XL])
+    // The next stage's pieces (the stages are asked for in order from init's: the walker moves on after each).  KEEP: a piece
+    // that does not count stays as loaded and xkeep[i] says so -- all ones, or zero -- for the caller to apply at its LDS write
+    // (antq_k_linear_i8_sk.h on why); else it is zeroed here.
+    template <bool KEEP>
+    __device__ __forceinline__ ANTQ_I8_KERNEL void gather(const int8_t *__restrict__ xq, u32x4_t (&xn)[XL], uint32_t (&xkeep)[XL])
     {
         const uint32_t rdh = r * g.dh, sdw = s * g.dw;
         const uint32_t tap = (rdh * g.W + sdw) * g.C + c0;
         const bool kok = r < g.R;
 #pragma unroll
-        for (int i = 0; i < TL::XL; i++) {
+        for (int i = 0; i < XL; i++) {
             const uint32_t hi = (uint32_t)((int32_t)(hw0[i] << 16) >> 16) + rdh, wi = (uint32_t)((int32_t)hw0[i] >> 16) + sdw;
             const bool ok = kok && hi < g.H && wi < g.W;
             const uint32_t off = ok ? origin[i] + tap : c0;
             u32x4_t v = *(const ANTQ_GLOBAL u32x4_t *)(reinterpret_cast<const char *>(xq) + off);
-            if (!ok) v = u32x4_t{0u, 0u, 0u, 0u};
+            if constexpr (KEEP) xkeep[i] = ok ? 0xffffffffu : 0u;
+            else if (!ok) v = u32x4_t{0u, 0u, 0u, 0u};
             xn[i] = v;
         }
         c0 += ac;
@@ -91,6 +106,15 @@ struct I8ConvX {
         r += ar;
         if (c0 >= g.C) { c0 -= g.C; s++; }
         if (s >= g.S) { s -= g.S; r++; }
+    }
+    __device__ __forceinline__ ANTQ_I8_KERNEL void load(const int8_t *__restrict__ xq, u32x4_t (&xn)[XL])
+    {
+        uint32_t unused[XL];
+        gather<false>(xq, xn, unused);
+    }
+    __device__ __forceinline__ ANTQ_I8_KERNEL void load(const int8_t *__restrict__ xq, u32x4_t (&xn)[XL], uint32_t (&xkeep)[XL])
+    {
+        gather<true>(xq, xn, xkeep);
     }
 };
 
@@ -100,9 +124,10 @@ k_conv2d_i8(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq, co
             uint32_t M, uint32_t N, uint32_t K, const ConvGeom g, const float *__restrict__ alpha_w, int per_row, int I_w,
             const int8_t *__restrict__ image_w, uint32_t m, const float *__restrict__ alpha_x, int I_x)
 {
-    I8ConvX<WAVES, MT> xs;
+    using TL = I8Tile<WAVES, MT>;
+    I8ConvX<TL::XL, TL::RSTEP> xs;
     xs.g = g;
-    xs.init(M, blockIdx.y * (uint32_t)I8Tile<WAVES, MT>::BM, threadIdx.x & 7u, threadIdx.x >> 3);
+    xs.init(M, blockIdx.y * (uint32_t)TL::BM, threadIdx.x & 7u, threadIdx.x >> 3);
     i8_tile<T, false, WAVES, MT>(codes, xq, bias, y, M, N, K, alpha_w, per_row, I_w, image_w, m, 0, alpha_x, I_x, xs);
 }
 

@@ -76,20 +76,21 @@ static inline void i8_shape(size_t M, size_t N, int forced_waves, int &waves, in
     mt = 4;
 }
 
-// The slices of K of the split-K form (antq_k_linear_i8_sk.h, M <= 64) on a part of `cus` compute units.  tiles = ceil(N / 64)
-// workgroups exist per slice, a slice is a whole number of 128-k stages:
+// The slices of K of the split-K forms (antq_k_linear_i8_sk.h, M <= 64; antq_k_conv_i8_sk.h, row tiles of 64) on a part of
+// `cus` compute units.  tiles = ceil(N / 64) ceil(M / 64) workgroups exist per slice, Mt = min(M, 64) rows per row tile, a
+// slice is a whole number of 128-k stages:
 //   S = the smallest of 1, 2, 4, 8, 16 with tiles S >= 2 cus (16 when none has)      two workgroups per CU
-//   S <= K / (16 M)                           above it the 8 S M N bytes of partial traffic exceed the N K / 2 bytes of codes
+//   S <= K / (16 Mt)       per row tile: above it the 8 S Mt N bytes of partial traffic exceed the N K / 2 bytes of codes
 //   S <= stages; forced (antq_debug_set key 24, 1 .. 16) replaces the rule and is clamped to stages alone
 //   per_slice = ceil(stages / S) stages, and S becomes the number of non-empty slices, ceil(stages / per_slice)
 // The sum is exact, so no result depends on S: the rule is for time alone.
 static inline int i8_sk_slices(size_t M, size_t N, size_t K, int cus, int forced, size_t &per_slice)
 {
-    const size_t tiles = (N + 63) / 64, stages = (K + 127) / 128;
+    const size_t tiles = ((N + 63) / 64) * ((M + 63) / 64), stages = (K + 127) / 128;
     size_t S = 16;
     for (size_t s = 1; s <= 16; s *= 2)
         if (tiles * s >= 2 * (size_t)std::max(cus, 1)) { S = s; break; }
-    S = std::min(S, std::max<size_t>(K / (16 * M), 1));
+    S = std::min(S, std::max<size_t>(K / (16 * std::min<size_t>(M, 64)), 1));
     if (forced >= 1) S = (size_t)std::min(forced, 16);
     S = std::max<size_t>(std::min(S, stages), 1);
     per_slice = (stages + S - 1) / S;

@@ -4,7 +4,8 @@
 // k_linear_i8 gives such a call ceil(N / 64) workgroups that each walk all of K through LDS; here the weights never touch
 // LDS, no two wavefronts share one, and K is cut into S slices (the launcher's rule: i8_sk_slices) -- the one place in the
 // library where that costs no determinism, because an exact sum has no order.
-// Part of libantq's batched translation unit (antq_batch.hip includes it); gfx950 only.
+// Part of libantq's batched translation unit (antq_batch.hip includes it); gfx950 only.  Everything below but the source of the
+// A operand lives in i8_sk_tile, which antq_k_conv_i8_sk.h shares: k_linear_i8_sk is i8_sk_tile with the matrix A side.
 //
 //   ownership  grid x = tiles of 64 output rows n, grid y = the S slices of K, a slice = per_slice stages of 128 k (the last
 //              one may be shorter).  A workgroup has 4 wavefronts; wavefront w owns the 16 output rows n0 + 16 w .. + 15 for
@@ -55,18 +56,29 @@ __device__ __forceinline__ ANTQ_I8_KERNEL void i8_sk_store(void *y, size_t idx, 
     IO<T>::store1(y, idx, v);
 }
 
-template <typename T, bool OVP, int MT, bool DIRECT>
-__global__ void __launch_bounds__(256) ANTQ_I8_KERNEL
-k_linear_i8_sk(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq, const void *__restrict__ bias, void *__restrict__ y,
-               int *__restrict__ workspace, uint32_t M, uint32_t N, uint32_t K, const float *__restrict__ alpha_w, int per_row, int I_w,
-               const int8_t *__restrict__ image_w, uint32_t m, int n_normal, const float *__restrict__ alpha_x, int I_x,
-               uint32_t per_slice)
+// The constants of an MT tile that the split-K kernels and their A sides share
+template <int MT>
+struct I8SkTile {
+    static constexpr int ROWS = 16 * MT;               // rows of xq of the workgroup
+    static constexpr int XROWS = ROWS < 32 ? 32 : ROWS;        // ... of the image: every thread stages (rows >= M are zeros anyway)
+    static constexpr int PIECES = kGemmBK / 16;        // 16-byte pieces of a row of xq per stage
+    static constexpr int XP = XROWS * PIECES;          // pieces of xq per stage
+    static constexpr int XL = XP / 256;                // ... per thread: piece tid & 7 of rows (tid >> 3) + 32 i
+};
+
+// One (64 output rows n, slice of K, ROWS rows m0 .. of the A operand) tile of the split-K form and its stores, as the header
+// states it: everything of k_linear_i8_sk but where a piece of the A operand comes from -- a row-major matrix xq [M, K]
+// (XS = I8Matrix, m0 = 0), or whatever xs.load(xq, xn, xkeep) gathers for the next stage, asked in order from the slice's
+// first one (antq_k_conv_i8_sk.h: im2col).  y and every slice of the workspace are [M, N] row-major.
+template <typename T, bool OVP, int MT, bool DIRECT, typename XS>
+__device__ __forceinline__ ANTQ_I8_KERNEL void
+i8_sk_tile(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq, const void *__restrict__ bias, void *__restrict__ y,
+           int *__restrict__ workspace, uint32_t M, uint32_t N, uint32_t K, const float *__restrict__ alpha_w, int per_row, int I_w,
+           const int8_t *__restrict__ image_w, uint32_t m, int n_normal, const float *__restrict__ alpha_x, int I_x,
+           uint32_t per_slice, const uint32_t m0, XS &xs)
 {
-    constexpr int ROWS = 16 * MT;                      // rows of xq of the workgroup
-    constexpr int XROWS = ROWS < 32 ? 32 : ROWS;       // ... of the image: every thread stages (rows >= M are zeros anyway)
-    constexpr int PIECES = kGemmBK / 16;               // 16-byte pieces of a row of xq per stage
-    constexpr int XP = XROWS * PIECES;                 // pieces of xq per stage
-    constexpr int XL = XP / 256;                       // ... per thread
+    using TL = I8SkTile<MT>;
+    constexpr int PIECES = TL::PIECES, XP = TL::XP, XL = TL::XL;
     static_assert((MT == 1 || MT == 2 || MT == 4) && PIECES == 8 && kGemmBK == 128 && kGemmBN == 64, "the maps below");
     struct Lds {
         u32x4_t xs[2][XP];                             // the staged xq of two stages: piece p of row r at [8 r + (p ^ (r & 7))]
@@ -91,15 +103,17 @@ k_linear_i8_sk(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq,
     uint32_t xkeep[XL];                                // all ones, or zero for a piece that is zeros: applied at the write -- a
                                                        // select or a mask at the load would wait for the load there and then
     auto load_x = [&](uint32_t c) __attribute__((always_inline)) {
-        const uint32_t k0 = min(c, c1 - 1u) * (uint32_t)kGemmBK + 16u * xp;
-        const bool kok = k0 < K;
-        const size_t koff = (size_t)min(k0, K - 16u);
+        if constexpr (std::is_same<XS, I8Matrix>::value) {
+            const uint32_t k0 = min(c, c1 - 1u) * (uint32_t)kGemmBK + 16u * xp;
+            const bool kok = k0 < K;
+            const size_t koff = (size_t)min(k0, K - 16u);
 #pragma unroll
-        for (int i = 0; i < XL; i++) {
-            const uint32_t r = xr0 + 32u * i;
-            xn[i] = *(const ANTQ_GLOBAL u32x4_t *)(reinterpret_cast<const char *>(xq) + (size_t)min(r, M - 1u) * K + koff);
-            xkeep[i] = (kok && r < M) ? 0xffffffffu : 0u;
-        }
+            for (int i = 0; i < XL; i++) {
+                const uint32_t r = xr0 + 32u * i;
+                xn[i] = *(const ANTQ_GLOBAL u32x4_t *)(reinterpret_cast<const char *>(xq) + (size_t)min(r, M - 1u) * K + koff);
+                xkeep[i] = (kok && r < M) ? 0xffffffffu : 0u;
+            }
+        } else xs.load(xq, xn, xkeep);                 // (the stages c0, c0 + 1, ... in order, past the slice's end too)
     };
     auto write_x = [&](uint32_t buf) __attribute__((always_inline)) {
 #pragma unroll
@@ -191,7 +205,7 @@ k_linear_i8_sk(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq,
         for (int mt = 0; mt < MT; mt++)
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                const uint32_t mrow = 16u * mt + 4u * kg + r;
+                const uint32_t mrow = m0 + 16u * mt + 4u * kg + r;
                 if (mrow < M) i8_sk_store<T>(y, (size_t)mrow * N + n, acc[mt][r], u_x, u_w, bias != nullptr, bv);
             }
     } else {
@@ -200,10 +214,22 @@ k_linear_i8_sk(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq,
         for (int mt = 0; mt < MT; mt++)
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                const uint32_t mrow = 16u * mt + 4u * kg + r;
+                const uint32_t mrow = m0 + 16u * mt + 4u * kg + r;
                 if (mrow < M) part[(size_t)mrow * N] = acc[mt][r];
             }
     }
+}
+
+template <typename T, bool OVP, int MT, bool DIRECT>
+__global__ void __launch_bounds__(256) ANTQ_I8_KERNEL
+k_linear_i8_sk(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq, const void *__restrict__ bias, void *__restrict__ y,
+               int *__restrict__ workspace, uint32_t M, uint32_t N, uint32_t K, const float *__restrict__ alpha_w, int per_row, int I_w,
+               const int8_t *__restrict__ image_w, uint32_t m, int n_normal, const float *__restrict__ alpha_x, int I_x,
+               uint32_t per_slice)
+{
+    I8Matrix xs;
+    i8_sk_tile<T, OVP, MT, DIRECT>(codes, xq, bias, y, workspace, M, N, K, alpha_w, per_row, I_w, image_w, m, n_normal, alpha_x, I_x,
+                                   per_slice, 0u, xs);
 }
 
 // y[m, n] from the S partial sums workspace[s][m][n]: added as integers, then the epilogue.  One thread per output.

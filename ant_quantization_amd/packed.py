@@ -162,6 +162,14 @@ integer_linear_call's conditions on the weight and the input quantiser, for a 4-
 channels-last memory, so a chain of served layers pays no relayout after the first.  OliVe's wrapper, byte-coded conv layers and
 groups are out of scope.  With the option off every launch and every bit is today's.  Measurements and verdict:
 profiles/int_conv4.md, DESIGN.md 5t.
+
+`integer_conv_split_k=True` (needs fused_linear, integer_linear and integer_conv) sends the served conv calls whose output has at
+most `_lib.CONV2D4_I8_SK_MAX_M` = 1024 positions B Ho Wo -- single-image and small-batch inference, the 7 x 7 and 14 x 14 stages
+-- to `antq_conv2d4_i8_sk`, which cuts K = R S C across workgroups as `antq_linear4_i8_sk` does (`.int_conv_sk_calls`; they still
+count in `.int_conv_calls`).  The sum is an exact integer, so the bits are those of `antq_conv2d4_i8`: the flag changes launches
+and time, never a result.  The partial sums go through the bank's one workspace per device, the one `integer_split_k` uses.  A
+flag, not a rows option.  Larger outputs run `antq_conv2d4_i8` as before; with the flag off every launch and every bit is
+today's, in banks that set `integer_split_k` too.  Measurements: profiles/int_conv4_sk.md, DESIGN.md 5u.
 """
 from collections import namedtuple
 
@@ -194,6 +202,7 @@ _OPTIONS = (
     _Option("integer_split_k", False, ("fused_linear", "integer_linear"), None),
     _Option("integer_bytes", False, ("fused_linear", "fused_bytes", "integer_linear"), None),
     _Option("integer_conv", False, ("fused_linear", "integer_linear"), None),
+    _Option("integer_conv_split_k", False, ("fused_linear", "integer_linear", "integer_conv"), None),
 )
 _NOTES = {("PackedBank", "keep_images"): " (nothing else computes from the codes)"}
 
@@ -259,7 +268,7 @@ class PackedBank:
     def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True, fused_rows=None,
                  byte_codes=False, fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None,
                  fused_conv1d=False, fused_conv1d_mm=False, fused_conv1d_gemm=False, integer_linear=False,
-                 integer_split_k=False, integer_bytes=False, integer_conv=False):
+                 integer_split_k=False, integer_bytes=False, integer_conv=False, integer_conv_split_k=False):
         """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict);
         a layer's code width is then the one its stored size says (numel / 2 bytes: 4-bit, numel bytes: byte codes).
         Every other parameter: see the module docstring."""
@@ -284,8 +293,9 @@ class PackedBank:
         self.int_linear_byte_calls = 0  # ... of int_linear_calls, those from byte codes: antq_linear8_i8 (or _sk) (integer_bytes)
         self.int_linear_byte_sk_calls = 0  # ... of them through antq_linear8_i8_sk
         self.int_conv_calls = 0    # forwards antq_quant_i8 + antq_conv2d4_i8 served (integer_conv)
+        self.int_conv_sk_calls = 0  # ... of them through antq_conv2d4_i8_sk (integer_conv_split_k)
         self.int_conv_relayouts = 0  # ... of them whose input was copied to channels-last memory first
-        self._sk_workspace = {}    # device -> the one workspace of antq_linear4_i8_sk / antq_linear8_i8_sk, grown on demand
+        self._sk_workspace = {}    # device -> the one workspace of antq_linear4_i8_sk / antq_linear8_i8_sk / antq_conv2d4_i8_sk, grown on demand
         self.launches = 0          # decode launches so far (one per (device, dtype, pair rule, code width) group and refresh)
         self.dirty = True
         self._batches = []
@@ -709,8 +719,19 @@ class PackedBank:
         self._integer_units(e, qi, plan_w, gmax_w, plan_x, gmax_x)
         xq = _lib.quant_i8(input.permute(0, 2, 3, 1), e["alpha_x"], plan_x, gmax_x, 1, input.numel(), False, plan_x.image_dev(dev))
         self.int_conv_calls += 1
-        return _lib.int_conv2d4(e["conv_codes"], xq, e["unit_w"], plan_w.image_dev(dev), e["integer"], e["unit_x"], image_x[0], N, (R, S),
-                                (sh, sw), (ph, pw), (dh, dw), e["per_row"], e["dtype"], bias=None if bias is None else bias.detach())
+        args = (e["conv_codes"], xq, e["unit_w"], plan_w.image_dev(dev), e["integer"], e["unit_x"], image_x[0], N, (R, S), (sh, sw), (ph, pw),
+                (dh, dw), e["per_row"], e["dtype"])
+        bias = None if bias is None else bias.detach()
+        M = B * Ho * Wo
+        if getattr(self, "integer_conv_split_k", False) and M <= _lib.CONV2D4_I8_SK_MAX_M:
+            # K = R S C split across workgroups: the same bits, on the bank's one workspace per device (integer_linear_call)
+            need = _lib.int_conv2d4_sk_workspace_bytes(M, N, C * R * S, dev)
+            ws = self._sk_workspace.get(dev)
+            if ws is None or ws.numel() < need:
+                ws = self._sk_workspace[dev] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+            self.int_conv_sk_calls += 1
+            return _lib.int_conv2d4_sk(*args, bias=bias, workspace=ws)
+        return _lib.int_conv2d4(*args, bias=bias)
 
     def _integer_byte_call(self, e, mod, xq, plan_w, I_x, M):
         """(integer_bytes) integer_linear_call's product for a byte-coded entry: antq_linear8_i8, or its split-K form."""
@@ -811,7 +832,7 @@ def pack_model(model, release_weights=False, **options):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
     (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
     options: fused_linear, keep_images, fused_rows, byte_codes, fused_bytes, fused_byte_rows, fused_gemm_rows,
-    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes, integer_conv -- PackedBank's keywords with its defaults; see the module docstring."""
+    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes, integer_conv, integer_conv_split_k -- PackedBank's keywords with its defaults; see the module docstring."""
     return PackedBank(model, release_weights, None, **options)     # (codes: not an option here -- given, it is a TypeError)
 
 
@@ -840,7 +861,7 @@ def load_packed_state_dict(model, sd, release_weights=True, **options):
     any other size raises AntqError naming the layer), and the weights are materialised by the batched decode
     (release_weights=False: copied into the layers' own float weights instead of replacing them).
     options: fused_linear, keep_images, fused_rows, fused_bytes, fused_byte_rows, fused_gemm_rows, fused_byte_gemm_rows,
-    fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes, integer_conv, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
+    fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes, integer_conv, integer_conv_split_k, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
     _check_options("load_packed_state_dict", **options)        # (before the model is touched)
     suffix = "." + CODES_KEY
     codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}

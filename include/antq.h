@@ -1040,6 +1040,40 @@ int antq_conv2d4_i8(const uint8_t *codes_dev /* N*R*S*C/2 bytes */, const int8_t
                     int dtype /* F32 | BF16 | F16: y and bias */, void *stream);
 
 /* -------------------------------------------------------------------------
+ * antq_conv2d4_i8_sk: antq_conv2d4_i8 for outputs of 1 .. ANTQ_CONV2D4_I8_SK_MAX_M rows (M = B Ho Wo: single-image and
+ * small-batch inference, the 7 x 7 and 14 x 14 stages of a CNN) with K = R S C split across workgroups -- what
+ * antq_linear4_i8_sk is to antq_linear4_i8.  The formula, the operands and their rules are antq_conv2d4_i8's, and so are the
+ * bits.  The launcher cuts K into 1 .. 16 slices of whole 128-k stages (csrc/antq_k_linear_i8.h: i8_sk_slices, with
+ * ceil(N / 64) ceil(M / 64) workgroups per slice and min(M, 64) rows in the traffic cap); every slice's workgroups write their
+ * int32 partial sums to workspace[slice][m][n], and a second small launch adds them as integers and applies the scales.
+ * With one slice there is one launch and no workspace.  No atomics, no order between workgroups.
+ *
+ * antq_conv2d4_i8_sk_slices(M, N, K, cus) and antq_conv2d4_i8_sk_workspace_bytes(M, N, K): as antq_linear4_i8_sk's helpers,
+ * for M = B Ho Wo and K = R S C: the slices the launcher would use NOW on the calling thread (cus >= 1: on a part of that many
+ * compute units; 0 for an empty call), and 0 with one slice, else 4 * slices * M * N rounded up to 16.  The workspace's previous
+ * contents are never read; the call writes its first 4 * slices * M * N bytes and nothing beyond.
+ *
+ * Refusals: antq_conv2d4_i8's, all of them, in its order; then, in this order,
+ *   ANTQ_ERR_UNSUPPORTED  B Ho Wo > ANTQ_CONV2D4_I8_SK_MAX_M (above it antq_conv2d4_i8 has 4 .. 16 row tiles per channel
+ *                         tile); B Ho Wo * N > (2^31 - 1) * 256 (the second launch's grid)
+ *   ANTQ_ERR_ALIGN        a non-null workspace_dev that is not 16-byte aligned
+ *   ANTQ_ERR_ARG          the call needs a workspace and workspace_dev is null or workspace_bytes too small
+ * Every check but the last comes before anything touches HIP; the last asks the device for its number of compute units
+ * (once per device; 256 when there is none) and nothing else.  A refused call launches and writes nothing.  antq_debug_set
+ * key 24 forces the slices as for antq_linear4_i8_sk.  One or two launches, stream-ordered, capturable; no allocation.
+ * Kernel: csrc/antq_k_conv_i8_sk.h.  Measurements: profiles/int_conv4_sk.md.
+ * ------------------------------------------------------------------------- */
+#define ANTQ_CONV2D4_I8_SK_MAX_M 1024
+int antq_conv2d4_i8_sk_slices(size_t M, size_t N, size_t K, int cus);
+size_t antq_conv2d4_i8_sk_workspace_bytes(size_t M, size_t N, size_t K);
+int antq_conv2d4_i8_sk(const uint8_t *codes_dev /* N*R*S*C/2 bytes */, const int8_t *xq_dev /* [B, H, W, C] */,
+                       const void *bias_dev /* N or NULL */, void *y_dev /* [B, Ho, Wo, N] */, size_t B, size_t H, size_t W, size_t C,
+                       size_t N, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                       const float *alpha_w_dev, int alpha_per_row, int I_w, const int8_t *image_w_dev, int m,
+                       const float *alpha_x_dev /* one float */, int I_x, void *workspace_dev, size_t workspace_bytes,
+                       unsigned flags /* 0 */, int dtype /* F32 | BF16 | F16: y and bias */, void *stream);
+
+/* -------------------------------------------------------------------------
  * OliVe's clip statistic on ONE read (replaces t.mean() + t.std() of olive_quantization/antquant/quant_modules.py:193-197
  * and :213-218, which read the tensor at least three times before the clip search reads it again).
  * antq_moments: sums_dev[2 r] = sum of x, sums_dev[2 r + 1] = sum of x^2 over row r (alpha_per_row) or over the whole

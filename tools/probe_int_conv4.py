@@ -11,7 +11,11 @@ captured graph of calls per arm, the arms ALTERNATED inside every repetition; th
 
 Signed flint-4 weights with one scale per output channel, unsigned int-4 activations (post-ReLU) with one scale, bias.
 
+    K   (--sk) antq_quant_i8 + antq_conv2d4_i8_sk, the input channels-last   (pack_model(integer_conv_split_k=True)); measured
+        against I and A at the points whose output has at most CONV2D4_I8_SK_MAX_M rows, `--force S` with forced slices
+
     python tools/probe_int_conv4.py [--quick] [--out profiles/int_conv4]      (writes .json and .md)
+    python tools/probe_int_conv4.py --sk [--force S] [--every n] [--dtype bfloat16] --out profiles/int_conv4_sk
 """
 import argparse
 import json
@@ -71,8 +75,42 @@ def write_md(rows, path, args):
         f.write("\n".join(out))
 
 
+def write_md_sk(rows, path, args):
+    """--sk: K = antq_quant_i8 + antq_conv2d4_i8_sk against I and A, the points where the rule gives one slice apart"""
+    out = ["# antq_conv2d4_i8_sk (split-K) against antq_conv2d4_i8 and today's forward, outputs of up to 1024 rows", "",
+           "Written by `tools/probe_int_conv4.py --sk`: one MI355X, one process; the protocol of profiles/int_conv4.md (every arm from "
+           "the RAW channels-last input, distinct weight buffers in rotation, per point %d repetitions of one graph-replayed batch of "
+           "calls per arm, the arms alternated inside a repetition; medians in us per call, `spread` = the largest (max - min) / median "
+           "of the point's arms).  K = antq_quant_i8 + antq_conv2d4_i8_sk, I = antq_quant_i8 + antq_conv2d4_i8 (the parent's kernel), "
+           "A = antq_fakequant + F.conv2d on the kept image, the faster input layout.  K / I and K / A are TIMES: below 1, K is "
+           "faster.  `won` / `lost`: by more than the point's spread.  `forced`: slices set with antq_debug_set key 24 (0: the rule)." % args.reps, ""]
+    for dt in sorted({r["dtype"] for r in rows}):
+        for title, rs in (("the rule splits K", [r for r in rows if r["dtype"] == dt and r["slices"] > 1 and not r["forced"]]),
+                          ("the rule gives one slice", [r for r in rows if r["dtype"] == dt and r["slices"] == 1 and not r["forced"]]),
+                          ("forced slices", [r for r in rows if r["dtype"] == dt and r["forced"]])):
+            if not rs:
+                continue
+            out += ["## %s, %s" % (dt, title), ""]
+            for k, name in (("k_over_i", "K / I"), ("k_over_a", "K / A")):
+                out.append("%s: %d points, won %d, lost %d, %s.  " % (name, len(rs), sum(r[k] < 1 - r["spread"] for r in rs),
+                                                                     sum(r[k] > 1 + r["spread"] for r in rs), _range([r[k] for r in rs])))
+            out += ["", "| C -> N, k / stride, input | B | M | K | slices | calls | K | I | A | K / I | K / A | spread |", "|---|---|---|---|---|---|---|---|---|---|---|---|"]
+            for r in rs:
+                out.append("| %d -> %d, %d / %d, %d x %d | %d | %d | %d | %d | %d | %.1f | %.1f | %.1f | %.2f | %.2f | %.1f %% |" % (
+                    r["C"], r["N"], r["k"], r["stride"], r["H"], r["H"], r["B"], r["M"], r["K"], r["slices"], r["calls"], r["us_k"], r["us_i"],
+                    r["us_a"], r["k_over_i"], r["k_over_a"], 100 * r["spread"]))
+            out.append("")
+    if args.notes and os.path.exists(args.notes):
+        out += [open(args.notes).read()]
+    with open(path, "w") as f:
+        f.write("\n".join(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sk", action="store_true", help="the split-K arm K against I and A, at the points of at most CONV2D4_I8_SK_MAX_M rows")
+    ap.add_argument("--force", type=int, default=0, help="(--sk) slices forced with antq_debug_set key 24")
+    ap.add_argument("--every", type=int, default=1, help="(--sk) every n-th shape only")
     ap.add_argument("--quick", action="store_true", help="bfloat16, batch 8, every fourth shape")
     ap.add_argument("--dtype", default=None, help="float32 or bfloat16 alone (a run split in two; merge with --rewrite)")
     ap.add_argument("--flop", type=float, default=1e11, help="operations per graph, about")
@@ -88,7 +126,7 @@ def main():
         if a.out:
             with open(a.out + ".json", "w") as f:
                 json.dump(rows, f, indent=1)
-        write_md(rows, (a.out or os.path.splitext(a.rewrite)[0]) + ".md", a)
+        (write_md_sk if a.sk else write_md)(rows, (a.out or os.path.splitext(a.rewrite)[0]) + ".md", a)
         return
     if not torch.cuda.is_available():
         raise SystemExit("probe_int_conv4: no GPU -- nothing is measured without one")
@@ -101,7 +139,7 @@ def main():
     rows = []
     for dt in ((getattr(torch, a.dtype),) if a.dtype else (torch.bfloat16,) if a.quick else (torch.float32, torch.bfloat16)):
         esz = torch.empty(0, dtype=dt).element_size()
-        for C, N, k, stride, pad, H in (SHAPES[::4] if a.quick else SHAPES):
+        for C, N, k, stride, pad, H in (SHAPES[::4] if a.quick else SHAPES[::a.every] if a.sk else SHAPES):
             K = C * k * k
             w = (torch.randn(N, C, k, k, device=dev) * 0.05).to(dt)
             alpha = (w.float().abs().amax((1, 2, 3)) * 0.9).contiguous()
@@ -114,6 +152,8 @@ def main():
             for B in ((8,) if a.quick else BATCHES):
                 Ho = (H + 2 * pad - k) // stride + 1
                 M = B * Ho * Ho
+                if a.sk and M > _lib.CONV2D4_I8_SK_MAX_M:
+                    continue
                 iters = int(min(a.max_iters, max(a.min_iters, a.flop / (2.0 * M * N * K))))
                 n_buf = int(min(iters, max(2, -(-ROTATE_BYTES // (K * N * esz)))))
                 images, taps = [image0.clone() for _ in range(n_buf)], [taps0.clone() for _ in range(n_buf)]
@@ -135,6 +175,30 @@ def main():
                                    out=dst.permute(0, 2, 3, 1) if last else dst)
                     return F.conv2d(dst, images[i], bias, stride, pad)
 
+                if a.sk:
+                    _lib.lib().antq_debug_set(24, a.force)
+                    slices = _lib.lib().antq_conv2d4_i8_sk_slices(M, N, K, 0)
+                    ws = torch.empty(max(_lib.int_conv2d4_sk_workspace_bytes(M, N, K), 16), dtype=torch.uint8, device=dev)
+
+                    def split(i):
+                        _lib.quant_i8(x_cl.permute(0, 2, 3, 1), ax, plan_x, gmax_x, 1, x_cl.numel(), False, img_x, out=xq)
+                        return _lib.int_conv2d4_sk(taps[i], xq, unit_w, img_w, I_w, unit_x, I_x, N, k, stride, pad, 1, True, dt, bias=bias,
+                                                   out=y, workspace=ws)
+
+                    t = alternate({"K": capture(split, n_buf, iters, 3), "I": capture(lambda i: integer(x_cl, i), n_buf, iters, 3),
+                                   "A": capture(lambda i: image(x, xf, i), n_buf, iters, 3),
+                                   "ACL": capture(lambda i: image(x_cl, xf_cl, i), n_buf, iters, 3)}, iters, a.reps)
+                    _lib.lib().antq_debug_set(24, 0)
+                    us = {key: v[0] for key, v in t.items()}
+                    us_a = min(us["A"], us["ACL"])
+                    r = dict(dtype=str(dt).split(".")[1], C=C, N=N, k=k, stride=stride, H=H, B=B, M=M, K=K, calls=iters, buffers=n_buf,
+                             forced=a.force, slices=slices, us_k=round(us["K"], 2), us_i=round(us["I"], 2), us_a=round(us_a, 2),
+                             k_over_i=round(us["K"] / us["I"], 3), k_over_a=round(us["K"] / us_a, 3),
+                             spread=round(max(v[1] for v in t.values()), 4))
+                    rows.append(r)
+                    print(json.dumps(r), flush=True)
+                    del t, images, taps
+                    continue
                 graphs = {"I": capture(lambda i: integer(x_cl, i), n_buf, iters, 3),
                           "IN": capture(lambda i: integer(x.contiguous(memory_format=torch.channels_last), i), n_buf, iters, 3),
                           "A": capture(lambda i: image(x, xf, i), n_buf, iters, 3),
@@ -155,7 +219,7 @@ def main():
                 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
                 with open(a.out + ".json", "w") as f:
                     json.dump(rows, f, indent=1)
-                write_md(rows, a.out + ".md", a)
+                (write_md_sk if a.sk else write_md)(rows, a.out + ".md", a)
 
 
 if __name__ == "__main__":
