@@ -39,6 +39,7 @@ LINEAR8_I8_MAX_M = 1 << 20  # include/antq.h ANTQ_LINEAR8_I8_MAX_M: rows of xq a
 CONV2D4_I8_MAX_DIM = 8191   # include/antq.h ANTQ_CONV2D4_I8_MAX_DIM: H, W, R, S, strides, paddings, dilations of antq_conv2d4_i8
 CONV2D4_I8_MAX_M = 1 << 22  # include/antq.h ANTQ_CONV2D4_I8_MAX_M: output positions B * Ho * Wo
 CONV2D4_I8_MAX_XQ_BYTES = 0x7fffffff  # include/antq.h ANTQ_CONV2D4_I8_MAX_XQ_BYTES: bytes of xq
+QUANT_I8_NHWC_MAX_BYTES = 0x7fffffff  # include/antq.h ANTQ_QUANT_I8_NHWC_MAX_BYTES: bytes quant_i8_nhwc writes
 CONV2D4_I8_SK_MAX_M = 1024  # include/antq.h ANTQ_CONV2D4_I8_SK_MAX_M: output positions B * Ho * Wo antq_conv2d4_i8_sk takes
 LINEAR8_I8_SK_MAX_M = 64  # include/antq.h ANTQ_LINEAR8_I8_SK_MAX_M: rows of xq antq_linear8_i8_sk takes
 PLAN_MAX_BYTES = 128 + 4 * MAX_GRID + 16 * 3072 + 20 * 1024 + 16 * 64
@@ -82,7 +83,7 @@ def lib():
                              "antq_linear8_gemm", "antq_linear4_t", "antq_linear4_t_mm", "antq_linear4_t_gemm", "antq_fakequant_outlier",
                              "antq_abs_order_stats", "antq_quant_i8", "antq_linear4_i8", "antq_linear4_i8_sk",
                              "antq_linear4_i8_sk_slices", "antq_linear8_i8", "antq_linear8_i8_sk", "antq_linear8_i8_sk_slices",
-                             "antq_conv2d4_i8", "antq_conv2d4_i8_sk", "antq_conv2d4_i8_sk_slices"):
+                             "antq_conv2d4_i8", "antq_conv2d4_i8_sk", "antq_conv2d4_i8_sk_slices", "antq_quant_i8_nhwc"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
                 L.antq_decode4_batch_capacity.restype = ctypes.c_size_t
@@ -130,6 +131,7 @@ def lib():
                 L.antq_conv2d4_i8_sk.argtypes = L.antq_conv2d4_i8.argtypes[:24] + [vp, sz] + L.antq_conv2d4_i8.argtypes[24:]
                 L.antq_conv2d4_i8_sk_workspace_bytes.argtypes = [sz, sz, sz]
                 L.antq_conv2d4_i8_sk_slices.argtypes = [sz, sz, sz, ci]
+                L.antq_quant_i8_nhwc.argtypes = [vp, vp, sz, sz, sz, vp, cf, vp, vp, vp, cu, ci, vp]
                 # development: ANTQ_DEBUG_KNOBS="14=2,0=8" applies antq_debug_set(key, value) pairs to the loading thread
                 # (the knobs are thread-local; tools/fuzz_campaign.sh forces code paths with it)
                 for kv in [k for k in os.environ.get("ANTQ_DEBUG_KNOBS", "").split(",") if "=" in k]:
@@ -1257,6 +1259,33 @@ def quant_i8(x, alpha, plan, gmax, rows, row_len, per_row, image, n_normal=0, ov
     if rc:
         _check(rc, "antq_quant_i8")
     return out
+
+
+def quant_i8_nhwc(x, alpha, plan, gmax, image, out=None):
+    """quant_i8 of a contiguous [B, C, H, W] tensor with one scale and a plain book, written in NHWC order
+    (antq_quant_i8_nhwc): int8 [B, H, W, C], the bytes quant_i8 gives for a channels-last copy of x, without the copy.  C must be
+    a multiple of 16.  out: a caller-owned contiguous, 16-byte-aligned int8 buffer of numel bytes.  Returns it, shaped [B, H, W, C]."""
+    _require_gpu(x, "x")
+    _require_gpu(image, "image")
+    dt = _DTYPES.get(x.dtype)
+    if dt is None or dt == F64:
+        raise AntqError("unsupported dtype %s" % x.dtype)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise AntqError("x must be a contiguous [B, C, H, W] tensor")
+    if image.dtype != torch.int8 or image.numel() != plan.grid.size or image.device != x.device or not image.is_contiguous():
+        raise AntqError("image must be a contiguous int8 tensor of the book's %d values on x's device" % plan.grid.size)
+    B, C, H, W = x.shape
+    if out is None:
+        out = torch.empty((B, H, W, C), dtype=torch.int8, device=x.device)
+    elif not (out.is_cuda and out.device == x.device and out.dtype == torch.int8 and out.numel() == x.numel() and out.is_contiguous()):
+        raise AntqError("out must be a contiguous int8 tensor of numel bytes on x's device")
+    pd = plan.dev(x.device)
+    with _on_device(x.device):
+        rc = lib().antq_quant_i8_nhwc(x.data_ptr(), out.data_ptr(), B, C, H * W, alpha.data_ptr(), gmax, plan.host_ptr(), pd.data_ptr(),
+                                      image.data_ptr(), 0, dt, _stream_int(x.device))
+    if rc:
+        _check(rc, "antq_quant_i8_nhwc")
+    return out.view(B, H, W, C)
 
 
 def _int_linear_args(codes, xq, alpha_w, image_w, alpha_x, N, K, per_row, dtype, bias, out, width=4):

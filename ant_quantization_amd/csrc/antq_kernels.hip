@@ -529,6 +529,33 @@ extern "C" int antq_quant_i8(const void *x, int8_t *q, size_t rows, size_t row_l
     });
 }
 
+// antq_quant_i8 of a contiguous NCHW activation, written in NHWC order (antq_k_quant_nhwc.h): the input of antq_conv2d4_i8
+// without the channels-last copy in front.  The checks in the order include/antq.h states, all before any HIP call.
+#include "antq_k_quant_nhwc.h"
+
+extern "C" int antq_quant_i8_nhwc(const void *x, int8_t *q, size_t B, size_t C, size_t P, const float *alpha, float gmax,
+                                  const void *plan_host, const void *plan_dev, const int8_t *image, unsigned flags, int dtype,
+                                  void *stream)
+{
+    if (!x || !q || !alpha || !plan_host || !plan_dev || !image) return ANTQ_ERR_ARG;
+    if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
+    if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_ARG;
+    if (B == 0 || C == 0 || P == 0) return ANTQ_OK;
+    if (flags & ANTQ_FLAG_OVP) return ANTQ_ERR_UNSUPPORTED;
+    if (C % 16 != 0) return ANTQ_ERR_UNSUPPORTED;
+    const size_t lim = ANTQ_QUANT_I8_NHWC_MAX_BYTES;
+    if (C > lim || P > lim / C || B > lim / (C * P)) return ANTQ_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(x) % (dtype == ANTQ_F32 ? 4 : 2) || reinterpret_cast<uintptr_t>(q) % 16 ||
+        reinterpret_cast<uintptr_t>(alpha) % 4)
+        return ANTQ_ERR_ALIGN;
+    PlanArgs pa;
+    if (!plan_args_from_host(plan_host, pa)) return ANTQ_ERR_PLAN;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return with_dtype(dtype, [&](auto tag) {
+        return launch_quant_i8_nhwc<decltype(tag)>(x, q, B, C, P, alpha, gmax, pa, plan_host, plan_dev, image, st);
+    });
+}
+
 // ======================================================================================
 // ANT `outlier` mode (AQ:417-465): fused forward, exact order statistics of |x| (antq_k_outlier.h)
 // ======================================================================================

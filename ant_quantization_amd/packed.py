@@ -170,6 +170,14 @@ count in `.int_conv_calls`).  The sum is an exact integer, so the bits are those
 and time, never a result.  The partial sums go through the bank's one workspace per device, the one `integer_split_k` uses.  A
 flag, not a rows option.  Larger outputs run `antq_conv2d4_i8` as before; with the flag off every launch and every bit is
 today's, in banks that set `integer_split_k` too.  Measurements: profiles/int_conv4_sk.md, DESIGN.md 5u.
+
+`integer_conv_nchw=True` (needs fused_linear, integer_linear and integer_conv) quantises a served conv call's input that is
+`is_contiguous()` but not channels-last -- plain NCHW memory, element alignment suffices -- with `antq_quant_i8_nhwc`, which reads
+along H W and writes the int8 NHWC image in one launch (`.int_conv_nchw_calls`; no `.int_conv_relayouts`).  The bytes are those of
+the copy + `antq_quant_i8`, so nothing downstream changes, the split-K routing included.  Any other stride pattern keeps the copy,
+and so does the one class the copy measured as fast or faster for: bfloat16 / float16 inputs of fewer than 2^16 elements with
+H W % 8 != 0;
+channels-last inputs keep `antq_quant_i8`; with the flag off every launch and every bit is today's.  DESIGN.md 5v.
 """
 from collections import namedtuple
 
@@ -203,6 +211,7 @@ _OPTIONS = (
     _Option("integer_bytes", False, ("fused_linear", "fused_bytes", "integer_linear"), None),
     _Option("integer_conv", False, ("fused_linear", "integer_linear"), None),
     _Option("integer_conv_split_k", False, ("fused_linear", "integer_linear", "integer_conv"), None),
+    _Option("integer_conv_nchw", False, ("fused_linear", "integer_linear", "integer_conv"), None),
 )
 _NOTES = {("PackedBank", "keep_images"): " (nothing else computes from the codes)"}
 
@@ -268,7 +277,8 @@ class PackedBank:
     def __init__(self, model, release_weights=False, codes=None, fused_linear=False, keep_images=True, fused_rows=None,
                  byte_codes=False, fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None,
                  fused_conv1d=False, fused_conv1d_mm=False, fused_conv1d_gemm=False, integer_linear=False,
-                 integer_split_k=False, integer_bytes=False, integer_conv=False, integer_conv_split_k=False):
+                 integer_split_k=False, integer_bytes=False, integer_conv=False, integer_conv_split_k=False,
+                 integer_conv_nchw=False):
         """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict);
         a layer's code width is then the one its stored size says (numel / 2 bytes: 4-bit, numel bytes: byte codes).
         Every other parameter: see the module docstring."""
@@ -295,6 +305,7 @@ class PackedBank:
         self.int_conv_calls = 0    # forwards antq_quant_i8 + antq_conv2d4_i8 served (integer_conv)
         self.int_conv_sk_calls = 0  # ... of them through antq_conv2d4_i8_sk (integer_conv_split_k)
         self.int_conv_relayouts = 0  # ... of them whose input was copied to channels-last memory first
+        self.int_conv_nchw_calls = 0  # ... of them whose contiguous NCHW input antq_quant_i8_nhwc quantised (integer_conv_nchw)
         self._sk_workspace = {}    # device -> the one workspace of antq_linear4_i8_sk / antq_linear8_i8_sk / antq_conv2d4_i8_sk, grown on demand
         self.launches = 0          # decode launches so far (one per (device, dtype, pair rule, code width) group and refresh)
         self.dirty = True
@@ -686,7 +697,9 @@ class PackedBank:
         nothing touched -- unless lookup() served the weight, the entry is integer-conv-fusable, the input quantiser is one
         integer_linear_call takes and its book is plain with an integer image, I_x I_w C R S < 2^31, and the input is a 4-D
         no-grad GPU tensor [B, C, H, W] of the layer's dtype on its device whose sizes the library takes.  An input that is not
-        channels-last contiguous is copied once (`.int_conv_relayouts`).  Returns [B, N, Ho, Wo] in channels-last memory."""
+        channels-last contiguous is copied once (`.int_conv_relayouts`) -- or, with integer_conv_nchw and plain contiguous NCHW
+        memory, quantised by antq_quant_i8_nhwc without a copy (`.int_conv_nchw_calls`).  Returns [B, N, Ho, Wo] in channels-last
+        memory."""
         q, qi = mod.quant_weight, mod.quant_input
         e = self.entries.get(id(q))
         if e is None or e.get("conv_codes") is None or weight is not e["out"]:
@@ -711,13 +724,22 @@ class PackedBank:
         last = input.is_contiguous(memory_format=torch.channels_last)
         if last and input.data_ptr() % 16:
             return None
-        if not last:
+        # (integer_conv_nchw) a contiguous NCHW input goes to the transposing quantiser: no copy, element alignment suffices
+        # (measured, DESIGN 5v: 16-bit rows that are no whole 16-byte vectors take element loads, and below 2^16 elements the
+        # copy is then as fast or 6 % faster: those keep it)
+        nchw = (not last and getattr(self, "integer_conv_nchw", False) and input.is_contiguous() and C % 16 == 0
+                and not (input.element_size() == 2 and (H * W) % 8 and input.numel() < 1 << 16))
+        if not last and not nchw:
             input = input.contiguous(memory_format=torch.channels_last)
             self.int_conv_relayouts += 1
         plan_w, gmax_w, _, _ = _codebook(q)
         dev = e["device"]
         self._integer_units(e, qi, plan_w, gmax_w, plan_x, gmax_x)
-        xq = _lib.quant_i8(input.permute(0, 2, 3, 1), e["alpha_x"], plan_x, gmax_x, 1, input.numel(), False, plan_x.image_dev(dev))
+        if nchw:
+            xq = _lib.quant_i8_nhwc(input, e["alpha_x"], plan_x, gmax_x, plan_x.image_dev(dev))
+            self.int_conv_nchw_calls += 1
+        else:
+            xq = _lib.quant_i8(input.permute(0, 2, 3, 1), e["alpha_x"], plan_x, gmax_x, 1, input.numel(), False, plan_x.image_dev(dev))
         self.int_conv_calls += 1
         args = (e["conv_codes"], xq, e["unit_w"], plan_w.image_dev(dev), e["integer"], e["unit_x"], image_x[0], N, (R, S), (sh, sw), (ph, pw),
                 (dh, dw), e["per_row"], e["dtype"])
@@ -832,7 +854,7 @@ def pack_model(model, release_weights=False, **options):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
     (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
     options: fused_linear, keep_images, fused_rows, byte_codes, fused_bytes, fused_byte_rows, fused_gemm_rows,
-    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes, integer_conv, integer_conv_split_k -- PackedBank's keywords with its defaults; see the module docstring."""
+    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes, integer_conv, integer_conv_split_k, integer_conv_nchw -- PackedBank's keywords with its defaults; see the module docstring."""
     return PackedBank(model, release_weights, None, **options)     # (codes: not an option here -- given, it is a TypeError)
 
 
@@ -861,7 +883,7 @@ def load_packed_state_dict(model, sd, release_weights=True, **options):
     any other size raises AntqError naming the layer), and the weights are materialised by the batched decode
     (release_weights=False: copied into the layers' own float weights instead of replacing them).
     options: fused_linear, keep_images, fused_rows, fused_bytes, fused_byte_rows, fused_gemm_rows, fused_byte_gemm_rows,
-    fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes, integer_conv, integer_conv_split_k, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
+    fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes, integer_conv, integer_conv_split_k, integer_conv_nchw, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
     _check_options("load_packed_state_dict", **options)        # (before the model is touched)
     suffix = "." + CODES_KEY
     codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}

@@ -1074,6 +1074,30 @@ int antq_conv2d4_i8_sk(const uint8_t *codes_dev /* N*R*S*C/2 bytes */, const int
                        unsigned flags /* 0 */, int dtype /* F32 | BF16 | F16: y and bias */, void *stream);
 
 /* -------------------------------------------------------------------------
+ * antq_quant_i8_nhwc: antq_quant_i8 of a CONTIGUOUS NCHW activation, written in NHWC order -- the xq operand of antq_conv2d4_i8
+ * and antq_conv2d4_i8_sk without a channels-last copy in front.  x_dev: [B, C, P] contiguous (P = H W), q_dev: int8 [B, P, C].
+ *     q[b, p, c] = the byte antq_quant_i8 writes for the element x[b, c, p] with rows = 1, the same one alpha, no pair rule
+ *                  and the same plan and image
+ * With one scale and no pair rule a byte depends on its element alone, so the order of the elements changes no bit.
+ * Refusals, in this order, all before anything touches HIP; a refused call launches and writes nothing:
+ *   ANTQ_ERR_ARG          a null pointer; a flag other than ANTQ_FLAG_OVP; a dtype other than F32 / BF16 / F16
+ *   ANTQ_OK, no launch    B == 0, C == 0 or P == 0
+ *   ANTQ_ERR_UNSUPPORTED  ANTQ_FLAG_OVP (the pair rule pairs neighbours of the NHWC order); C % 16 != 0;
+ *                         B P C > ANTQ_QUANT_I8_NHWC_MAX_BYTES (= ANTQ_CONV2D4_I8_MAX_XQ_BYTES: what the conv kernels take)
+ *   ANTQ_ERR_ALIGN        x_dev not aligned to its element; q_dev not 16-byte aligned; alpha_dev not 4-byte aligned
+ *   ANTQ_ERR_PLAN         a malformed plan (plan_host is read from here on)
+ *   ANTQ_ERR_UNSUPPORTED  the byte encoder's book refusal (antq_encode8: m > 256)
+ * 16-byte loads along P when x_dev is 16-byte aligned and P * sizeof(element) % 16 == 0, element loads otherwise: the same
+ * bits.  Nothing outside q[0 .. B P C) is written.  One launch, no workspace, no atomics, no allocation, stream-ordered,
+ * capturable.  Kernel: csrc/antq_k_quant_nhwc.h.  Measurements: profiles/quant_i8_nhwc.md.
+ * ------------------------------------------------------------------------- */
+#define ANTQ_QUANT_I8_NHWC_MAX_BYTES 0x7fffffff
+int antq_quant_i8_nhwc(const void *x_dev /* [B, C, P] contiguous, P = H W */, int8_t *q_dev /* [B, P, C] */,
+                       size_t B, size_t C, size_t P, const float *alpha_dev /* one float */, float gmax,
+                       const void *plan_host, const void *plan_dev, const int8_t *image_dev /* m bytes */,
+                       unsigned flags, int dtype /* F32 | BF16 | F16 */, void *stream);
+
+/* -------------------------------------------------------------------------
  * OliVe's clip statistic on ONE read (replaces t.mean() + t.std() of olive_quantization/antquant/quant_modules.py:193-197
  * and :213-218, which read the tensor at least three times before the clip search reads it again).
  * antq_moments: sums_dev[2 r] = sum of x, sums_dev[2 r + 1] = sum of x^2 over row r (alpha_per_row) or over the whole

@@ -14,7 +14,11 @@ Signed flint-4 weights with one scale per output channel, unsigned int-4 activat
     K   (--sk) antq_quant_i8 + antq_conv2d4_i8_sk, the input channels-last   (pack_model(integer_conv_split_k=True)); measured
         against I and A at the points whose output has at most CONV2D4_I8_SK_MAX_M rows, `--force S` with forced slices
 
+    Q0 / Q1 / Q2, IN2   (--nchw) the quantiser alone -- antq_quant_i8 on a channels-last input, today's copy + antq_quant_i8 on an
+        NCHW input, antq_quant_i8_nhwc on it -- and IN2 = Q2 + antq_conv2d4_i8 against IN and A   (pack_model(integer_conv_nchw=True))
+
     python tools/probe_int_conv4.py [--quick] [--out profiles/int_conv4]      (writes .json and .md)
+    python tools/probe_int_conv4.py --nchw [--dtype bfloat16] --out profiles/quant_i8_nhwc
     python tools/probe_int_conv4.py --sk [--force S] [--every n] [--dtype bfloat16] --out profiles/int_conv4_sk
 """
 import argparse
@@ -106,8 +110,42 @@ def write_md_sk(rows, path, args):
         f.write("\n".join(out))
 
 
+def write_md_nchw(rows, path, args):
+    """--nchw: the quantiser alone (Q0, Q1, Q2) and the whole call from an NCHW input (IN, IN2, A)"""
+    out = ["# antq_quant_i8_nhwc against the channels-last copy + antq_quant_i8, NCHW inputs", "",
+           "Written by `tools/probe_int_conv4.py --nchw`: one MI355X, one process; the protocol of profiles/int_conv4.md (per point %d "
+           "repetitions of one graph-replayed batch of calls per arm, the arms alternated inside a repetition; medians in us per call, "
+           "`spread` = the largest (max - min) / median of the point's arms).  Q0 = antq_quant_i8 on a channels-last input, Q1 = "
+           "contiguous(channels_last) + antq_quant_i8 (today's NCHW path), Q2 = antq_quant_i8_nhwc, COPY = the copy alone; IN = Q1 + "
+           "antq_conv2d4_i8, IN2 = Q2 + antq_conv2d4_i8, A = antq_fakequant + F.conv2d on the kept image, the faster input layout.  "
+           "Ratios are TIMES: below 1, the first is faster.  `won` / `lost`: by more than the point's spread.  GB/s: bytes read + "
+           "written (Q2: element + 1, COPY: 2 elements) over the time; every call of an arm reads the same input, so small inputs "
+           "come from the caches." % args.reps, ""]
+    for dt in sorted({r["dtype"] for r in rows}):
+        rs = [r for r in rows if r["dtype"] == dt]
+        out += ["## %s" % dt, "", "| ratio | points | won | lost | range |", "|---|---|---|---|---|"]
+        for k, name in (("q2_over_q1", "Q2 / Q1"), ("in2_over_in", "IN2 / IN"), ("in_over_a", "IN / A"), ("in2_over_a", "IN2 / A")):
+            out.append("| %s | %d | %d | %d | %s |" % (name, len(rs), sum(r[k] < 1 - r["spread"] for r in rs),
+                                                     sum(r[k] > 1 + r["spread"] for r in rs), _range([r[k] for r in rs])))
+        big = sorted(rs, key=lambda r: -r["B"] * r["C"] * r["H"] * r["H"])[:3]
+        out += ["", "The three largest inputs: " + "; ".join("%d x %d x %d x %d: Q2 %.0f GB/s, COPY %.0f GB/s" % (
+            r["B"], r["C"], r["H"], r["H"], r["q2_gbs"], r["copy_gbs"]) for r in big) + ".", "",
+                "| C -> N, k / stride, input | B | Q0 | Q1 | Q2 | COPY | IN | IN2 | A | Q2 / Q1 | IN2 / IN | IN2 / A | Q2 GB/s | spread |",
+                "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+        for r in rs:
+            out.append("| %d -> %d, %d / %d, %d x %d | %d | %.1f | %.1f | %.1f | %.1f | %.1f | %.1f | %.1f | %.2f | %.2f | %.2f | %.0f | %.1f %% |" % (
+                r["C"], r["N"], r["k"], r["stride"], r["H"], r["H"], r["B"], r["us_q0"], r["us_q1"], r["us_q2"], r["us_copy"], r["us_in"],
+                r["us_in2"], r["us_a"], r["q2_over_q1"], r["in2_over_in"], r["in2_over_a"], r["q2_gbs"], 100 * r["spread"]))
+        out.append("")
+    if args.notes and os.path.exists(args.notes):
+        out += [open(args.notes).read()]
+    with open(path, "w") as f:
+        f.write("\n".join(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--nchw", action="store_true", help="the quantiser arms Q0 / Q1 / Q2 and the whole call IN / IN2 / A from an NCHW input")
     ap.add_argument("--sk", action="store_true", help="the split-K arm K against I and A, at the points of at most CONV2D4_I8_SK_MAX_M rows")
     ap.add_argument("--force", type=int, default=0, help="(--sk) slices forced with antq_debug_set key 24")
     ap.add_argument("--every", type=int, default=1, help="(--sk) every n-th shape only")
@@ -126,7 +164,7 @@ def main():
         if a.out:
             with open(a.out + ".json", "w") as f:
                 json.dump(rows, f, indent=1)
-        (write_md_sk if a.sk else write_md)(rows, (a.out or os.path.splitext(a.rewrite)[0]) + ".md", a)
+        (write_md_nchw if a.nchw else write_md_sk if a.sk else write_md)(rows, (a.out or os.path.splitext(a.rewrite)[0]) + ".md", a)
         return
     if not torch.cuda.is_available():
         raise SystemExit("probe_int_conv4: no GPU -- nothing is measured without one")
@@ -199,6 +237,37 @@ def main():
                     print(json.dumps(r), flush=True)
                     del t, images, taps
                     continue
+                if a.nchw:
+                    def q1(i):
+                        src = x.contiguous(memory_format=torch.channels_last)
+                        _lib.quant_i8(src.permute(0, 2, 3, 1), ax, plan_x, gmax_x, 1, src.numel(), False, img_x, out=xq)
+
+                    def in2(i):
+                        _lib.quant_i8_nhwc(x, ax, plan_x, gmax_x, img_x, out=xq)
+                        return _lib.int_conv2d4(taps[i], xq, unit_w, img_w, I_w, unit_x, I_x, N, k, stride, pad, 1, True, dt, bias=bias, out=y)
+
+                    t = alternate({"Q0": capture(lambda i: _lib.quant_i8(x_cl.permute(0, 2, 3, 1), ax, plan_x, gmax_x, 1, x.numel(), False,
+                                                                         img_x, out=xq), n_buf, iters, 3),
+                                   "Q1": capture(q1, n_buf, iters, 3),
+                                   "Q2": capture(lambda i: _lib.quant_i8_nhwc(x, ax, plan_x, gmax_x, img_x, out=xq), n_buf, iters, 3),
+                                   "COPY": capture(lambda i: x.contiguous(memory_format=torch.channels_last), n_buf, iters, 3),
+                                   "IN": capture(lambda i: integer(x.contiguous(memory_format=torch.channels_last), i), n_buf, iters, 3),
+                                   "IN2": capture(in2, n_buf, iters, 3),
+                                   "A": capture(lambda i: image(x, xf, i), n_buf, iters, 3),
+                                   "ACL": capture(lambda i: image(x_cl, xf_cl, i), n_buf, iters, 3)}, iters, a.reps)
+                    us = {key: v[0] for key, v in t.items()}
+                    us_a, n = min(us["A"], us["ACL"]), x.numel()
+                    r = dict(dtype=str(dt).split(".")[1], C=C, N=N, k=k, stride=stride, H=H, B=B, M=M, K=K, calls=iters,
+                             us_q0=round(us["Q0"], 2), us_q1=round(us["Q1"], 2), us_q2=round(us["Q2"], 2), us_copy=round(us["COPY"], 2),
+                             us_in=round(us["IN"], 2), us_in2=round(us["IN2"], 2), us_a=round(us_a, 2),
+                             q2_over_q1=round(us["Q2"] / us["Q1"], 3), in2_over_in=round(us["IN2"] / us["IN"], 3),
+                             in_over_a=round(us["IN"] / us_a, 3), in2_over_a=round(us["IN2"] / us_a, 3),
+                             q2_gbs=round(n * (esz + 1) / us["Q2"] / 1e3, 1), copy_gbs=round(n * 2 * esz / us["COPY"] / 1e3, 1),
+                             spread=round(max(v[1] for v in t.values()), 4))
+                    rows.append(r)
+                    print(json.dumps(r), flush=True)
+                    del t, images, taps
+                    continue
                 graphs = {"I": capture(lambda i: integer(x_cl, i), n_buf, iters, 3),
                           "IN": capture(lambda i: integer(x.contiguous(memory_format=torch.channels_last), i), n_buf, iters, 3),
                           "A": capture(lambda i: image(x, xf, i), n_buf, iters, 3),
@@ -219,7 +288,7 @@ def main():
                 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
                 with open(a.out + ".json", "w") as f:
                     json.dump(rows, f, indent=1)
-                (write_md_sk if a.sk else write_md)(rows, a.out + ".md", a)
+                (write_md_nchw if a.nchw else write_md_sk if a.sk else write_md)(rows, a.out + ".md", a)
 
 
 if __name__ == "__main__":
