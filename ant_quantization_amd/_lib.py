@@ -42,6 +42,7 @@ CONV2D4_I8_MAX_XQ_BYTES = 0x7fffffff  # include/antq.h ANTQ_CONV2D4_I8_MAX_XQ_BY
 QUANT_I8_NHWC_MAX_BYTES = 0x7fffffff  # include/antq.h ANTQ_QUANT_I8_NHWC_MAX_BYTES: bytes quant_i8_nhwc writes
 CONV2D4_I8_SK_MAX_M = 1024  # include/antq.h ANTQ_CONV2D4_I8_SK_MAX_M: output positions B * Ho * Wo antq_conv2d4_i8_sk takes
 LINEAR8_I8_SK_MAX_M = 64  # include/antq.h ANTQ_LINEAR8_I8_SK_MAX_M: rows of xq antq_linear8_i8_sk takes
+CONV2D8_I8_SK_MAX_M = 1024  # include/antq.h ANTQ_CONV2D8_I8_SK_MAX_M: output positions B * Ho * Wo antq_conv2d8_i8_sk takes
 PLAN_MAX_BYTES = 128 + 4 * MAX_GRID + 16 * 3072 + 20 * 1024 + 16 * 64
 
 _DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16, torch.float64: F64}
@@ -83,7 +84,8 @@ def lib():
                              "antq_linear8_gemm", "antq_linear4_t", "antq_linear4_t_mm", "antq_linear4_t_gemm", "antq_fakequant_outlier",
                              "antq_abs_order_stats", "antq_quant_i8", "antq_linear4_i8", "antq_linear4_i8_sk",
                              "antq_linear4_i8_sk_slices", "antq_linear8_i8", "antq_linear8_i8_sk", "antq_linear8_i8_sk_slices",
-                             "antq_conv2d4_i8", "antq_conv2d4_i8_sk", "antq_conv2d4_i8_sk_slices", "antq_quant_i8_nhwc"):
+                             "antq_conv2d4_i8", "antq_conv2d4_i8_sk", "antq_conv2d4_i8_sk_slices", "antq_quant_i8_nhwc",
+                             "antq_conv2d8_i8", "antq_conv2d8_i8_sk", "antq_conv2d8_i8_sk_slices"):
                     getattr(L, name).restype = ctypes.c_int
                 L.antq_batch_capacity.restype = ctypes.c_size_t
                 L.antq_decode4_batch_capacity.restype = ctypes.c_size_t
@@ -95,6 +97,7 @@ def lib():
                 L.antq_linear4_i8_sk_workspace_bytes.restype = ctypes.c_size_t
                 L.antq_linear8_i8_sk_workspace_bytes.restype = ctypes.c_size_t
                 L.antq_conv2d4_i8_sk_workspace_bytes.restype = ctypes.c_size_t
+                L.antq_conv2d8_i8_sk_workspace_bytes.restype = ctypes.c_size_t
                 # declared signatures: plain python ints go straight through (no per-call wrapper objects)
                 vp, sz, ci, cf, cu = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_float, ctypes.c_uint
                 L.antq_fakequant.argtypes = [vp, vp, vp, sz, sz, vp, ci, cf, vp, vp, cu, ci, vp]
@@ -132,6 +135,11 @@ def lib():
                 L.antq_conv2d4_i8_sk_workspace_bytes.argtypes = [sz, sz, sz]
                 L.antq_conv2d4_i8_sk_slices.argtypes = [sz, sz, sz, ci]
                 L.antq_quant_i8_nhwc.argtypes = [vp, vp, sz, sz, sz, vp, cf, vp, vp, vp, cu, ci, vp]
+                L.antq_conv2d8_i8.argtypes = ([vp, vp, vp, vp, sz, sz, sz, sz, sz, ci, ci, ci, ci, ci, ci, ci, ci, vp, ci, ci, vp, vp, ci, vp, ci,
+                                               ci, vp, cu, ci, vp])
+                L.antq_conv2d8_i8_sk.argtypes = L.antq_conv2d8_i8.argtypes[:27] + [vp, sz] + L.antq_conv2d8_i8.argtypes[27:]
+                L.antq_conv2d8_i8_sk_workspace_bytes.argtypes = [sz, sz, sz]
+                L.antq_conv2d8_i8_sk_slices.argtypes = [sz, sz, sz, ci]
                 # development: ANTQ_DEBUG_KNOBS="14=2,0=8" applies antq_debug_set(key, value) pairs to the loading thread
                 # (the knobs are thread-local; tools/fuzz_campaign.sh forces code paths with it)
                 for kv in [k for k in os.environ.get("ANTQ_DEBUG_KNOBS", "").split(",") if "=" in k]:
@@ -366,14 +374,23 @@ class Plan:
             self._image8 = grids.integer_image(self.grid, limit=128)
         return self._image8
 
+    def offset_image(self):
+        """(I, int8 numpy array of value - 128) of this grid when it is unsigned with integer values 0 .. I, I <= 255
+        (grids.offset_image: what int_conv2d8 takes with x_offset=128), else None; found once."""
+        if not hasattr(self, "_image_off"):
+            from . import grids
+            self._image_off = grids.offset_image(self.grid)
+        return self._image_off
+
     def image_dev(self, device, limit=127):
         """The integer image's m bytes (int8) on `device`, next to grid_dev; the grid must have one.  limit=128: the image of
-        integer_image8, under a key of its own."""
-        wide = limit == 128
-        key = ("image8" if wide else "image", device.index if device.index is not None else torch.cuda.current_device())
+        integer_image8, limit="offset": the one of offset_image, each under a key of its own."""
+        name, get = {127: ("image", self.integer_image), 128: ("image8", self.integer_image8),
+                     "offset": ("image_off", self.offset_image)}[limit if limit in (128, "offset") else 127]
+        key = (name, device.index if device.index is not None else torch.cuda.current_device())
         t = self._dev.get(key)
         if t is None:
-            t = self._dev[key] = torch.from_numpy((self.integer_image8() if wide else self.integer_image())[1]).to(device)
+            t = self._dev[key] = torch.from_numpy(get()[1]).to(device)
         return t
 
     def eval_host(self, d):
@@ -1340,8 +1357,8 @@ def _pair(v):
     return int(a), int(b)
 
 
-def _int_conv_args(codes, xq, alpha_w, image_w, alpha_x, N, kernel_size, stride, padding, dilation, per_row, dtype, bias, out):
-    """What int_conv2d4 and int_conv2d4_sk check alike.  Returns (dtype code, the geometry as antq_conv2d4_i8 takes it -- B, H,
+def _int_conv_args(codes, xq, alpha_w, image_w, alpha_x, N, kernel_size, stride, padding, dilation, per_row, dtype, bias, out, width=4):
+    """What int_conv2d4, int_conv2d4_sk, int_conv2d8 and int_conv2d8_sk check alike (width: bits per code).  Returns (dtype code, the geometry as antq_conv2d4_i8 takes it -- B, H,
     W, C, N, R, S, sh, sw, ph, pw, dh, dw --, M = B Ho Wo, out)."""
     for t, name in ((codes, "codes"), (xq, "xq"), (alpha_w, "alpha_w"), (image_w, "image_w"), (alpha_x, "alpha_x")):
         _require_gpu(t, name)
@@ -1352,8 +1369,8 @@ def _int_conv_args(codes, xq, alpha_w, image_w, alpha_x, N, kernel_size, stride,
         raise AntqError("xq must be a contiguous int8 tensor [B, H, W, C]")
     (R, S), (sh, sw), (ph, pw), (dh, dw) = _pair(kernel_size), _pair(stride), _pair(padding), _pair(dilation)
     B, H, W, C = xq.shape
-    if codes.dtype != torch.uint8 or codes.numel() * 2 != N * R * S * C:
-        raise AntqError("codes must be uint8 of N*R*S*C/2 bytes")
+    if codes.dtype != torch.uint8 or codes.numel() * 8 != N * R * S * C * width:
+        raise AntqError("codes must be uint8 of N*R*S*C%s bytes" % ("/2" if width == 4 else ""))
     if (alpha_w.dtype != torch.float32 or alpha_w.numel() < (N if per_row else 1) or alpha_x.dtype != torch.float32 or alpha_x.numel() < 1
             or image_w.dtype != torch.int8):
         raise AntqError("alpha_w must be float32, one per row (per_row) or one; alpha_x one float32; image_w int8")
@@ -1363,7 +1380,7 @@ def _int_conv_args(codes, xq, alpha_w, image_w, alpha_x, N, kernel_size, stride,
             raise AntqError("bias must hold N elements of `dtype`")
     for t in (codes, alpha_w, image_w, alpha_x, bias, out):
         if t is not None and t.device != xq.device:
-            raise AntqError("every tensor of int_conv2d4 must live on one device")
+            raise AntqError("every tensor of int_conv2d%d must live on one device" % width)
     # (sizes the library refuses -- an empty output among them -- give an empty `out` here and its code there)
     Ho = max((H + 2 * ph - dh * (R - 1) - 1) // sh + 1, 0) if sh >= 1 else 0
     Wo = max((W + 2 * pw - dw * (S - 1) - 1) // sw + 1, 0) if sw >= 1 else 0
@@ -1504,6 +1521,75 @@ def int_linear8_sk(codes, xq, alpha_w, image_w, image_host, I_w, alpha_x, I_x, N
                                       _stream_int(xq.device))
     if rc:
         _check(rc, "antq_linear8_i8_sk")
+    return out
+
+
+def _wsum_arg(x_offset, wsum, xq, N):
+    """the wsum argument of int_conv2d8 / int_conv2d8_sk as a pointer: required with x_offset=128, an int32 tensor of N sums"""
+    if x_offset == 128 and wsum is None:
+        raise AntqError("x_offset=128 needs wsum, the int32 sums of the weight's image per output channel")
+    if wsum is None:
+        return None
+    _require_gpu(wsum, "wsum")
+    if wsum.dtype != torch.int32 or wsum.numel() != N or wsum.device != xq.device or not wsum.is_contiguous():
+        raise AntqError("wsum must be a contiguous int32 tensor of N sums on xq's device")
+    return wsum.data_ptr()
+
+
+def int_conv2d8(codes, xq, alpha_w, image_w, image_host, I_w, alpha_x, I_x, N, kernel_size, stride, padding, dilation, per_row, dtype,
+                bias=None, out=None, x_offset=0, wsum=None):
+    """int_conv2d4's conv2d from BYTE codes (antq_conv2d8_i8): codes uint8 [N][R][S][C], one byte per weight (PackedBank's
+    `conv_codes` of a byte-coded entry), V = image_w[code] (a code past the image reads 0), plain books, C % 32 == 0.  image_w,
+    image_host: as int_linear8.  x_offset=0: xq holds the values of a signed image, I_x in 1 .. 128.  x_offset=128: xq holds
+    value - 128 of an unsigned image 0 .. I_x, I_x <= 255 -- quant_i8 with Plan.image_dev(device, "offset") -- and wsum, int32
+    [N], holds sum_k V[n, k] (PackedBank's `wsum`): taps outside the image still contribute 0.  Everything else as int_conv2d4."""
+    dt, geom, _, out = _int_conv_args(codes, xq, alpha_w, image_w, alpha_x, N, kernel_size, stride, padding, dilation, per_row, dtype, bias,
+                                      out, width=8)
+    h = _image_host(image_host, image_w)
+    ws = _wsum_arg(x_offset, wsum, xq, N)
+    with _on_device(xq.device):
+        rc = lib().antq_conv2d8_i8(codes.data_ptr(), xq.data_ptr(), _ptr(bias), out.data_ptr(), *geom, alpha_w.data_ptr(),
+                                   1 if per_row else 0, I_w, h.ctypes.data, image_w.data_ptr(), h.size, alpha_x.data_ptr(), I_x, x_offset, ws,
+                                   0, dt, _stream_int(xq.device))
+    if rc:
+        _check(rc, "antq_conv2d8_i8")
+    return out
+
+
+def int_conv2d8_sk_workspace_bytes(M, N, K, device=None):
+    """int_conv2d4_sk_workspace_bytes for int_conv2d8_sk (antq_conv2d8_i8_sk_workspace_bytes)."""
+    if device is None:
+        return int(lib().antq_conv2d8_i8_sk_workspace_bytes(M, N, K))
+    with _on_device(device):
+        return int(lib().antq_conv2d8_i8_sk_workspace_bytes(M, N, K))
+
+
+def int_conv2d8_sk_slices(M, N, K, cus=0):
+    """The slices int_conv2d8_sk would cut K into now (antq_conv2d8_i8_sk_slices); cus >= 1: on a part of that many compute units."""
+    return int(lib().antq_conv2d8_i8_sk_slices(M, N, K, cus))
+
+
+def int_conv2d8_sk(codes, xq, alpha_w, image_w, image_host, I_w, alpha_x, I_x, N, kernel_size, stride, padding, dilation, per_row, dtype,
+                   bias=None, out=None, workspace=None, x_offset=0, wsum=None):
+    """int_conv2d8 for outputs of at most CONV2D8_I8_SK_MAX_M rows (B Ho Wo) with K = R S C split across workgroups
+    (antq_conv2d8_i8_sk): the same arguments, the same bits.  workspace: as for int_conv2d4_sk, of
+    int_conv2d8_sk_workspace_bytes(B Ho Wo, N, R S C) bytes; None allocates one of that size."""
+    dt, geom, M, out = _int_conv_args(codes, xq, alpha_w, image_w, alpha_x, N, kernel_size, stride, padding, dilation, per_row, dtype, bias,
+                                      out, width=8)
+    h = _image_host(image_host, image_w)
+    ws = _wsum_arg(x_offset, wsum, xq, N)
+    if workspace is None:
+        workspace = torch.empty(int_conv2d8_sk_workspace_bytes(M, N, geom[3] * geom[5] * geom[6], xq.device), dtype=torch.uint8,
+                                device=xq.device)
+    elif not (workspace.is_cuda and workspace.device == xq.device and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise AntqError("workspace must be a contiguous uint8 tensor on xq's device")
+    with _on_device(xq.device):
+        rc = lib().antq_conv2d8_i8_sk(codes.data_ptr(), xq.data_ptr(), _ptr(bias), out.data_ptr(), *geom, alpha_w.data_ptr(),
+                                      1 if per_row else 0, I_w, h.ctypes.data, image_w.data_ptr(), h.size, alpha_x.data_ptr(), I_x, x_offset,
+                                      ws, workspace.data_ptr() if workspace.numel() else None, workspace.numel(), 0, dt,
+                                      _stream_int(xq.device))
+    if rc:
+        _check(rc, "antq_conv2d8_i8_sk")
     return out
 
 

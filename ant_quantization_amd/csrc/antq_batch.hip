@@ -17,6 +17,7 @@
 #include "antq_k_linear8_i8.h"
 #include "antq_k_conv_i8.h"
 #include "antq_k_conv_i8_sk.h"
+#include "antq_k_conv8_i8.h"
 
 #include <atomic>
 #include <type_traits>
@@ -797,18 +798,22 @@ extern "C" int antq_linear4_i8(const uint8_t *codes, const int8_t *xq, const voi
 
 // The checks antq_conv2d4_i8 and antq_conv2d4_i8_sk share, in the order include/antq.h states (kLinearGo: launch, with the
 // call's M = B Ho Wo, K = R S C and geometry); the limits are what the kernels' 32-bit offsets and packed 16-bit row origins
-// need.  Nothing here touches HIP.
+// need.  Nothing here touches HIP.  bytes: the byte-code entries' differences (antq_conv2d8_i8, antq_conv2d8_i8_sk) -- the host
+// copy of the image required, m <= 256, I up to 128, and x_offset / wsum with their own argument, range, sum and alignment rules;
+// the 4-bit entries pass false, image_w itself, 0 and nullptr, and nothing changes for them.
 static int conv_i8_checks(const uint8_t *codes, const int8_t *xq, const void *bias, void *y, size_t B, size_t H, size_t W, size_t C, size_t N,
                           int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, const float *alpha_w,
                           int I_w, const int8_t *image_w, int m, const float *alpha_x, int I_x, unsigned flags, int dtype, size_t &M,
-                          size_t &K, ConvGeom &g)
+                          size_t &K, ConvGeom &g, bool bytes = false, const int8_t *image_w_host = nullptr, int x_offset = 0,
+                          const int32_t *wsum = nullptr)
 {
     if (!codes || !xq || !y || !alpha_w || !image_w || !alpha_x || m < 1) return ANTQ_ERR_ARG;
+    if (bytes && (!image_w_host || (x_offset != 0 && x_offset != 128) || (x_offset == 128 && !wsum))) return ANTQ_ERR_ARG;
     if (dtype != ANTQ_F32 && dtype != ANTQ_BF16 && dtype != ANTQ_F16) return ANTQ_ERR_ARG;
     if (flags & ~ANTQ_FLAG_OVP) return ANTQ_ERR_ARG;
     if (B == 0 || N == 0) return ANTQ_OK;
     constexpr long long D = ANTQ_CONV2D4_I8_MAX_DIM;
-    if ((flags & ANTQ_FLAG_OVP) || !dec4_book_ok(m, 0, false)) return ANTQ_ERR_UNSUPPORTED;
+    if ((flags & ANTQ_FLAG_OVP) || (bytes ? m > 256 : !dec4_book_ok(m, 0, false))) return ANTQ_ERR_UNSUPPORTED;
     if (C == 0 || C % 32 != 0 || H < 1 || W < 1 || R < 1 || S < 1 || stride_h < 1 || stride_w < 1 || dil_h < 1 || dil_w < 1 || pad_h < 0 ||
         pad_w < 0)
         return ANTQ_ERR_UNSUPPORTED;
@@ -822,11 +827,14 @@ static int conv_i8_checks(const uint8_t *codes, const int8_t *xq, const void *bi
     M = B * Ho * Wo;
     K = (size_t)R * (size_t)S * C;
     if (M > ANTQ_CONV2D4_I8_MAX_M || B * H * W > ANTQ_CONV2D4_I8_MAX_XQ_BYTES / C) return ANTQ_ERR_UNSUPPORTED;
-    if (I_x < 1 || I_x > 127 || I_w < 1 || I_w > 127) return ANTQ_ERR_UNSUPPORTED;
-    if ((uint64_t)I_x * (uint64_t)I_w * (uint64_t)K >= (1ull << 31)) return ANTQ_ERR_UNSUPPORTED;      // (the sum could leave int32)
+    // (bytes: I up to 128, the offset image 0 .. I_x up to 255; its sum bound is on |S'| + |128 wsum| <= 256 I_w K)
+    const int max_w = bytes ? 128 : 127, max_x = x_offset == 128 ? 255 : max_w;
+    if (I_x < 1 || I_x > max_x || I_w < 1 || I_w > max_w) return ANTQ_ERR_UNSUPPORTED;
+    if ((uint64_t)(x_offset == 128 ? 256 : I_x) * (uint64_t)I_w * (uint64_t)K >= (1ull << 31)) return ANTQ_ERR_UNSUPPORTED;      // (the sum could leave int32)
     const uintptr_t esz = dtype == ANTQ_F32 ? 4 : 2;
     if (reinterpret_cast<uintptr_t>(xq) % 16 || reinterpret_cast<uintptr_t>(codes) % 16 || reinterpret_cast<uintptr_t>(y) % esz ||
-        reinterpret_cast<uintptr_t>(bias) % esz || reinterpret_cast<uintptr_t>(alpha_w) % 4 || reinterpret_cast<uintptr_t>(alpha_x) % 4)
+        reinterpret_cast<uintptr_t>(bias) % esz || reinterpret_cast<uintptr_t>(alpha_w) % 4 || reinterpret_cast<uintptr_t>(alpha_x) % 4 ||
+        reinterpret_cast<uintptr_t>(wsum) % 4)
         return ANTQ_ERR_ALIGN;
     g = ConvGeom{(uint32_t)H, (uint32_t)W, (uint32_t)C, (uint32_t)R, (uint32_t)S, (uint32_t)Wo, (uint32_t)(Ho * Wo),
                  (uint32_t)stride_h, (uint32_t)stride_w, (uint32_t)dil_h, (uint32_t)dil_w, pad_h, pad_w};
@@ -1088,8 +1096,105 @@ extern "C" int antq_linear8_i8_sk(const uint8_t *codes, const int8_t *xq, const 
     });
 }
 
+// The integer-domain conv2d from BYTE codes (antq_k_conv8_i8.h): antq_conv2d4_i8's implicit GEMM with antq_linear8_i8's B side
+// and decode kinds.  x_offset 128: xq holds value - 128 of an unsigned image, the kernels fill what does not count with 0x80
+// and add 128 wsum[n] as an integer.  Every check comes before anything touches HIP; tile shape and knob 23 as there.
+extern "C" int antq_conv2d8_i8(const uint8_t *codes, const int8_t *xq, const void *bias, void *y, size_t B, size_t H, size_t W, size_t C,
+                               size_t N, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                               const float *alpha_w, int per_row, int I_w, const int8_t *image_w_host, const int8_t *image_w, int m,
+                               const float *alpha_x, int I_x, int x_offset, const int32_t *wsum, unsigned flags, int dtype, void *stream)
+{
+    size_t M, K;
+    ConvGeom g;
+    const int rc = conv_i8_checks(codes, xq, bias, y, B, H, W, C, N, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, alpha_w, I_w,
+                                  image_w, m, alpha_x, I_x, flags, dtype, M, K, g, true, image_w_host, x_offset, wsum);
+    if (rc != kLinearGo) return rc;
+    const bool table = !i8b_image_is_xor(image_w_host, m);
+    const int32_t *ws = x_offset == 128 ? wsum : nullptr;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int waves, mt;
+    i8_shape(M, N, one_of<2, 4>(g_knob_gemm_tile, 0), waves, mt);
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return with_bool(table, [&](auto tb) {
+            return with_value<2, 4>(waves, [&](auto wv) {
+                return with_value<4, 2>(mt, [&](auto mm) {
+                    constexpr int WAVES = decltype(wv)::value, MT = decltype(mm)::value;
+                    if constexpr (WAVES == 4 && MT == 2) return (int)ANTQ_ERR_UNSUPPORTED;      // (no such shape: i8_shape)
+                    else {
+                        constexpr size_t BM = (size_t)16 * MT * WAVES;
+                        const dim3 blocks((unsigned)((N + kGemmBN - 1) / kGemmBN), (unsigned)((M + BM - 1) / BM));
+                        launch_k(false, k_conv2d8_i8<T, decltype(tb)::value, WAVES, MT>, blocks, dim3(64u * WAVES), 0, st, codes, xq, bias,
+                                 y, (uint32_t)M, (uint32_t)N, (uint32_t)K, g, alpha_w, per_row ? 1 : 0, I_w, image_w, (uint32_t)m, alpha_x, I_x,
+                                 conv8_fill(x_offset), ws);
+                        return launch_status();
+                    }
+                });
+            });
+        });
+    });
+}
+
+// The slices antq_conv2d8_i8_sk would cut K = R S C into now for M = B Ho Wo output rows: i8b_sk_slices, whose tiles count the
+// ceil(M / 64) row tiles (antq_debug_set key 24 forces it); cus < 1: the device's.
+extern "C" int antq_conv2d8_i8_sk_slices(size_t M, size_t N, size_t K, int cus)
+{
+    if (M == 0 || N == 0 || K == 0) return 0;
+    size_t per_slice;
+    return i8b_sk_slices(M, N, K, cus >= 1 ? cus : i8_sk_cus(), g_knob_i8_split, per_slice);
+}
+
+extern "C" size_t antq_conv2d8_i8_sk_workspace_bytes(size_t M, size_t N, size_t K)
+{
+    const int S = antq_conv2d8_i8_sk_slices(M, N, K, 0);
+    return S <= 1 ? 0 : (((size_t)S * M * N * sizeof(int) + 15) & ~(size_t)15);
+}
+
+// antq_conv2d8_i8 for outputs of 1 .. ANTQ_CONV2D8_I8_SK_MAX_M rows with K split across workgroups (antq_k_conv8_i8.h): the
+// same checks in the same order, then antq_conv2d4_i8_sk's three: the row limit (and the finish's grid), the workspace's
+// alignment and -- the one check that asks the device -- the workspace's size.
+extern "C" int antq_conv2d8_i8_sk(const uint8_t *codes, const int8_t *xq, const void *bias, void *y, size_t B, size_t H, size_t W, size_t C,
+                                  size_t N, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                                  const float *alpha_w, int per_row, int I_w, const int8_t *image_w_host, const int8_t *image_w, int m,
+                                  const float *alpha_x, int I_x, int x_offset, const int32_t *wsum, void *workspace, size_t workspace_bytes,
+                                  unsigned flags, int dtype, void *stream)
+{
+    size_t M, K;
+    ConvGeom g;
+    const int rc = conv_i8_checks(codes, xq, bias, y, B, H, W, C, N, R, S, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, alpha_w, I_w,
+                                  image_w, m, alpha_x, I_x, flags, dtype, M, K, g, true, image_w_host, x_offset, wsum);
+    if (rc != kLinearGo) return rc;
+    // (M N / 256 workgroups of k_i8_sk_finish in one grid dimension)
+    if (M > ANTQ_CONV2D8_I8_SK_MAX_M || M * N > 0x7fffffffull * 256) return ANTQ_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(workspace) % 16) return ANTQ_ERR_ALIGN;
+    const bool table = !i8b_image_is_xor(image_w_host, m);
+    const int32_t *ws = x_offset == 128 ? wsum : nullptr;
+    size_t per_slice;
+    const int slices = i8b_sk_slices(M, N, K, i8_sk_cus(), g_knob_i8_split, per_slice);
+    if (slices > 1 && (!workspace || workspace_bytes < (size_t)slices * M * N * sizeof(int))) return ANTQ_ERR_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 blocks((unsigned)((N + kGemmBN - 1) / kGemmBN), (unsigned)slices, (unsigned)((M + kConvSkBM - 1) / kConvSkBM));
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return with_bool(table, [&](auto tb) {
+            return with_value<1, 2, 4>(M <= 16 ? 1 : M <= 32 ? 2 : 4, [&](auto mm) {
+                return with_bool(slices == 1, [&](auto direct) {
+                    launch_k(false, k_conv2d8_i8_sk<T, decltype(tb)::value, decltype(mm)::value, decltype(direct)::value>, blocks, dim3(256),
+                             0, st, codes, xq, bias, y, static_cast<int *>(workspace), (uint32_t)M, (uint32_t)N, (uint32_t)K, g, alpha_w,
+                             per_row ? 1 : 0, I_w, image_w, (uint32_t)m, alpha_x, I_x, (uint32_t)per_slice, conv8_fill(x_offset), ws);
+                    if constexpr (!decltype(direct)::value)
+                        launch_k(false, k_i8_sk_finish<T>, dim3((unsigned)((M * N + 255) / 256)), dim3(256), 0, st,
+                                 static_cast<const int *>(workspace), bias, y, (uint32_t)M, (uint32_t)N, (uint32_t)slices, alpha_w,
+                                 per_row ? 1 : 0, I_w, alpha_x, I_x);
+                    return launch_status();
+                });
+            });
+        });
+    });
+}
+
 namespace antq {
-int prefetch_unit_batch()        // antq_prefetch_kernels (antq_kernels.hip): load this unit's code object now
+int prefetch_unit_batch()       // antq_prefetch_kernels (antq_kernels.hip): load this unit's code object now
 {
     hipFuncAttributes at;
     return hipFuncGetAttributes(&at, reinterpret_cast<const void *>(&k_fq_hbatch<bf16_tag, false>)) == hipSuccess ? ANTQ_OK : ANTQ_ERR_LAUNCH;

@@ -44,10 +44,13 @@ struct ConvGeom {
 };
 
 // XL: the pieces a thread stages per stage, RSTEP: the rows between them (k_conv2d_i8: I8Tile's; antq_k_conv_i8_sk.h: 1 or 2
-// pieces, 32 rows apart).
-template <int XL, int RSTEP>
+// pieces, 32 rows apart).  FILL: a piece that does not count becomes four copies of the word `fill` instead of zeros
+// (antq_k_conv8_i8.h: 0x80808080 for an image stored as value - 128); without it the member is never set or read.
+template <int XL, int RSTEP, bool FILL = false>
 struct I8ConvX {
+    static constexpr bool kFill = FILL;
     ConvGeom g;
+    uint32_t fill;                         // (FILL) the word of a piece that does not count
     uint32_t origin[XL];                   // byte offset of xq[b, hi0, wi0, 0] (mod 2^32)
     uint32_t hw0[XL];                      // hi0 in the low, wi0 in the high 16 bits (int16 each)
     uint32_t r, s, c0;                     // the tap and channel of k = 128 stage + 16 p
@@ -98,7 +101,7 @@ struct I8ConvX {
             const uint32_t off = ok ? origin[i] + tap : c0;
             u32x4_t v = *(const ANTQ_GLOBAL u32x4_t *)(reinterpret_cast<const char *>(xq) + off);
             if constexpr (KEEP) xkeep[i] = ok ? 0xffffffffu : 0u;
-            else if (!ok) v = u32x4_t{0u, 0u, 0u, 0u};
+            else if (!ok) v = FILL ? u32x4_t{fill, fill, fill, fill} : u32x4_t{0u, 0u, 0u, 0u};
             xn[i] = v;
         }
         c0 += ac;
@@ -115,6 +118,12 @@ struct I8ConvX {
     __device__ __forceinline__ ANTQ_I8_KERNEL void load(const int8_t *__restrict__ xq, u32x4_t (&xn)[XL], uint32_t (&xkeep)[XL])
     {
         gather<true>(xq, xn, xkeep);
+    }
+    // (FILL) a KEEP-mode piece as the caller writes it to LDS: as loaded where it counts, the fill word where it does not
+    __device__ __forceinline__ ANTQ_I8_KERNEL u32x4_t masked(u32x4_t v, uint32_t keep) const
+    {
+        const uint32_t f = fill & ~keep;
+        return (v & u32x4_t{keep, keep, keep, keep}) | u32x4_t{f, f, f, f};
     }
 };
 

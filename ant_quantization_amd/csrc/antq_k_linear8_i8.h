@@ -3,6 +3,9 @@
 // antq_linear4_i8's with bytes in place of nibbles (include/antq.h): v[n, k] = image_w[code[n, k]] (a code >= m reads 0),
 // S = sum_k xq[m, k] v[n, k] an exact int32 sum on v_mfma_i32_16x16x64_i8, the scales applied once per output.  Plain books only:
 // a pair-rule byte book has no int8 image.  Part of libantq's batched translation unit (antq_batch.hip includes it); gfx950 only.
+// Everything below but the source of the A operand is shared with antq_k_conv8_i8.h: the tiled kernel's body is
+// antq_k_linear8_i8_tile.h, included inside both kernels (as an inlined function it compiled to other control flow), the
+// split-K kernel's is the function i8b_sk_tile; the two kernels here are those bodies with the matrix A side (I8Matrix).
 //
 //   decode     two kinds, chosen by the launcher from the image on the host (i8b_image_is_xor):
 //              XOR    m == 256 and image[c] == c - 128 (ANT's signed int8 book): the code IS the weight plus 128, so sixteen
@@ -67,14 +70,15 @@ static inline bool i8b_image_is_xor(const int8_t *image, int m)
 }
 
 // The slices of K of k_linear8_i8_sk: i8_sk_slices (antq_k_linear_i8.h) with the traffic cap derived again for byte codes --
-// above S = K / (8 M) the 8 S M N bytes of partial traffic exceed the N K bytes of codes.
+// above S = K / (8 Mt) the 8 S Mt N bytes of partial traffic exceed the N K bytes of codes.  Like i8_sk_slices it counts the
+// ceil(M / 64) row tiles of the conv form (antq_k_conv8_i8.h) with Mt = min(M, 64) rows each; the linear has M <= 64: one.
 static inline int i8b_sk_slices(size_t M, size_t N, size_t K, int cus, int forced, size_t &per_slice)
 {
-    const size_t tiles = (N + 63) / 64, stages = (K + 127) / 128;
+    const size_t tiles = ((N + 63) / 64) * ((M + 63) / 64), stages = (K + 127) / 128;
     size_t S = 16;
     for (size_t s = 1; s <= 16; s *= 2)
         if (tiles * s >= 2 * (size_t)std::max(cus, 1)) { S = s; break; }
-    S = std::min(S, std::max<size_t>(K / (8 * M), 1));
+    S = std::min(S, std::max<size_t>(K / (8 * std::min<size_t>(M, 64)), 1));
     if (forced >= 1) S = (size_t)std::min(forced, 16);
     S = std::max<size_t>(std::min(S, stages), 1);
     per_slice = (stages + S - 1) / S;
@@ -102,166 +106,22 @@ k_linear8_i8(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq, c
              uint32_t M, uint32_t N, uint32_t K, const float *__restrict__ alpha_w, int per_row, int I_w,
              const int8_t *__restrict__ image_w, uint32_t m, const float *__restrict__ alpha_x, int I_x)
 {
-    constexpr int NT = kGemmBN / 16;                   // a wavefront's tiles of 16 output rows
-    constexpr int WR = 16 * MT;                        // rows of xq per wavefront
-    constexpr int BM = WR * WAVES, NTH = 64 * WAVES;
-    constexpr int PIECES = kGemmBK / 16;               // 16-byte pieces of a row (of xq, of codes) per stage
-    constexpr int XL = BM * PIECES / NTH;              // pieces of xq a thread stages per stage
-    constexpr int RSTEP = NTH / PIECES;                // rows between a thread's pieces
-    constexpr int CL = kGemmBN * PIECES / NTH;         // pieces of codes a thread forwards per stage
-    constexpr uint32_t BSLOTS = 2u * NT * 64u;         // 16-byte slots of one B image
-    static_assert((WAVES == 2 || WAVES == 4) && (MT == 2 || MT == 4) && PIECES == 8 && XL == 2 * MT && kGemmBK == 64 * 2 && NT == 4 &&
-                  CL % 2 == 0, "the maps below");
-    struct Lds {
-        u32x4_t xs[BM * PIECES];                       // the staged xq: piece p of row r at [8 r + (p ^ (r & 7))]
-        u32x4_t b[2][BSLOTS];                          // the B images: fragment (j, nt), lane (col, kg) at [((4 j + nt) 4 + kg) 16 + (col ^ (4 j + kg) ^ 8 (col & 1))]
-        __attribute__((aligned(16))) uint8_t tab[256]; // (TABLE) the int8 of a code byte, zero beyond m
-    };
-    __shared__ Lds lds;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t col = lane & 15u, kg = lane >> 4;
-    const uint32_t n0 = blockIdx.x * (uint32_t)kGemmBN, m0 = blockIdx.y * (uint32_t)BM;
-    const uint32_t nstages = (K + (uint32_t)kGemmBK - 1u) / (uint32_t)kGemmBK;
-    const bool active = m0 + (uint32_t)WR * wave < M;  // (wave-uniform) this wavefront has rows of xq
-
-    // this thread's pieces of xq: piece tid & 7 of rows (tid >> 3) + RSTEP i
-    const uint32_t xp = tid & 7u, xr0 = tid >> 3;
-    u32x4_t xn[XL];
-    auto load_x = [&](uint32_t c) __attribute__((always_inline)) {
-        const uint32_t k0 = c * (uint32_t)kGemmBK + 16u * xp;
-        const bool kok = k0 < K;
-        const size_t koff = (size_t)min(k0, K - 16u);
-#pragma unroll
-        for (int i = 0; i < XL; i++) {
-            const uint32_t r = m0 + xr0 + (uint32_t)(RSTEP * i);
-            u32x4_t v = *(const ANTQ_GLOBAL u32x4_t *)(reinterpret_cast<const char *>(xq) + (size_t)min(r, M - 1u) * K + koff);
-            if (!(kok && r < M)) v = u32x4_t{0u, 0u, 0u, 0u};
-            xn[i] = v;
-        }
-    };
-    auto write_x = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < XL; i++) {
-            const uint32_t r = xr0 + (uint32_t)(RSTEP * i);
-            lds.xs[r * PIECES + (xp ^ (r & 7u))] = xn[i];
-        }
-    };
-    // this thread's pieces of codes: piece cp = tid & 7 of the tile's rows (tid >> 3) + RSTEP l (q = tid + NTH l).  Loaded
-    // from a clamped address whatever n and k; piece_ok says whether it counts.
-    const uint32_t cp = tid & 7u, cr0 = tid >> 3;
-    auto piece_ok = [&](uint32_t c, int l) __attribute__((always_inline)) {
-        return n0 + cr0 + (uint32_t)(RSTEP * l) < N && c * (uint32_t)kGemmBK + 16u * cp < K;
-    };
-    auto load_codes = [&](uint32_t c, u32x4_t (&w)[CL]) __attribute__((always_inline)) {
-        const size_t koff = (size_t)min(c * (uint32_t)kGemmBK + 16u * cp, K - 16u);
-#pragma unroll
-        for (int l = 0; l < CL; l++) {
-            const uint32_t n = min(n0 + cr0 + (uint32_t)(RSTEP * l), N - 1u);
-            w[l] = __builtin_nontemporal_load((const ANTQ_GLOBAL u32x4_t *)(reinterpret_cast<const char *>(codes) + (size_t)n * K + koff));
-        }
-    };
-
-    // __syncthreads(), spelled out: a function without this kernel's target attribute is not inlined into it
-    auto sync = [&]() __attribute__((always_inline)) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    };
-
-    u32x4_t cw[CL], cwn[CL];
-    load_x(0u);                                        // in flight while the table is built
-    load_codes(0u, cw);
-    load_codes(1u, cwn);
-    if constexpr (TABLE) {
-        for (uint32_t b = tid; b < 256u; b += (uint32_t)NTH) lds.tab[b] = b < m ? (uint8_t)image_w[b] : (uint8_t)0;
-        sync();
-    }
-
-    // piece l of this thread, stage c: its 16 codes -> one operand of 16 int8, into B image c & 1
-    auto decode_write = [&](uint32_t c, int l) __attribute__((always_inline)) {
-        const uint32_t n = cr0 + (uint32_t)(RSTEP * l), ncol = n & 15u;
-        u32x4_t v = i8b_operand<TABLE>(cw[l], lds.tab);
-        // (a piece that does not count: exact zeros, not the entry of whatever code was loaded)
-        if (!piece_ok(c, l)) v = u32x4_t{0u, 0u, 0u, 0u};
-        const uint32_t j = cp >> 2, g = cp & 3u;
-        lds.b[c & 1u][((4u * j + (n >> 4)) * 4u + g) * 16u + (ncol ^ cp ^ (8u * (ncol & 1u)))] = v;
-    };
-
-    i32x4_t acc[MT][NT];
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-        for (int nt = 0; nt < NT; nt++) acc[mt][nt] = i32x4_t{0, 0, 0, 0};
-
-    // MFMA step j of stage c: k = 128 c + 64 j + 16 kg .. + 15
-    auto mfma_step = [&](uint32_t c, int j) __attribute__((always_inline)) {
-        i32x4_t b[NT];
-        const uint32_t p = 4u * j + kg;
-#pragma unroll
-        for (int nt = 0; nt < NT; nt++)
-            b[nt] = __builtin_bit_cast(i32x4_t, lds.b[c & 1u][((4u * j + nt) * 4u + kg) * 16u + (col ^ p ^ (8u * (col & 1u)))]);
-#pragma unroll
-        for (int mt = 0; mt < MT; mt++) {
-            const i32x4_t a = __builtin_bit_cast(i32x4_t, lds.xs[((uint32_t)WR * wave + 16u * mt + col) * PIECES + (p ^ (col & 7u))]);
-#pragma unroll
-            for (int nt = 0; nt < NT; nt++) acc[mt][nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b[nt], acc[mt][nt], 0, 0, 0);
-        }
-    };
-
-    // stage 0: written and staged before the loop
-#pragma unroll
-    for (int l = 0; l < CL; l++) decode_write(0u, l);
-    write_x();
-
-    for (uint32_t c = 0; c < nstages; c++) {
-        sync();                               // xq image and B image of stage c written
-        const bool more = c + 1u < nstages;
-#pragma unroll
-        for (int l = 0; l < CL; l++) cw[l] = cwn[l];
-        if (more) {
-            load_x(c + 1u);
-            load_codes(c + 2u, cwn);
-            // the B image of stage c + 1 beside the MFMAs of stage c
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-#pragma unroll
-                for (int l = j * (CL / 2); l < (j + 1) * (CL / 2); l++) decode_write(c + 1u, l);
-                if (active) mfma_step(c, j);
-            }
-        } else if (active) {
-#pragma unroll
-            for (int j = 0; j < 2; j++) mfma_step(c, j);
-        }
-        if (!more) break;
-        sync();                               // the xq image free again
-        write_x();
-    }
-
-    // C / D map: column (n) = lane & 15, row (m) = 4 (lane >> 4) + reg
-    if (!active) return;
-    const float u_x = ld_global(alpha_x) / (float)I_x;
-#pragma unroll
-    for (int nt = 0; nt < NT; nt++) {
-        const uint32_t n = n0 + 16u * nt + col;
-        if (n >= N) continue;
-        const float u_w = ld_global(alpha_w + (per_row ? n : 0u)) / (float)I_w;
-        const float bv = bias ? IO<T>::load1(bias, n) : 0.0f;
-#pragma unroll
-        for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const uint32_t mrow = m0 + (uint32_t)WR * wave + 16u * mt + 4u * kg + r;
-                if (mrow < M) i8_sk_store<T>(y, (size_t)mrow * N + n, acc[mt][nt][r], u_x, u_w, bias != nullptr, bv);
-            }
-    }
+    using XS = std::conditional_t<(WAVES > 0), I8Matrix, void>;      // (I8Matrix, as a dependent type: the body's discarded branches)
+    [[maybe_unused]] XS xs;
+    [[maybe_unused]] const int32_t *const wsum = nullptr;
+#include "antq_k_linear8_i8_tile.h"
 }
 
-template <typename T, bool TABLE, int MT, bool DIRECT>
-__global__ void __launch_bounds__(256) ANTQ_I8_KERNEL
-k_linear8_i8_sk(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq, const void *__restrict__ bias, void *__restrict__ y,
-                int *__restrict__ workspace, uint32_t M, uint32_t N, uint32_t K, const float *__restrict__ alpha_w, int per_row, int I_w,
-                const int8_t *__restrict__ image_w, uint32_t m, const float *__restrict__ alpha_x, int I_x, uint32_t per_slice)
+// One (64 output rows n, slice of K, 16 MT rows m0 .. of the A operand) tile of the byte split-K form and its stores: everything
+// of k_linear8_i8_sk but where a piece of the A operand comes from -- the matrix xq [M, K] (XS = I8Matrix, m0 = 0), or whatever
+// xs.load(xq, xn, xkeep) gathers for the next stage, asked in order from the slice's first one (antq_k_conv8_i8.h).  wsum as
+// in antq_k_linear8_i8_tile.h: DIRECT adds 128 wsum[n] in its epilogue, otherwise the slice blockIdx.y == 0 adds it to the partial sums it stores.
+template <typename T, bool TABLE, int MT, bool DIRECT, typename XS>
+__device__ __forceinline__ ANTQ_I8_KERNEL void
+i8b_sk_tile(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq, const void *__restrict__ bias, void *__restrict__ y,
+            int *__restrict__ workspace, uint32_t M, uint32_t N, uint32_t K, const float *__restrict__ alpha_w, int per_row, int I_w,
+            const int8_t *__restrict__ image_w, uint32_t m, const float *__restrict__ alpha_x, int I_x, uint32_t per_slice,
+            const uint32_t m0, XS &xs, const int32_t *__restrict__ wsum)
 {
     constexpr int ROWS = 16 * MT;                      // rows of xq of the workgroup
     constexpr int XROWS = ROWS < 32 ? 32 : ROWS;       // ... of the image: every thread stages (rows >= M are zeros anyway)
@@ -289,21 +149,24 @@ k_linear8_i8_sk(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq
     u32x4_t xn[XL];
     uint32_t xkeep[XL];                                // all ones, or zero for a piece that is zeros: applied at the write
     auto load_x = [&](uint32_t c) __attribute__((always_inline)) {
-        const uint32_t k0 = min(c, c1 - 1u) * (uint32_t)kGemmBK + 16u * xp;
-        const bool kok = k0 < K;
-        const size_t koff = (size_t)min(k0, K - 16u);
+        if constexpr (std::is_same<XS, I8Matrix>::value) {
+            const uint32_t k0 = min(c, c1 - 1u) * (uint32_t)kGemmBK + 16u * xp;
+            const bool kok = k0 < K;
+            const size_t koff = (size_t)min(k0, K - 16u);
 #pragma unroll
-        for (int i = 0; i < XL; i++) {
-            const uint32_t r = xr0 + 32u * i;
-            xn[i] = *(const ANTQ_GLOBAL u32x4_t *)(reinterpret_cast<const char *>(xq) + (size_t)min(r, M - 1u) * K + koff);
-            xkeep[i] = (kok && r < M) ? 0xffffffffu : 0u;
-        }
+            for (int i = 0; i < XL; i++) {
+                const uint32_t r = xr0 + 32u * i;
+                xn[i] = *(const ANTQ_GLOBAL u32x4_t *)(reinterpret_cast<const char *>(xq) + (size_t)min(r, M - 1u) * K + koff);
+                xkeep[i] = (kok && r < M) ? 0xffffffffu : 0u;
+            }
+        } else xs.load(xq, xn, xkeep);                 // (the stages c0, c0 + 1, ... in order, past the slice's end too)
     };
     auto write_x = [&](uint32_t buf) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < XL; i++) {
             const uint32_t r = xr0 + 32u * i;
-            lds.xs[buf][r * PIECES + (xp ^ (r & 7u))] = xn[i] & u32x4_t{xkeep[i], xkeep[i], xkeep[i], xkeep[i]};
+            if constexpr (XS::kFill) lds.xs[buf][r * PIECES + (xp ^ (r & 7u))] = xs.masked(xn[i], xkeep[i]);
+            else lds.xs[buf][r * PIECES + (xp ^ (r & 7u))] = xn[i] & u32x4_t{xkeep[i], xkeep[i], xkeep[i], xkeep[i]};
         }
     };
     // this lane's codes of stage c: the 32 k from 128 c + 32 kg; they count when n < N and k < K (K % 32 == 0: both halves or
@@ -366,6 +229,8 @@ k_linear8_i8_sk(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq
 
     // C / D map: column (n) = lane & 15, row (m) = 4 (lane >> 4) + reg
     if (n >= N) return;
+    int corr = 0;                             // (the offset form) 128 wsum[n], added once: by the DIRECT epilogue, or by slice 0
+    if constexpr (XS::kFill) corr = (wsum && (DIRECT || blockIdx.y == 0u)) ? wsum[n] * 128 : 0;
     if constexpr (DIRECT) {
         const float u_x = ld_global(alpha_x) / (float)I_x;
         const float u_w = ld_global(alpha_w + (per_row ? n : 0u)) / (float)I_w;
@@ -374,8 +239,8 @@ k_linear8_i8_sk(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq
         for (int mt = 0; mt < MT; mt++)
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                const uint32_t mrow = 16u * mt + 4u * kg + r;
-                if (mrow < M) i8_sk_store<T>(y, (size_t)mrow * N + n, acc[mt][r], u_x, u_w, bias != nullptr, bv);
+                const uint32_t mrow = m0 + 16u * mt + 4u * kg + r;
+                if (mrow < M) i8_sk_store<T>(y, (size_t)mrow * N + n, acc[mt][r] + corr, u_x, u_w, bias != nullptr, bv);
             }
     } else {
         int *part = workspace + (size_t)blockIdx.y * M * N + n;
@@ -383,10 +248,21 @@ k_linear8_i8_sk(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq
         for (int mt = 0; mt < MT; mt++)
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                const uint32_t mrow = 16u * mt + 4u * kg + r;
-                if (mrow < M) part[(size_t)mrow * N] = acc[mt][r];
+                const uint32_t mrow = m0 + 16u * mt + 4u * kg + r;
+                if (mrow < M) part[(size_t)mrow * N] = acc[mt][r] + corr;
             }
     }
+}
+
+template <typename T, bool TABLE, int MT, bool DIRECT>
+__global__ void __launch_bounds__(256) ANTQ_I8_KERNEL
+k_linear8_i8_sk(const uint8_t *__restrict__ codes, const int8_t *__restrict__ xq, const void *__restrict__ bias, void *__restrict__ y,
+                int *__restrict__ workspace, uint32_t M, uint32_t N, uint32_t K, const float *__restrict__ alpha_w, int per_row, int I_w,
+                const int8_t *__restrict__ image_w, uint32_t m, const float *__restrict__ alpha_x, int I_x, uint32_t per_slice)
+{
+    I8Matrix xs;
+    i8b_sk_tile<T, TABLE, MT, DIRECT>(codes, xq, bias, y, workspace, M, N, K, alpha_w, per_row, I_w, image_w, m, alpha_x, I_x, per_slice,
+                                      0u, xs, nullptr);
 }
 
 }  // namespace antq

@@ -132,7 +132,7 @@ struct I8Tile {
 
 // The A side of k_linear_i8 itself: xq is a row-major [M, K] matrix, read by i8_tile's own load_x.  Any other A side is a
 // type with load(xq, xn), called once per stage in order, which fills the thread's XL pieces of that stage (antq_k_conv_i8.h).
-struct I8Matrix {};
+struct I8Matrix { static constexpr bool kFill = false; };
 
 // One tile of S = A . V^T and its epilogue, as the header states it: everything of k_linear_i8 but where a piece of the A
 // operand comes from: a row-major matrix xq [M, K] (XS = I8Matrix), or whatever xs.load(xq, xn) gathers for the next stage

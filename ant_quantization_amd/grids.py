@@ -232,3 +232,23 @@ def integer_image(values, limit=127):
         if np.all(np.abs(t - r) <= 1e-5) and r.max() <= 127:
             return I, (r + 0.0).astype(np.int8)        # (+ 0.0: a book's -0 is 0)
     return None
+
+
+def offset_image(values):
+    """(I, int8 array) of a book WITHOUT a negative value whose values are the integers 0 .. I of a unit, I <= 255: array[i] =
+    integer[i] - 128, the offset image antq_conv2d8_i8 takes with x_offset = 128 (ANT's unsigned 8-bit int book: I = 255, the
+    bytes -128 .. 127).  I is found as integer_image finds it, with 255 in place of its limit.  None when a value is negative or
+    not finite, the book is empty or all zero, or there is no such I.  integer_image and its 1 .. 128 limit are untouched."""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    if v.size == 0 or not np.all(np.isfinite(v)) or np.any(v < 0):
+        return None
+    vmax = float(np.max(v))
+    if vmax == 0.0:
+        return None
+    for I in range(1, 256):
+        t = v / vmax * I
+        r = np.rint(t)
+        # (the grids are float32: value and maximum carry 2^-24 each, times I -- above integer_image's 1e-5 from I = 168 on)
+        if np.all(np.abs(t - r) <= max(1e-5, I * 2.0 ** -22)):
+            return I, (r - 128.0).astype(np.int8)
+    return None

@@ -178,6 +178,23 @@ the copy + `antq_quant_i8`, so nothing downstream changes, the split-K routing i
 and so does the one class the copy measured as fast or faster for: bfloat16 / float16 inputs of fewer than 2^16 elements with
 H W % 8 != 0;
 channels-last inputs keep `antq_quant_i8`; with the flag off every launch and every bit is today's.  DESIGN.md 5v.
+
+`integer_conv_bytes=True` (needs fused_linear, fused_bytes, integer_linear, integer_bytes and integer_conv) serves the BYTE-coded
+conv entries -- the conv layers ANT's mixed-precision recipe promotes to 8 bit -- with `antq_conv2d8_i8`: W8A8 on the int8 matrix
+cores.  A byte-coded `Conv2dQuantizer` entry of the ant tree is integer-conv-fusable under integer_conv's conditions (groups,
+C % 32, zero padding by integers, a plain book) when its book has `integer_image8()`; it gets `conv_codes` (the code bytes
+permuted to [N, R, S, C]), `wsum` (int32 [N], the sums of `image[conv_codes]` per output channel, formed in int64 at pack time)
+and `integer` = I_w; neither `conv_codes` nor `wsum` goes into checkpoints, and every other byte-coded conv entry is listed in
+`.integer_skipped` with its reason.  The offset is chosen per call from the input book: `integer_image8()` gives x_offset = 0;
+otherwise `Plan.offset_image()` -- an unsigned book with the integers 0 .. I, I <= 255, which is what a `Conv2dQuantizer`'s
+8-bit input quantiser has -- gives x_offset = 128: the input is quantised to value - 128, the kernel pads with the byte 0x80 and
+adds 128 wsum[n]; `256 * I_w * C R S < 2^31` must hold.  An input book with neither is not served.  The input layout is
+integer_conv's; the routing is the measured one: a call with at most 1024 output rows takes `antq_conv2d8_i8_sk` on the bank's
+workspace with or without `integer_conv_split_k` (it beat the tiled entry at every such point), larger ones `antq_conv2d8_i8`
+(`.int_conv_byte_calls`, `.int_conv_byte_sk_calls`,
+`.int_conv_offset_calls` for the calls that took x_offset = 128; all of them also count in `.int_conv_calls` /
+`.int_conv_sk_calls`).  With the flag off every launch, every bit and every `.integer_skipped` text is today's.
+Measurements and verdict: profiles/int_conv8.md, DESIGN.md 5w.
 """
 from collections import namedtuple
 
@@ -212,6 +229,7 @@ _OPTIONS = (
     _Option("integer_conv", False, ("fused_linear", "integer_linear"), None),
     _Option("integer_conv_split_k", False, ("fused_linear", "integer_linear", "integer_conv"), None),
     _Option("integer_conv_nchw", False, ("fused_linear", "integer_linear", "integer_conv"), None),
+    _Option("integer_conv_bytes", False, ("fused_linear", "fused_bytes", "integer_linear", "integer_bytes", "integer_conv"), None),
 )
 _NOTES = {("PackedBank", "keep_images"): " (nothing else computes from the codes)"}
 
@@ -278,7 +296,7 @@ class PackedBank:
                  byte_codes=False, fused_bytes=False, fused_byte_rows=None, fused_gemm_rows=None, fused_byte_gemm_rows=None,
                  fused_conv1d=False, fused_conv1d_mm=False, fused_conv1d_gemm=False, integer_linear=False,
                  integer_split_k=False, integer_bytes=False, integer_conv=False, integer_conv_split_k=False,
-                 integer_conv_nchw=False):
+                 integer_conv_nchw=False, integer_conv_bytes=False):
         """codes: {layer name: uint8 tensor} -- stored codes to attach instead of encoding the weights (load_packed_state_dict);
         a layer's code width is then the one its stored size says (numel / 2 bytes: 4-bit, numel bytes: byte codes).
         Every other parameter: see the module docstring."""
@@ -306,6 +324,9 @@ class PackedBank:
         self.int_conv_sk_calls = 0  # ... of them through antq_conv2d4_i8_sk (integer_conv_split_k)
         self.int_conv_relayouts = 0  # ... of them whose input was copied to channels-last memory first
         self.int_conv_nchw_calls = 0  # ... of them whose contiguous NCHW input antq_quant_i8_nhwc quantised (integer_conv_nchw)
+        self.int_conv_byte_calls = 0  # ... of int_conv_calls, those from byte codes: antq_conv2d8_i8 (or _sk) (integer_conv_bytes)
+        self.int_conv_byte_sk_calls = 0  # ... of them through antq_conv2d8_i8_sk
+        self.int_conv_offset_calls = 0  # ... of int_conv_byte_calls, those with an unsigned input image: x_offset = 128
         self._sk_workspace = {}    # device -> the one workspace of antq_linear4_i8_sk / antq_linear8_i8_sk / antq_conv2d4_i8_sk, grown on demand
         self.launches = 0          # decode launches so far (one per (device, dtype, pair rule, code width) group and refresh)
         self.dirty = True
@@ -358,13 +379,23 @@ class PackedBank:
                         integer = plan.integer_image()[0]
                     else:
                         self.integer_skipped.append((name, why))
+                conv_codes = wsum = None   # (integer_conv) the codes in tap-major order, when the entry is integer-conv-fusable
+                if self.integer_conv_bytes and width == 8 and w.dim() == 4:
+                    # (integer_conv_bytes) a byte-coded conv entry: the bytes tap-major, and the sums of its image per channel
+                    why = ("not a Conv2dQuantizer of the ant tree" if not _is_ant_conv2d(mod)
+                           else self._conv_integer_refusal(mod, tuple(w.shape), plan, ovp, width, bytes_too=True))
+                    if why is None:
+                        integer = plan.integer_image8()[0]
+                        conv_codes = _tap_major_bytes(c, tuple(w.shape))
+                        wsum = _image_sums(conv_codes, plan.integer_image8()[1], w.shape[0])
+                    else:
+                        self.integer_skipped.append((name, why))
                 elif self.integer_linear and self.integer_bytes and width == 8:
                     why = self._byte_integer_refusal(mod, w, plan, ovp, kind == "linear" and fusable)
                     if why is None:
                         integer = plan.integer_image8()[0]
                     else:
                         self.integer_skipped.append((name, why))
-                conv_codes = None          # (integer_conv) the codes in tap-major order, when the entry is integer-conv-fusable
                 if self.integer_conv and w.dim() == 4 and not (self.integer_bytes and width == 8):      # (those are listed above)
                     why = ("not a Conv2dQuantizer of the ant tree" if not _is_ant_conv2d(mod)
                            else self._conv_integer_refusal(mod, tuple(w.shape), plan, ovp, width))
@@ -372,7 +403,7 @@ class PackedBank:
                         integer, conv_codes = plan.integer_image()[0], _tap_major(c, tuple(w.shape))
                     else:
                         self.integer_skipped.append((name, why))
-                self.entries[id(q)] = dict(name=name, q=q, mod=mod, rows=rows, row_len=row_len, per_row=per_row, codes=c, width=width, conv_codes=conv_codes,
+                self.entries[id(q)] = dict(name=name, q=q, mod=mod, rows=rows, row_len=row_len, per_row=per_row, codes=c, width=width, conv_codes=conv_codes, wsum=wsum,
                                            fusable=fusable, kind=kind, shape=tuple(w.shape), dtype=w.dtype, device=w.device, integer=integer,
                                            out=torch.empty_like(w, memory_format=torch.contiguous_format) if image else None)
             if not self.entries:
@@ -414,10 +445,10 @@ class PackedBank:
         return None
 
     @staticmethod
-    def _conv_integer_refusal(mod, shape, plan, ovp, width):
+    def _conv_integer_refusal(mod, shape, plan, ovp, width, bytes_too=False):
         """(integer_conv) Why the entry of an ANT Conv2dQuantizer `mod` with weight [N, C, R, S] is not integer-conv-fusable
-        (None: it is)."""
-        if width != 4:
+        (None: it is).  bytes_too (integer_conv_bytes): byte codes are allowed, and then the book needs integer_image8()."""
+        if width != 4 and not (bytes_too and width == 8):
             return "byte codes"
         if mod.groups != 1:
             return "groups = %d" % mod.groups
@@ -429,7 +460,7 @@ class PackedBank:
             return "padding %r (%s) is not zero padding by integers" % (pad, getattr(mod, "padding_mode", "zeros"))
         if ovp:
             return "a pair-rule book does not survive the tap-major order"
-        if plan.integer_image() is None:
+        if (plan.integer_image8() if width == 8 else plan.integer_image()) is None:
             return "the weight's codebook has no integer image"
         return None
 
@@ -712,9 +743,13 @@ class PackedBank:
                 and (bias is None or (bias.dtype == input.dtype and bias.is_contiguous() and bias.device == input.device))):
             return None
         plan_x, gmax_x, nn_x, ovp_x = _codebook(qi)
-        image_x = plan_x.integer_image()
-        if image_x is None or ovp_x or image_x[0] * e["integer"] * C * R * S >= 2 ** 31:
+        wide = e["width"] == 8             # (integer_conv_bytes) byte codes: images with I up to 128, or the input's offset image
+        image_x, x_offset = (plan_x.integer_image8() if wide else plan_x.integer_image()), 0
+        if wide and image_x is None:
+            image_x, x_offset = plan_x.offset_image(), 128     # (an unsigned book 0 .. I, I <= 255: value - 128, 128 wsum added)
+        if image_x is None or ovp_x or (256 if x_offset else image_x[0]) * e["integer"] * C * R * S >= 2 ** 31:
             return None
+        image_key = "offset" if x_offset else 128 if wide else 127
         B, _, H, W = input.shape
         (sh, sw), (ph, pw), (dh, dw) = _lib._pair(mod.stride), _lib._pair(mod.padding), _lib._pair(mod.dilation)
         Ho, Wo = (H + 2 * ph - dh * (R - 1) - 1) // sh + 1, (W + 2 * pw - dw * (S - 1) - 1) // sw + 1
@@ -736,11 +771,14 @@ class PackedBank:
         dev = e["device"]
         self._integer_units(e, qi, plan_w, gmax_w, plan_x, gmax_x)
         if nchw:
-            xq = _lib.quant_i8_nhwc(input, e["alpha_x"], plan_x, gmax_x, plan_x.image_dev(dev))
+            xq = _lib.quant_i8_nhwc(input, e["alpha_x"], plan_x, gmax_x, plan_x.image_dev(dev, image_key))
             self.int_conv_nchw_calls += 1
         else:
-            xq = _lib.quant_i8(input.permute(0, 2, 3, 1), e["alpha_x"], plan_x, gmax_x, 1, input.numel(), False, plan_x.image_dev(dev))
+            xq = _lib.quant_i8(input.permute(0, 2, 3, 1), e["alpha_x"], plan_x, gmax_x, 1, input.numel(), False,
+                               plan_x.image_dev(dev, image_key))
         self.int_conv_calls += 1
+        if wide:
+            return self._integer_conv_byte_call(e, mod, xq, plan_w, image_x[0], x_offset, B * Ho * Wo)
         args = (e["conv_codes"], xq, e["unit_w"], plan_w.image_dev(dev), e["integer"], e["unit_x"], image_x[0], N, (R, S), (sh, sw), (ph, pw),
                 (dh, dw), e["per_row"], e["dtype"])
         bias = None if bias is None else bias.detach()
@@ -754,6 +792,27 @@ class PackedBank:
             self.int_conv_sk_calls += 1
             return _lib.int_conv2d4_sk(*args, bias=bias, workspace=ws)
         return _lib.int_conv2d4(*args, bias=bias)
+
+    def _integer_conv_byte_call(self, e, mod, xq, plan_w, I_x, x_offset, M):
+        """(integer_conv_bytes) integer_conv_call's product for a byte-coded entry: antq_conv2d8_i8, or its split-K form."""
+        N, C, R, S = e["shape"]
+        dev = e["device"]
+        args = (e["conv_codes"], xq, e["unit_w"], plan_w.image_dev(dev, 128), plan_w.integer_image8()[1], e["integer"], e["unit_x"], I_x,
+                N, (R, S), _lib._pair(mod.stride), _lib._pair(mod.padding), _lib._pair(mod.dilation), e["per_row"], e["dtype"])
+        kw = dict(bias=None if mod.bias is None else mod.bias.detach(), x_offset=x_offset, wsum=e["wsum"] if x_offset else None)
+        self.int_conv_byte_calls += 1
+        self.int_conv_offset_calls += 1 if x_offset else 0
+        # the measured rule (profiles/int_conv8.md): up to 1024 rows the split-K entry beat the tiled one at all 44 points, the
+        # one-slice ones included, so byte-coded calls take it with or without integer_conv_split_k
+        if M <= _lib.CONV2D8_I8_SK_MAX_M:
+            need = _lib.int_conv2d8_sk_workspace_bytes(M, N, C * R * S, dev)
+            ws = self._sk_workspace.get(dev)
+            if ws is None or ws.numel() < need:
+                ws = self._sk_workspace[dev] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+            self.int_conv_sk_calls += 1
+            self.int_conv_byte_sk_calls += 1
+            return _lib.int_conv2d8_sk(*args, workspace=ws, **kw)
+        return _lib.int_conv2d8(*args, **kw)
 
     def _integer_byte_call(self, e, mod, xq, plan_w, I_x, M):
         """(integer_bytes) integer_linear_call's product for a byte-coded entry: antq_linear8_i8, or its split-K form."""
@@ -822,6 +881,21 @@ def _tap_major(codes, shape):
     return (nib[:, 0] | (nib[:, 1] << 4)).contiguous()
 
 
+def _tap_major_bytes(codes, shape):
+    """The byte codes of a conv weight [N, C, R, S] (encode8's layout: one byte per element) re-ordered to [N, R, S, C], as
+    antq_conv2d8_i8 reads them."""
+    N, C, R, S = shape
+    return codes.reshape(N, C, R, S).permute(0, 2, 3, 1).contiguous().reshape(-1)
+
+
+def _image_sums(conv_codes, image, N):
+    """wsum of antq_conv2d8_i8: int32 [N], the sum of image[code] over each output channel's codes (a code past the image
+    counts 0), formed in int64 on the codes' device."""
+    table = torch.zeros(256, dtype=torch.int64)
+    table[:len(image)] = torch.from_numpy(np.asarray(image, dtype=np.int64))
+    return table.to(conv_codes.device)[conv_codes.reshape(N, -1).long()].sum(dim=1).to(torch.int32).contiguous()
+
+
 def _is_ant_conv2d(mod):
     """Whether `mod` is the ant tree's Conv2dQuantizer (OliVe's wrapper is out of integer_conv's scope)."""
     from .ant.quant_modules import Conv2dQuantizer
@@ -854,7 +928,7 @@ def pack_model(model, release_weights=False, **options):
     """Encode every suitable calibrated weight of `model` as 4-bit codes and serve the layers from one batched decode
     (PackedBank).  Returns the bank; `.skipped` lists the layers that stay float, with reasons.
     options: fused_linear, keep_images, fused_rows, byte_codes, fused_bytes, fused_byte_rows, fused_gemm_rows,
-    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes, integer_conv, integer_conv_split_k, integer_conv_nchw -- PackedBank's keywords with its defaults; see the module docstring."""
+    fused_byte_gemm_rows, fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes, integer_conv, integer_conv_split_k, integer_conv_nchw, integer_conv_bytes -- PackedBank's keywords with its defaults; see the module docstring."""
     return PackedBank(model, release_weights, None, **options)     # (codes: not an option here -- given, it is a TypeError)
 
 
@@ -883,7 +957,7 @@ def load_packed_state_dict(model, sd, release_weights=True, **options):
     any other size raises AntqError naming the layer), and the weights are materialised by the batched decode
     (release_weights=False: copied into the layers' own float weights instead of replacing them).
     options: fused_linear, keep_images, fused_rows, fused_bytes, fused_byte_rows, fused_gemm_rows, fused_byte_gemm_rows,
-    fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes, integer_conv, integer_conv_split_k, integer_conv_nchw, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
+    fused_conv1d, fused_conv1d_mm, fused_conv1d_gemm, integer_linear, integer_split_k, integer_bytes, integer_conv, integer_conv_split_k, integer_conv_nchw, integer_conv_bytes, as in pack_model (no byte_codes: the code width comes from the stored size).  Returns the bank."""
     _check_options("load_packed_state_dict", **options)        # (before the model is touched)
     suffix = "." + CODES_KEY
     codes = {k[:-len(suffix)]: v for k, v in sd.items() if k.endswith(suffix)}

@@ -1074,6 +1074,61 @@ int antq_conv2d4_i8_sk(const uint8_t *codes_dev /* N*R*S*C/2 bytes */, const int
                        unsigned flags /* 0 */, int dtype /* F32 | BF16 | F16: y and bias */, void *stream);
 
 /* -------------------------------------------------------------------------
+ * antq_conv2d8_i8 and antq_conv2d8_i8_sk: the integer-domain conv2d from BYTE codes (W8A8 on the int8 matrix cores), for the
+ * conv layers a mixed-precision model promotes to 8 bit -- antq_conv2d4_i8's contract with antq_linear8_i8's codes.
+ * codes_dev: one byte per weight in the order [N = Cout][R][S][C] (tap-major), K = R S C; image_w_host / image_w_dev / m and the
+ * decode kinds (XOR, TABLE) as for antq_linear8_i8.  With v[n, r, s, c] = image_w[code] (a code >= m reads 0; plain books, m <= 256)
+ *     S[(b, ho, wo), n] = sum over r, s, c of X[b, hi, wi, c] * v[n, r, s, c]
+ *     X = xq + x_offset inside the image, X = 0 for a tap outside it        (hi, wi, Ho, Wo as for antq_conv2d4_i8)
+ *     y[b, ho, wo, n]   = round_dtype( fl32( fl32( fl32( fl32(S) * u_x ) * u_w[n] ) + fl32(bias[n]) ) )      as antq_conv2d4_i8
+ * x_offset == 0: xq holds the values -I_x .. I_x of a signed image, I_x in 1 .. 128 (xq may hold -128).
+ * x_offset == 128: xq holds value - 128 of an UNSIGNED image 0 .. I_x, I_x in 1 .. 255 -- ANT's unsigned 8-bit book, the input
+ * of nearly every conv layer of a CNN.  antq_quant_i8 and antq_quant_i8_nhwc write such an xq when given the image
+ * image[code] = value(code) - 128: the byte of an element is image[its code] whatever the element, and the zero code is looked
+ * up like any other, so an element that encodes to the value 0 gives -128 and one at or beyond the clip gives I_x - 128.
+ * The kernels fill every piece of xq that does not count -- a tap outside the
+ * image, m >= M, k >= K -- with the byte 0x80 instead of 0, so that X = 0 there, and add 128 * wsum[n] to the int32 sum as an
+ * integer before fl32(S).  wsum_dev: int32 [N], wsum[n] = sum over r, s, c of v[n, r, s, c] -- the caller's array, computed once
+ * when the weight is packed; the kernels do not verify it.  A codes piece with k >= K or n >= N is an exact zero, so the fill
+ * never reaches a result through the K tail.  S is an exact integer and has no order: the bits of an output depend on its
+ * receptive field, row n of the codes, wsum[n], the scales and the bias -- not on the tile, the slices, the decode kind, B, N or
+ * the run; with x_offset == 0 a 1 x 1 / stride 1 / pad 0 call gives antq_linear8_i8's bits.
+ * Refusals: antq_conv2d4_i8's, in its order, with these differences:
+ *   ANTQ_ERR_ARG          image_w_host null as well; x_offset neither 0 nor 128; wsum_dev null while x_offset == 128
+ *                         (checked with the null pointers, before dtype and flags)
+ *   ANTQ_ERR_UNSUPPORTED  in place of the 4-bit book refusals: ANTQ_FLAG_OVP, m > 256; I_w outside 1 .. 128; I_x outside
+ *                         1 .. 128 (x_offset == 0) or 1 .. 255 (x_offset == 128); x_offset == 0: I_x * I_w * K >= 2^31;
+ *                         x_offset == 128: 256 * I_w * K >= 2^31 (it bounds |S'| + |128 wsum|: no intermediate leaves int32
+ *                         wherever the correction is added)
+ *   ANTQ_ERR_ALIGN        wsum_dev not 4-byte aligned as well
+ * antq_conv2d8_i8_sk, _sk_slices and _sk_workspace_bytes are to antq_conv2d8_i8 what antq_conv2d4_i8_sk and its helpers are to
+ * antq_conv2d4_i8: the same bits, outputs of 1 .. ANTQ_CONV2D8_I8_SK_MAX_M rows, and after the checks above its three trailing
+ * ones in its order (the row limit and the finish's grid, the workspace's alignment, the workspace's size -- the one check after
+ * the device is asked).  The slice rule is antq_linear8_i8_sk's byte rule counting ceil(N / 64) ceil(M / 64) workgroups per
+ * slice, cap K / (8 min(M, 64)).  The slice 0 adds 128 * wsum[n] to the partial sums it stores; with one slice the launch adds
+ * it itself.  antq_debug_set keys 23 (tile) and 24 (slices) act as on the other integer entries.  One or two launches,
+ * stream-ordered, capturable; no atomics, no allocation.  Kernels: csrc/antq_k_conv8_i8.h.  Measurements: profiles/int_conv8.md.
+ * ------------------------------------------------------------------------- */
+#define ANTQ_CONV2D8_I8_MAX_DIM ANTQ_CONV2D4_I8_MAX_DIM
+#define ANTQ_CONV2D8_I8_MAX_M ANTQ_CONV2D4_I8_MAX_M
+#define ANTQ_CONV2D8_I8_MAX_XQ_BYTES ANTQ_CONV2D4_I8_MAX_XQ_BYTES
+#define ANTQ_CONV2D8_I8_SK_MAX_M 1024
+int antq_conv2d8_i8(const uint8_t *codes_dev /* N*R*S*C bytes, [N][R][S][C] */, const int8_t *xq_dev /* [B, H, W, C] */,
+                    const void *bias_dev /* N or NULL */, void *y_dev /* [B, Ho, Wo, N] */, size_t B, size_t H, size_t W, size_t C,
+                    size_t N, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                    const float *alpha_w_dev, int alpha_per_row, int I_w, const int8_t *image_w_host /* m bytes */,
+                    const int8_t *image_w_dev /* the same m bytes */, int m, const float *alpha_x_dev /* one float */, int I_x,
+                    int x_offset /* 0 or 128 */, const int32_t *wsum_dev /* int32 [N], or NULL when x_offset == 0 */,
+                    unsigned flags /* 0 */, int dtype /* F32 | BF16 | F16: y and bias */, void *stream);
+int antq_conv2d8_i8_sk_slices(size_t M, size_t N, size_t K, int cus);
+size_t antq_conv2d8_i8_sk_workspace_bytes(size_t M, size_t N, size_t K);
+int antq_conv2d8_i8_sk(const uint8_t *codes_dev, const int8_t *xq_dev, const void *bias_dev, void *y_dev, size_t B, size_t H, size_t W,
+                       size_t C, size_t N, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                       const float *alpha_w_dev, int alpha_per_row, int I_w, const int8_t *image_w_host, const int8_t *image_w_dev,
+                       int m, const float *alpha_x_dev, int I_x, int x_offset, const int32_t *wsum_dev, void *workspace_dev,
+                       size_t workspace_bytes, unsigned flags /* 0 */, int dtype /* F32 | BF16 | F16: y and bias */, void *stream);
+
+/* -------------------------------------------------------------------------
  * antq_quant_i8_nhwc: antq_quant_i8 of a CONTIGUOUS NCHW activation, written in NHWC order -- the xq operand of antq_conv2d4_i8
  * and antq_conv2d4_i8_sk without a channels-last copy in front.  x_dev: [B, C, P] contiguous (P = H W), q_dev: int8 [B, P, C].
  *     q[b, p, c] = the byte antq_quant_i8 writes for the element x[b, c, p] with rows = 1, the same one alpha, no pair rule

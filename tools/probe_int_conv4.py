@@ -143,9 +143,45 @@ def write_md_nchw(rows, path, args):
         f.write("\n".join(out))
 
 
+def write_md_bytes(rows, path, args):
+    """--bytes: I8 and K8 (offset form) against A on the kept 8-bit image, I4 for scale"""
+    out = ["# antq_conv2d8_i8 / antq_conv2d8_i8_sk (W8A8, unsigned 8-bit activations) against today's forward of a byte-coded Conv2d layer", "",
+           "Written by `tools/probe_int_conv4.py --bytes`: one MI355X, one process; the protocol of profiles/int_conv4.md (every arm from "
+           "the RAW input, distinct weight buffers in rotation, per point %d repetitions of one graph-replayed batch of calls per arm, "
+           "the arms alternated inside a repetition; medians in us per call, `spread` = the largest (max - min) / median of the point's "
+           "arms).  Signed int8 weights (XOR kind), unsigned int8 activations (x_offset = 128), bias.  I8 = antq_quant_i8 + "
+           "antq_conv2d8_i8 from a channels-last input, K8 = the same through antq_conv2d8_i8_sk (M <= 1024; `S` = its slices), A = "
+           "antq_fakequant + F.conv2d on the kept 8-bit image with the faster input layout, I4 = antq_quant_i8 + antq_conv2d4_i8 at "
+           "the same shape.  Ratios are TIMES: below 1, the first is faster.  `won` / `lost`: by more than the point's spread." % args.reps, ""]
+    for dt in sorted({r["dtype"] for r in rows}):
+        rs = [r for r in rows if r["dtype"] == dt]
+        out += ["## %s" % dt, "", "| ratio | points | won | lost | range |", "|---|---|---|---|---|"]
+        for k, name, sel in (("i8_over_a", "I8 / A", rs), ("k8_over_a", "K8 / A", [r for r in rs if r["slices"]]),
+                             ("k8_over_i8", "K8 / I8, the rule splits", [r for r in rs if r["slices"] > 1]),
+                             ("k8_over_i8", "K8 / I8, one slice", [r for r in rs if r["slices"] == 1]), ("i8_over_i4", "I8 / I4", rs)):
+            if sel:
+                out.append("| %s | %d | %d | %d | %s |" % (name, len(sel), sum(r[k] < 1 - r["spread"] for r in sel),
+                                                         sum(r[k] > 1 + r["spread"] for r in sel), _range([r[k] for r in sel])))
+        out += ["", "I8 reaches %s TOP/s.  The largest spread of a point is %.1f %%." % (_range([r["tops"] for r in rs]), 100 * max(r["spread"] for r in rs)), "",
+                "| C -> N, k / stride, input | B | M | K | S | I8 | K8 | A | A in | I4 | I8 / A | K8 / A | K8 / I8 | I8 / I4 | spread |",
+                "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+        f = lambda v, p: "-" if v is None else p % v
+        for r in rs:
+            out.append("| %d -> %d, %d / %d, %d x %d | %d | %d | %d | %d | %.1f | %s | %.1f | %s | %.1f | %.2f | %s | %s | %.2f | %.1f %% |" % (
+                r["C"], r["N"], r["k"], r["stride"], r["H"], r["H"], r["B"], r["M"], r["K"], r["slices"], r["us_i8"], f(r["us_k8"], "%.1f"),
+                r["us_a"], r["a_layout"], r["us_i4"], r["i8_over_a"], f(r["k8_over_a"], "%.2f"), f(r["k8_over_i8"], "%.2f"), r["i8_over_i4"],
+                100 * r["spread"]))
+        out.append("")
+    if args.notes and os.path.exists(args.notes):
+        out += [open(args.notes).read()]
+    with open(path, "w") as f:
+        f.write("\n".join(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nchw", action="store_true", help="the quantiser arms Q0 / Q1 / Q2 and the whole call IN / IN2 / A from an NCHW input")
+    ap.add_argument("--bytes", action="store_true", help="W8A8: I8 / K8 (antq_conv2d8_i8 / _sk, offset form) against A on the 8-bit image and I4")
     ap.add_argument("--sk", action="store_true", help="the split-K arm K against I and A, at the points of at most CONV2D4_I8_SK_MAX_M rows")
     ap.add_argument("--force", type=int, default=0, help="(--sk) slices forced with antq_debug_set key 24")
     ap.add_argument("--every", type=int, default=1, help="(--sk) every n-th shape only")
@@ -164,7 +200,7 @@ def main():
         if a.out:
             with open(a.out + ".json", "w") as f:
                 json.dump(rows, f, indent=1)
-        (write_md_nchw if a.nchw else write_md_sk if a.sk else write_md)(rows, (a.out or os.path.splitext(a.rewrite)[0]) + ".md", a)
+        (write_md_bytes if a.bytes else write_md_nchw if a.nchw else write_md_sk if a.sk else write_md)(rows, (a.out or os.path.splitext(a.rewrite)[0]) + ".md", a)
         return
     if not torch.cuda.is_available():
         raise SystemExit("probe_int_conv4: no GPU -- nothing is measured without one")
@@ -174,6 +210,12 @@ def main():
     gmax_w, gmax_x = float(gw.max()), float(gx.max())
     (I_w, _), (I_x, _) = plan_w.integer_image(), plan_x.integer_image()
     img_w, img_x = plan_w.image_dev(dev), plan_x.image_dev(dev)
+    if a.bytes:
+        gw8, gx8 = grids.ant_grid("int", 8, True), grids.ant_grid("int", 8, False)
+        plan_w8, plan_x8 = _lib.plan_for(gw8), _lib.plan_for(gx8)
+        gmax_w8, gmax_x8 = float(gw8.max()), float(gx8.max())
+        (I_w8, host8), I_x8 = plan_w8.integer_image8(), plan_x8.offset_image()[0]
+        img_w8, img_x8 = plan_w8.image_dev(dev, 128), plan_x8.image_dev(dev, "offset")
     rows = []
     for dt in ((getattr(torch, a.dtype),) if a.dtype else (torch.bfloat16,) if a.quick else (torch.float32, torch.bfloat16)):
         esz = torch.empty(0, dtype=dt).element_size()
@@ -213,6 +255,53 @@ def main():
                                    out=dst.permute(0, 2, 3, 1) if last else dst)
                     return F.conv2d(dst, images[i], bias, stride, pad)
 
+                if a.bytes:
+                    # W8A8: signed int8 weights (the XOR kind), unsigned int8 activations -- the offset form, x_offset = 128
+                    if B == (8 if a.quick else BATCHES[0]):       # (the shape's first batch: its byte-coded weight)
+                        w8 = (torch.randn(N, C, k, k, device=dev) * 0.05).to(dt)
+                        alpha8 = (w8.float().abs().amax((1, 2, 3)) * 0.9).contiguous()
+                        codes8 = _lib.encode8(w8, alpha8, plan_w8, gmax_w8, N, K, True)
+                        image8 = _lib.decode8(codes8, alpha8, plan_w8, gmax_w8, N, K, True, dt).view(N, C, k, k)
+                        taps8 = packed._tap_major_bytes(codes8, (N, C, k, k))
+                        wsum = packed._image_sums(taps8, host8, N)
+                        unit_w8 = packed._unit_alpha(alpha8, plan_w8, gmax_w8)
+                    n_buf8 = int(min(iters, max(2, -(-ROTATE_BYTES // (K * N)))))
+                    images8, tap8s = [image8.clone() for _ in range(n_buf)], [taps8.clone() for _ in range(n_buf8)]
+                    unit_x8 = packed._unit_alpha(ax, plan_x8, gmax_x8)
+                    use_sk = M <= _lib.CONV2D8_I8_SK_MAX_M
+                    ws = torch.empty(max(_lib.int_conv2d8_sk_workspace_bytes(M, N, K), 16) if use_sk else 16, dtype=torch.uint8, device=dev)
+
+                    def bytes8(fn, i, **kw):
+                        _lib.quant_i8(x_cl.permute(0, 2, 3, 1), ax, plan_x8, gmax_x8, 1, x_cl.numel(), False, img_x8, out=xq)
+                        return fn(tap8s[i % n_buf8], xq, unit_w8, img_w8, host8, I_w8, unit_x8, I_x8, N, k, stride, pad, 1, True, dt, bias=bias,
+                                  out=y, x_offset=128, wsum=wsum, **kw)
+
+                    def image8bit(src, dst, i):
+                        last = not src.is_contiguous()
+                        _lib.fakequant(src.permute(0, 2, 3, 1) if last else src, ax, plan_x8, gmax_x8, 1, src.numel(), False,
+                                       out=dst.permute(0, 2, 3, 1) if last else dst)
+                        return F.conv2d(dst, images8[i], bias, stride, pad)
+
+                    graphs = {"I8": capture(lambda i: bytes8(_lib.int_conv2d8, i), n_buf, iters, 3),
+                              "A": capture(lambda i: image8bit(x, xf, i), n_buf, iters, 3),
+                              "ACL": capture(lambda i: image8bit(x_cl, xf_cl, i), n_buf, iters, 3),
+                              "I4": capture(lambda i: integer(x_cl, i), n_buf, iters, 3)}
+                    if use_sk:
+                        graphs["K8"] = capture(lambda i: bytes8(_lib.int_conv2d8_sk, i, workspace=ws), n_buf, iters, 3)
+                    t = alternate(graphs, iters, a.reps)
+                    us = {key: v[0] for key, v in t.items()}
+                    us_a = min(us["A"], us["ACL"])
+                    r = dict(dtype=str(dt).split(".")[1], C=C, N=N, k=k, stride=stride, H=H, B=B, M=M, K=K, calls=iters,
+                             slices=_lib.int_conv2d8_sk_slices(M, N, K) if use_sk else 0, us_i8=round(us["I8"], 2),
+                             us_k8=round(us["K8"], 2) if use_sk else None, us_a=round(us_a, 2), us_i4=round(us["I4"], 2),
+                             a_layout="NCHW" if us["A"] <= us["ACL"] else "channels-last", i8_over_a=round(us["I8"] / us_a, 3),
+                             k8_over_a=round(us["K8"] / us_a, 3) if use_sk else None, k8_over_i8=round(us["K8"] / us["I8"], 3) if use_sk else None,
+                             i8_over_i4=round(us["I8"] / us["I4"], 3), tops=round(2.0 * M * N * K / (us["I8"] * 1e-6) / 1e12, 1),
+                             spread=round(max(v[1] for v in t.values()), 4))
+                    rows.append(r)
+                    print(json.dumps(r), flush=True)
+                    del graphs, t, images, taps, images8, tap8s
+                    continue
                 if a.sk:
                     _lib.lib().antq_debug_set(24, a.force)
                     slices = _lib.lib().antq_conv2d4_i8_sk_slices(M, N, K, 0)
@@ -288,7 +377,7 @@ def main():
                 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
                 with open(a.out + ".json", "w") as f:
                     json.dump(rows, f, indent=1)
-                (write_md_nchw if a.nchw else write_md_sk if a.sk else write_md)(rows, a.out + ".md", a)
+                (write_md_bytes if a.bytes else write_md_nchw if a.nchw else write_md_sk if a.sk else write_md)(rows, a.out + ".md", a)
 
 
 if __name__ == "__main__":
